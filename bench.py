@@ -11,10 +11,17 @@ packed moments, the device solves, weights back on the host.  With N ranks the n
 contiguously across the ranks (``sample_device(row0=...)``: the data do not depend on N; total work fixed ->
 "scaling": "strong").  Rank 0 prints ONE JSON line.
 
-Parity gate: before anything is printed the fitted model is checked on the very views that were timed
-(``check_fit_properties``): rows regenerated on the host by the NumPy restatement of the generator, K1 against a
-float64 Gram of those rows, and the size-independent properties of a CCA solution on all n rows.  A failed gate
-aborts the run (no JSON line).
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.  ``--dump-outputs DIR``
+then writes what the last timed fit returned (weights, means, singular values) as ``DIR/<name>.npy``: the inputs are a
+fixed, seeded data set, so two builds can be compared output for output.
+
+``--full`` adds everything else the benchmark measures or checks, after the timed steps:
+
+* parity gate: the fitted model is checked on the very views that were timed (``check_fit_properties``): rows
+  regenerated on the host by the NumPy restatement of the generator, K1 against a float64 Gram of those rows, and the
+  size-independent properties of a CCA solution on all n rows.  A failed gate aborts the run (no JSON line);
+* the extra configurations (``extra``: K1 routes, DCCA loss, transform, grid search, host inputs, BASELINE configs,
+  dense EVD; ``--no-extras`` / ``--only`` narrow them) and the CPU baselines (``cpu_baseline``; ``--no-cpu-baseline``).
 """
 
 from __future__ import annotations
@@ -37,6 +44,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity gate, the extra configurations and the CPU baselines "
+                         "(a plain run only times the headline fit)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed fit returned (weights, means, singular values) as DIR/<name>.npy")
     ap.add_argument("--rows", dest="n", type=int, default=1_000_000)
     ap.add_argument("--d", "--dim", dest="d", type=int, default=4096)
     ap.add_argument("--k", type=int, default=64)
@@ -47,21 +59,40 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the extra configurations (C2, C3, C5, f64, losses, grid search)")
     ap.add_argument("--no-dcca", action="store_true")
     ap.add_argument("--with-sharded-dcca", action="store_true",
-                    help="N > 1 only: also time CCALoss fwd+bwd on the batch sharded over the ranks (extra collectives "
+                    help="N > 1 with --full only: also time CCALoss fwd+bwd on the batch sharded over the ranks (extra collectives "
                          "after the timed fits; off by default so that nothing can delay the headline result)")
     ap.add_argument("--no-cpu-mcca", action="store_true",
                     help="skip the reference-structured MCCA / GCCA comparators (BASELINE configs[2] / [4] on bounded samples: ~1 min of CPU)")
     ap.add_argument("--cpu-mcca", action="store_true", help="(kept for compatibility: the MCCA comparator is on by default)")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of the rCCA CPU comparator's sample (0: 2 d)")
     ap.add_argument("--cpu-runs", type=int, default=3, help="repeats of the rCCA CPU comparator at n = 2 d (a run is ~25 s; the median is reported)")
-    ap.add_argument("--no-gates", action="store_true", help="skip the parity gates of the extras (the headline gate always runs)")
+    ap.add_argument("--no-gates", action="store_true", help="skip the parity gates of the extras (under --full the headline gate always runs)")
     ap.add_argument("--only", default="", help="comma-separated subset of the extras to run (routes, transform, dcca, grid, host, metric_loss, configs, evd)")
     ap.add_argument("--transport", choices=["torch", "ccz", "gloo-staged"], default=os.environ.get("CCZ_BENCH_TRANSPORT", "torch"),
                     help="exchange step of the sharded fit: torch.distributed (nccl = RCCL) all-reduces, or libccz's own RCCL collective "
                          "behind the C ABI (ccz_moments_exchange); both run the two-part exchange that overlaps the factorization")
     ap.add_argument("--launch-test", action="store_true",
                     help="(CPU test of the launcher) rendezvous over gloo, one all-reduce, ONE JSON line on rank 0; no GPU work")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(model, out_dir):
+    """What a caller of the timed path receives from ``CCA.fit``: the weights and means of every view and the canonical
+    correlations, one float32 / float64 ``.npy`` file each (2 x 4096 x 64 fp32 weights at the metric shape: 2 MB)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"weights_{i}": w for i, w in enumerate(model.weights_)}
+    arrays.update({f"means_{i}": m for i, m in enumerate(model.means_)})
+    arrays["singular_values"] = model.singular_values_
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
 
 
 def dist_all_reduce(t, op=None):
@@ -1394,16 +1425,19 @@ def main():
         dist_all_reduce(gt)
         k1_ms_per_rank = [float(x) for x in gt.cpu().tolist()]
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(model, a.dump_outputs)
+
     # ---- parity gate on the views that were timed (every rank takes part: transform / score all-reduce) ----
-    gate = check_fit_properties(model, views, jd, seed=DATA_SEED, row0=lo, sharded=distributed)
-    if not gate["ok"]:
+    gate = check_fit_properties(model, views, jd, seed=DATA_SEED, row0=lo, sharded=distributed) if a.full else None
+    if gate is not None and not gate["ok"]:
         sys.stderr.write("bench.py: PARITY GATE FAILED on the timed model: " + json.dumps(gate) + "\n")
         if distributed:
             dist.destroy_process_group()
         sys.exit(3)
 
     sharded_loss_s = None
-    if distributed and (a.with_sharded_dcca or os.environ.get("CCZ_BENCH_FORCE_SHARDED")) and 8.0 * n_local * a.d * 4 < 150e9:
+    if a.full and distributed and (a.with_sharded_dcca or os.environ.get("CCZ_BENCH_FORCE_SHARDED")) and 8.0 * n_local * a.d * 4 < 150e9:
         del views
         torch.cuda.empty_cache()
         views = None
@@ -1462,7 +1496,7 @@ def main():
             extra["dcca_loss_metric_shape_sharded"] = {
                 "metric": f"DCCA CCALoss fwd+bwd/sec (batch {a.n} sharded over {world} GPUs, 2x{a.d}, fp32)",
                 "value": 1.0 / sharded_loss_s, "ms": sharded_loss_s * 1e3}
-        if world == 1 and not a.no_extras and views is not None:
+        if a.full and world == 1 and not a.no_extras and views is not None:
             gates = not a.no_gates
 
             def gated(name, res):
@@ -1508,7 +1542,7 @@ def main():
             out["dcca_loss_fwd_bwd_per_s"] = extra["dcca_loss_metric_shape"]["value"]
             out["dcca_loss_roofline"] = extra["dcca_loss_metric_shape"]["roofline"]
         # last: its BLAS threads keep spinning for a while and would slow the launch chains of the GPU extras
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.n, a.d, a.k, a.cpu_sample_rows, a.cpu_runs)
             if not a.no_extras:
                 out["cpu_baseline"]["c2_rcca"] = cpu_c2_whole()

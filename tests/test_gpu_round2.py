@@ -284,10 +284,10 @@ def test_offset_golden_from_the_reference():
     tools/gen_golden.py from cca_zoo itself on fp32 views with mean = 100 sigma, n = 4000)."""
     import os
 
-    from conftest import GOLDEN, load_golden
+    from conftest import GOLDEN, golden_files, load_golden
     from cca_zoo_amd.linear import CCA, rCCA
 
-    if not os.path.exists(os.path.join(GOLDEN, "offset_two_view_f32.npz")):
+    if not golden_files(os.path.join(GOLDEN, "offset_two_view_f32.npz")):
         pytest.skip("golden not generated")
     g = load_golden("offset_two_view_f32")
     train = [g["train0"], g["train1"]]

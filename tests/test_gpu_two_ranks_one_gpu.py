@@ -121,7 +121,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_json_line():
     ONE JSON line) with two ranks on the one GPU; a reduced n keeps it to seconds."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "gloo-staged", "--steps", "2", "--warmup", "1",
-           "--no-extras", "--no-cpu-baseline", "--rows", "131072", "--dim", "1024", "--k", "16"]     # (--dim: torch.distributed.run would take "--d" for one of its own options)
+           "--full", "--no-extras", "--no-cpu-baseline", "--rows", "131072", "--dim", "1024", "--k", "16"]     # (--dim: torch.distributed.run would take "--d" for one of its own options)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -129,3 +129,40 @@ def test_bench_two_ranks_on_one_gpu_prints_one_json_line():
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["transport"] == "gloo-staged" and rec["ranks_on_one_gpu"] == 2
     assert rec["parity_gate"]["ok"] and rec["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_fit_on_one_and_two_ranks():
+    """A plain ``bench.py`` run (no ``--full``) times the steps and prints the result line without gates or extras;
+    ``--dump-outputs`` writes what the last timed fit returned.  Two ranks on the one GPU dump the same solution as one."""
+    import numpy as np
+
+    from conftest import col_rel_err
+
+    small = ["--steps", "3", "--warmup", "1", "--rows", "131072", "--dim", "1024", "--k", "16"]
+    recs, dumps = [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        for world in (1, 2):
+            out = os.path.join(tmp, f"w{world}")
+            env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + small + ["--dump-outputs", out]
+            if world > 1:
+                cmd += ["--transport", "gloo-staged"]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+            assert p.returncode == 0, p.stderr[-4000:]
+            lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+            assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-2000:]
+            recs.append(json.loads(lines[0]))
+            dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+    for rec in recs:
+        assert rec["steps"] == 3 and len(rec["step_ms"]) == 3 and rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(1e3 / rec["ms_per_step"]) and rec["unit"] == "fit/s" and rec["dtype"] == "f32"
+        assert rec["parity_gate"] is None and "extra" not in rec and "cpu_baseline" not in rec
+    one, two = dumps
+    assert sorted(one) == ["means_0", "means_1", "singular_values", "weights_0", "weights_1"] and sorted(two) == sorted(one)
+    for i in range(2):
+        assert one[f"weights_{i}"].shape == (1024, 16) and one[f"weights_{i}"].dtype == np.float32
+        assert col_rel_err(two[f"weights_{i}"], one[f"weights_{i}"].astype(np.float64)) < 1e-3
+        np.testing.assert_allclose(two[f"means_{i}"], one[f"means_{i}"], rtol=1e-5, atol=1e-6)
+    sv = one["singular_values"]
+    assert np.all(np.diff(sv) <= 1e-6) and sv[0] <= 1.0 + 1e-6 and sv[-1] > 0
+    np.testing.assert_allclose(two["singular_values"], sv, rtol=1e-5)

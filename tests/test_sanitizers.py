@@ -21,7 +21,9 @@ def test_solver_drivers_under_asan_and_ubsan():
     # the real one at start-up (the drivers report errors by C++ exceptions caught at the ABI)
     libstd = subprocess.run(["gcc", "-print-file-name=libstdc++.so.6"], capture_output=True, text=True).stdout.strip()
     env = dict(os.environ)
-    env.update({"CCZ_HOSTSIM_SANITIZE": "1", "LD_PRELOAD": f"{libasan} {libstd}",
+    # (libasan first; whatever the environment already preloads stays preloaded behind it)
+    preload = " ".join([libasan, libstd] + os.environ.get("LD_PRELOAD", "").split())
+    env.update({"CCZ_HOSTSIM_SANITIZE": "1", "LD_PRELOAD": preload,
                 "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0:verify_asan_link_order=0",
                 "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1", "OMP_NUM_THREADS": "2", "OPENBLAS_NUM_THREADS": "2"})
     # the solver-logic suite drives every driver of solve.cpp (whitening, eps-shift, Chebyshev iteration, fallbacks, error

@@ -6,7 +6,7 @@ cd $R
 SECONDS=0; python -m pytest tests -q -rs --durations=12 -m gpu > $O/final_pytest.log 2>&1; echo "pytest rc=$? wall ${SECONDS}s" > $O/summary.txt
 grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" $O/final_pytest.log | tail -30 >> $O/summary.txt
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/final_smoke.log 2>&1; tail -2 $O/final_smoke.log >> $O/summary.txt
-SECONDS=0; python bench.py > $O/final_bench.json 2> $O/final_bench.err; echo "bench.py rc=$? wall: $SECONDS s" >> $O/summary.txt; grep -i "PARITY" $O/final_bench.err >> $O/summary.txt
+SECONDS=0; python bench.py --full > $O/final_bench.json 2> $O/final_bench.err; echo "bench.py rc=$? wall: $SECONDS s" >> $O/summary.txt; grep -i "PARITY" $O/final_bench.err >> $O/summary.txt
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o bench -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> $O/bench_profiled.err
 f=$(find /tmp/p_bench -name "*results.db" | head -1); python $R/tools/rocpd_stats.py $f k_gram_f32_fifo k_colsum > $O/bench_kernel_stats.md; rm -rf /tmp/p_bench

@@ -46,6 +46,8 @@ from cca_zoo.linear import CCA, GCCA, MCCA, PLS, rCCA  # noqa: E402
 from cca_zoo._utils._linalg import gevp, svd_whiten  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+sys.path.insert(0, os.path.dirname(OUT))
+from conftest import save_npz_parts  # noqa: E402  (a fixture over 1 MiB is stored in parts)
 os.makedirs(OUT, exist_ok=True)
 
 
@@ -72,7 +74,7 @@ def linear_case(name, train, fresh, specs):
         store[f"fresh{i}"] = v
     for tag, ctor in specs.items():
         fitted(ctor(), train, fresh, tag, store)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    save_npz_parts(os.path.join(OUT, name + ".npz"), store)
     print(name, len(store), "arrays")
 
 
@@ -216,7 +218,7 @@ spd = a.T @ a / 39
 store["inv_sqrtm/A"] = spd.numpy()
 store["inv_sqrtm/out_eps1e-5"] = _inv_sqrtm(spd, 1e-5).numpy()
 store["inv_sqrtm/out_eps0.5"] = _inv_sqrtm(spd, 0.5).numpy()      # clamp active
-np.savez_compressed(os.path.join(OUT, "losses.npz"), **store)
+save_npz_parts(os.path.join(OUT, "losses.npz"), store)
 print("losses", len(store), "arrays")
 
 # ------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ cd $R
 SECONDS=0; python -m pytest tests -q -rs --durations=8 -m gpu > $O/suite.log 2>&1; echo "pytest rc=$? wall ${SECONDS}s" > $O/summary.txt
 grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" $O/suite.log | tail -16 >> $O/summary.txt
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log >> $O/summary.txt
-SECONDS=0; python bench.py > $O/bench.json 2> $O/bench.err; echo "bench.py rc=$? wall: $SECONDS s" >> $O/summary.txt; grep -i "PARITY" $O/bench.err | tail -3 >> $O/summary.txt
+SECONDS=0; python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench.py rc=$? wall: $SECONDS s" >> $O/summary.txt; grep -i "PARITY" $O/bench.err | tail -3 >> $O/summary.txt
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o b -- python $R/bench.py --steps 3 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_profiled.json 2> $O/bench_profiled.err
 f=$(find /tmp/p_bench -name "*results.db" | head -1); python $R/tools/rocpd_stats.py $f > $O/bench_kernel_stats.md 2>&1; rm -rf /tmp/p_bench
