@@ -118,6 +118,12 @@ SIGNATURES = {
     "ccz_gcca_loss_moments": (_int, [_vp, _vp, _i64, _pi64, _int, _dbl, _int, C.POINTER(_dbl), _vp, _vp]),
     "ccz_factor_loadings": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "ccz_transform": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
+    "ccz_pairwise_kernel": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _int, _dbl, _dbl, _dbl,
+                                   _vp, _i64]),
+    "ccz_kernel_project": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _int, _dbl, _dbl, _dbl,
+                                  _vp, _i64, _i64, _vp, _i64]),
+    "ccz_kcca_solve": (_int, [_vp, C.POINTER(_vp), _int, _i64, _pdbl, _dbl, _int, _vp, _pdbl, _pint]),
+    "ccz_kgcca_solve": (_int, [_vp, C.POINTER(_vp), _int, _i64, _pdbl, _pdbl, _dbl, _int, _vp, _pdbl, _pint]),
 }
 
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "hip_common.h"
+#include "abi_guard.h"
 
 using namespace ccz;
 
@@ -29,22 +30,6 @@ void randn_fill_impl(ccz_ctx* c, int dtype, void* out, int64_t rows, int64_t col
                      int64_t row0, int64_t row_stride, double scale, bool accumulate);
 }  // namespace ccz
 
-#define CCZ_GUARD(h, ...)                   \
-  if (!(h)) return CCZ_EINVAL;              \
-  try {                                     \
-    ::ccz::DeviceScope ccz_scope_(h);                   \
-    __VA_ARGS__;                            \
-    return CCZ_OK;                          \
-  } catch (const ccz::Error& e) {           \
-    (h)->err = e.msg;                       \
-    return e.code;                          \
-  } catch (const std::bad_alloc&) {         \
-    (h)->err = "host allocation failed";    \
-    return CCZ_ENOMEM;                      \
-  } catch (...) {                           \
-    (h)->err = "unknown internal error";    \
-    return CCZ_EHIP;                        \
-  }
 
 namespace ccz {
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "ops.h"
+#include "abi_guard.h"
 
 namespace ccz {
 
@@ -1073,22 +1074,6 @@ static void factor_loadings_impl(ccz_ctx* c, const double* mom, int64_t n, int64
 // ===========================================================================
 // C ABI (solver part)
 // ===========================================================================
-#define CCZ_GUARD(h, ...)                                              \
-  if (!(h)) return CCZ_EINVAL;                                         \
-  try {                                                                \
-    ::ccz::DeviceScope ccz_scope_(h);                                              \
-    __VA_ARGS__;                                                       \
-    return CCZ_OK;                                                     \
-  } catch (const ccz::Error& e) {                                      \
-    (h)->err = e.msg;                                                  \
-    return e.code;                                                     \
-  } catch (const std::bad_alloc&) {                                    \
-    (h)->err = "host allocation failed";                               \
-    return CCZ_ENOMEM;                                                 \
-  } catch (...) {                                                      \
-    (h)->err = "unknown internal error";                               \
-    return CCZ_EHIP;                                                   \
-  }
 
 namespace {
 // The off-diagonal half of a sharded exchange may still be in flight when a solve starts (ccz_solve_defer).  Whatever

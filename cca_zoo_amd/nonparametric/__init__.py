@@ -1,0 +1,6 @@
+"""Nonparametric (kernel) CCA on the MI355X solver core: kernel matrices, solve and projection in libccz."""
+
+from cca_zoo_amd.nonparametric._kcca import KCCA
+from cca_zoo_amd.nonparametric._kgcca import KGCCA
+
+__all__ = ["KCCA", "KGCCA"]

@@ -370,6 +370,55 @@ CCZ_API int ccz_randn_fill(ccz_handle h, int dtype, void* out_dev, int64_t rows,
 CCZ_API int ccz_factor_loadings(ccz_handle h, const double* moments_dev, int64_t n_rows, int64_t d,
                                 const double* W_dev, int64_t k, double* out_dev);
 
+/* ---- nonparametric models: kernel matrices, KCCA / KGCCA (csrc/kernel_matrix.hip, csrc/kcca.cpp) ----------------
+ * Kernel kinds: scikit-learn's pairwise_kernels(..., filter_params=True).  gamma is always explicit here (the
+ * estimators resolve None to 1 / n_features); degree is a real exponent; parameters a kind does not take are ignored. */
+#define CCZ_KERNEL_LINEAR 0   /* <a, b>                                                     */
+#define CCZ_KERNEL_POLY 1     /* (gamma <a, b> + coef0)^degree                              */
+#define CCZ_KERNEL_RBF 2      /* exp(-gamma max(||a||^2 + ||b||^2 - 2 <a, b>, 0))           */
+#define CCZ_KERNEL_SIGMOID 3  /* tanh(gamma <a, b> + coef0)                                 */
+#define CCZ_KERNEL_COSINE 4   /* <a, b> / (||a|| ||b||), 0 for a zero row                   */
+
+/* K (na x nb, device float64, ld ldk) = f(a_i - meanA, b_j - meanB) over the rows of A (na x d, ld lda) and B (nb x d,
+ * ld ldb), both CCZ_F32 or both CCZ_F64 (fp32 is widened exactly; all products on the fp64 matrix pipe).  meanA /
+ * meanB (d, device float64) are optional and independent: each is subtracted on load when non-NULL.  A_dev == B_dev
+ * with the same shape, ld and mean is the symmetric case: only tiles on and above the diagonal are computed and then
+ * mirrored, and the rbf distance on the diagonal is exactly 0 (K_ii = 1).  Enqueue-only on the handle's stream.
+ * cca_zoo/nonparametric/_kcca.py:195-196 (pairwise_kernels in _compute_kernels), _kgcca.py:120-127 */
+CCZ_API int ccz_pairwise_kernel(ccz_handle h, int dtype, const void* A_dev, int64_t na, int64_t lda, const double* meanA_dev,
+                                const void* B_dev, int64_t nb, int64_t ldb, const double* meanB_dev, int64_t d, int kind,
+                                double gamma, double degree, double coef0, double* K_dev, int64_t ldk);
+
+/* out (nb x k, device float64, ld ldo) = K(A, B)' W with K as in ccz_pairwise_kernel and W (na x k, device float64,
+ * ld ldw) -- K is never written: each 64 x 64 tile lives in registers between the two products.  Any k (64 columns
+ * per pass).  Enqueue-only on the handle's stream.
+ * cca_zoo/nonparametric/_kcca.py:119-148 (transform: pairwise_kernels(train, test).T @ weights), _kgcca.py:136-165 */
+CCZ_API int ccz_kernel_project(ccz_handle h, int dtype, const void* A_dev, int64_t na, int64_t lda, const double* meanA_dev,
+                               const void* B_dev, int64_t nb, int64_t ldb, const double* meanB_dev, int64_t d, int kind,
+                               double gamma, double degree, double coef0, const double* W_dev, int64_t k, int64_t ldw,
+                               double* out_dev, int64_t ldo);
+
+/* KCCA on n_views >= 2 training kernel matrices K_dev[i] (n x n, ld n, device float64, symmetric; DESTROYED: each
+ * is overwritten by its eigenvectors).  Solves the reference's  A v = lambda B v,  v'Bv = 1  with
+ *   A = (cov(hstack K) - blockdiag cov(K_i)) / M,   B = (blockdiag(c_i K_i + (1 - c_i) K_i^2) + shift I) / M,
+ *   shift = max(0, eps - lambda_min(blockdiag)),
+ * through one eigendecomposition K_i = U diag(l) U' per view (B_i is a polynomial in K_i): two views take the top-k
+ * SVD of  D_1^-1/2 U_1' Kc_1' Kc_2 U_2 D_2^-1/2 / (n - 1)  (Kc: column-centred), more views a dense EVD of the
+ * whitened (M n)-sized A.  weights_dev: n_views consecutive n x k_out blocks (row-major, device float64); vals_host:
+ * k_out eigenvalues (descending).  k <= n.  Ordered with the host on return.
+ * cca_zoo/nonparametric/_kcca.py:82-117 (fit), :214 (_build_A / _build_B), cca_zoo/_utils/_linalg.py:gevp */
+CCZ_API int ccz_kcca_solve(ccz_handle h, double* const* K_dev, int n_views, int64_t n, const double* c, double eps, int k,
+                           double* weights_dev, double* vals_host, int* k_out);
+
+/* KGCCA on n_views >= 1 kernel matrices (as in ccz_kcca_solve, destroyed):
+ *   Q = sum_i mu_i K_i B_i^-1 K_i,  B_i = c_i K_i + (1 - c_i) K_i^2 + shift_i I,  shift_i = max(0, eps - lambda_min(B_i)),
+ * T = top-k eigenvectors of Q (view_weights mu_i >= 0: the top-k left singular vectors of [sqrt(mu_i) U_i diag(l / sqrt(b))]),
+ * weights_i = pinv(K_i) T with NumPy's cutoff (|l| <= 1e-15 max|l| counts as zero).  Outputs as ccz_kcca_solve; vals_host:
+ * the top-k eigenvalues of Q.
+ * cca_zoo/nonparametric/_kgcca.py:80-134 (fit) */
+CCZ_API int ccz_kgcca_solve(ccz_handle h, double* const* K_dev, int n_views, int64_t n, const double* c,
+                            const double* view_weights, double eps, int k, double* weights_dev, double* vals_host, int* k_out);
+
 #ifdef __cplusplus
 }
 #endif
