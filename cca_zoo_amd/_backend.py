@@ -124,6 +124,13 @@ SIGNATURES = {
                                   _vp, _i64, _i64, _vp, _i64]),
     "ccz_kcca_solve": (_int, [_vp, C.POINTER(_vp), _int, _i64, _pdbl, _dbl, _int, _vp, _pdbl, _pint]),
     "ccz_kgcca_solve": (_int, [_vp, C.POINTER(_vp), _int, _i64, _pdbl, _pdbl, _dbl, _int, _vp, _pdbl, _pint]),
+    "ccz_ey_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _dbl, C.POINTER(_vp)]),
+    "ccz_ey_destroy": (_int, [_vp, _vp]),
+    "ccz_ey_set_weights": (_int, [_vp, _vp, _pdbl]),
+    "ccz_ey_project": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pdbl]),
+    "ccz_ey_steps": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _i64, _pi64, _pint]),
+    "ccz_ey_status": (_int, [_vp, _vp, _pi64, _pint, _pdbl]),
+    "ccz_ey_get_weights": (_int, [_vp, _vp, _pdbl]),
 }
 
 

@@ -419,6 +419,48 @@ CCZ_API int ccz_kcca_solve(ccz_handle h, double* const* K_dev, int n_views, int6
 CCZ_API int ccz_kgcca_solve(ccz_handle h, double* const* K_dev, int n_views, int64_t n, const double* c,
                             const double* view_weights, double eps, int k, double* weights_dev, double* vals_host, int* k_out);
 
+/* ---- gradient models: CCA_EY / PLS_EY / MCCA_EY (csrc/ey.hip) ------------------------------------------------------
+ * Mini-batch momentum SGD on the Eckart-Young objective, four launches per step, no host wait inside a chunk of steps.
+ * A fit state (opaque, out-parameter) holds W (double-buffered), the velocity, the per-step scratch, the stop word and two
+ * pinned index slots.  Views are ccz_view's of DEVICE rows (all CCZ_F32 or all CCZ_F64); means_dev[i] (device, the views'
+ * dtype, or a NULL array / entry: no centring) is subtracted on load in the input precision.  W blocks: view i's p_i x k
+ * row-major weights, views back to back (float64).  fp64 views: fp64 arithmetic throughout.  fp32 views: the two
+ * products per step on the fp32 matrix pipe (centred fp32 rows times W or T rounded to fp32, fp32 within a stage of at
+ * most 1024 features / 32 rows, fp64 across stages); W, velocity and all k x k algebra in fp64.  Measured per-step
+ * relative error against float64 on the same rows (max abs error / max abs value): Z 3.5e-7, one update 3.6e-7.
+ * cca_zoo/linear/gradient/_base.py:101-130, _cca_ey.py:134-225, _pls_ey.py:56-104, _mcca_ey.py:46-61,
+ * cca_zoo/_utils/_ey.py:36-61 (C, V), :85-96 (B), :98-127 (PLS init), :129-185 (CCA init) */
+
+/* Create a fit state: n_views (1..16) views of widths p[i] >= k, k in 1..128, batch_rows rows per step, up to
+ * chunk_steps steps per ccz_ey_steps call; c, learning_rate, momentum and tol as in the reference. */
+CCZ_API int ccz_ey_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t k, int64_t batch_rows,
+                          int64_t chunk_steps, double c, double learning_rate, double momentum, double tol, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op. */
+CCZ_API int ccz_ey_destroy(ccz_handle h, void* state);
+
+/* Upload initial weights (host, float64, W blocks): velocity <- 0, B <- sum_i W_i'W_i / M, steps <- 0, objective <- inf. */
+CCZ_API int ccz_ey_set_weights(ccz_handle h, void* state, const double* W_host);
+
+/* Z (host, float64, n_views consecutive batch_rows x k blocks) = (X_i[idx] - mu_i) W_i with the weights of the last
+ * ccz_ey_set_weights; idx_host: batch_rows row indices in [0, n_rows) (NULL: rows 0 .. batch_rows - 1, then n_rows must
+ * equal batch_rows).  The initial projection z0 of CCA_EY (cca_zoo/_utils/_ey.py:177-184).  Ordered with the host on return. */
+CCZ_API int ccz_ey_project(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_rows,
+                           const int64_t* idx_host, double* Z_host);
+
+/* Enqueue n_steps (<= chunk_steps) steps.  idx_host: n_steps x batch_rows row indices (host; copied into a pinned slot
+ * and uploaded asynchronously), NULL = full batch (identity; n_rows == batch_rows).  Returns without waiting for the
+ * device; the only host wait is for the chunk that used the same slot two calls earlier, whose status is returned in
+ * steps_known / stopped_known (-1 / 0 when there is none yet).  Steps after the stop are no-ops on the device. */
+CCZ_API int ccz_ey_steps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_rows,
+                         const int64_t* idx_host, int64_t n_steps, int64_t* steps_known, int* stopped_known);
+
+/* Steps applied so far, whether the tol test stopped the fit, and the last objective.  Synchronises. */
+CCZ_API int ccz_ey_status(ccz_handle h, void* state, int64_t* steps_done, int* stopped, double* last_objective);
+
+/* Copy the current weights (W blocks, float64) to the host.  Synchronises. */
+CCZ_API int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host);
+
 #ifdef __cplusplus
 }
 #endif
