@@ -73,7 +73,7 @@ int ccz_create(ccz_handle* out, int device) {
   // null-stream work (PyTorch's default stream) and, unlike the null stream, can be captured into graphs
   ok = ok && hipStreamCreate(&im->own_stream) == hipSuccess;
   if (ok) c->stream = im->own_stream;
-  if (const char* e = getenv("CCZ_GRAPHS")) im->graphs_on = atoi(e);
+  im->graphs_on = env::live(env::GRAPHS);
   ok = ok && hipMalloc(reinterpret_cast<void**>(&im->d_flag), 64 * sizeof(int)) == hipSuccess;
   ok = ok && hipMalloc(reinterpret_cast<void**>(&im->d_small), im->small_cap * sizeof(double)) == hipSuccess;
   if (!ok) { (void)hipGetLastError(); delete im; delete c; return CCZ_EHIP; }

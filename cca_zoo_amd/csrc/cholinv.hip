@@ -1306,12 +1306,12 @@ static void cholinv_attr_once() {
 }
 
 // CCZ_CHOLINV_MFMA: 0 shift-register (two-wave) form of the 64 x 64 factorization, 1 MFMA form with 4-column panels
-// (rounds 2-4: 30.4k shader cycles per block inside the chain kernel), 2 (default) MFMA form with 16-column panels (24.3k).
+// (rounds 2-4: 30.4k shader cycles per block inside the chain kernel), 2 MFMA form with 16-column panels (24.3k).
 // Either way ONE wave issues ~3000 instructions per block: a dependent fp64 operation costs 4-8 cycles, not the 32 that
 // rounds 2-4 designed around (tools/probes/lat_probe.hip: that probe timed a loop branch) -- the block is issue-bound.
 static int cholinv_form() {
-  static const int form = [] { const char* e = getenv("CCZ_CHOLINV_MFMA"); const int v = e ? atoi(e) : 2; return v < 0 || v > 2 ? 2 : v; }();
-  return form;
+  const int v = env::once(env::CHOLINV_MFMA);
+  return v < 0 || v > 2 ? 2 : v;
 }
 
 // The sync block of the chain kernel belongs to the STREAM the launch goes into: launches on one stream are ordered, so
@@ -1334,12 +1334,10 @@ static ChainSync* chain_sync_for(ccz_ctx* c) {
 }
 
 // CCZ_CHOLINV_CHAIN=0: the launch-per-link form (rounds 2-4).  CCZ_CHAIN_WGS: workgroups of the persistent launch
-// (default 128; Impl::chain_cap overrides it for callers that share the chip with throughput work on another stream).
+// (Impl::chain_cap overrides it for callers that share the chip with throughput work on another stream).
 static bool chain_launch(ccz_ctx* c, const CholInvBatch& bt, int nbmax, int* info_dev) {
-  static const int on = [] { const char* e = getenv("CCZ_CHOLINV_CHAIN"); return e ? atoi(e) : 1; }();
-  static const int wgs_env = [] { const char* e = getenv("CCZ_CHAIN_WGS"); return e ? atoi(e) : 128; }();
   const int form = cholinv_form();
-  if (!on || form == 0 || bt.inv_only || nbmax > CH_MAXNB) return false;
+  if (!env::once(env::CHOLINV_CHAIN) || form == 0 || bt.inv_only || nbmax > CH_MAXNB) return false;
   ChainPlan plan{};
   plan.nbmax = nbmax;
   int total = 0;
@@ -1353,16 +1351,14 @@ static bool chain_launch(ccz_ctx* c, const CholInvBatch& bt, int nbmax, int* inf
   }
   plan.link_first[nbmax] = total;
   plan.total = total + bt.count;
-  static const int sleep_env = [] { const char* e = getenv("CCZ_CHAIN_SLEEP"); return e ? std::max(1, atoi(e)) : 1; }();
-  plan.poll_sleep = sleep_env;
+  plan.poll_sleep = std::max(1, env::once(env::CHAIN_SLEEP));
   ChainSync* sy = chain_sync_for(c);
   if (!sy) return false;
   Impl* im = impl(c);
-  const int cap = im->chain_cap > 0 ? im->chain_cap : std::max(wgs_env, 2);
+  const int cap = im->chain_cap > 0 ? im->chain_cap : std::max(env::once(env::CHAIN_WGS), 2);
   // at least one helper workgroup next to the chain workgroups (they never leave their matrix)
   const int grid = std::min(plan.total, std::max(cap, bt.count + 1));
-  // CCZ_CHAIN_DEBUG=1: shader-clock stamps of matrix 0's chain workgroup, printed per launch (synchronises: measurement only)
-  static const int debug = [] { const char* e = getenv("CCZ_CHAIN_DEBUG"); return e ? atoi(e) : 0; }();
+  const int debug = env::once(env::CHAIN_DEBUG);     // stamps of matrix 0's chain workgroup, printed per launch
   unsigned long long* dbg = nullptr;
   if (debug) {
     if (!im->chain_dbg) CCZ_HIP(hipMalloc(&im->chain_dbg, 8 * (CH_MAXNB + 1) * sizeof(unsigned long long)));

@@ -45,7 +45,7 @@ Rccl& rccl() {
   static std::once_flag once;
   std::call_once(once, [] {
     // CCZ_RCCL_LIB: the one library to use (a deployment that pins its RCCL; the tests force the not-found path with it)
-    if (const char* forced = getenv("CCZ_RCCL_LIB")) {
+    if (const char* forced = env::once(env::RCCL_LIB)) {
       r.lib = dlopen(forced, RTLD_NOW | RTLD_GLOBAL);
     } else {
       const char* names[] = {"librccl.so.1", "librccl.so"};

@@ -505,8 +505,7 @@ struct BjRows {
 };
 constexpr int BJ_AG = 4;  // tiles (K, L .. L + 3) per A-tile workgroup when the grid is large (rows.rg > 1)
 inline int bj_row_group(int np, int chunks_total) {
-  static const int64_t min_tiles = [] { const char* e = getenv("CCZ_BJ_GROUP_MIN_TILES"); return e ? atoll(e) : 2048LL; }();
-  return int64_t(np) * chunks_total >= min_tiles ? 4 : 1;
+  return int64_t(np) * chunks_total >= env::once(env::BJ_GROUP_MIN_TILES) ? 4 : 1;
 }
 
 // part: 0 = both kinds of tile in one launch, 1 = the A tiles only, 2 = the row tiles only.  fused: A is three rotating
@@ -844,13 +843,10 @@ __global__ void k_bj_diag(const double* __restrict__ Aw, int64_t dp, int64_t d, 
   if (i < d) w[i] = Aw[i * dp + i];
 }
 
-bool bj_fused() {   // CCZ_BJ_FUSED=1: pair kernels and tile updates on two streams (A/B; measured: no gain, see syev_block)
-  static const bool v = [] { const char* e = getenv("CCZ_BJ_FUSED"); return e && atoi(e) == 1; }();
-  return v;
-}
+bool bj_fused() { return env::once(env::BJ_FUSED) == 1; }   // (measured: no gain, see syev_block)
 
 int bj_max_gram_split() {
-  static const int v = [] { const char* e = getenv("CCZ_BJ_GRAM_SPLIT"); return e ? std::max(1, atoi(e)) : 0; }();
+  static const int v = env::is_set(env::BJ_GRAM_SPLIT) ? std::max(1, env::once(env::BJ_GRAM_SPLIT)) : 0;
   return v;
 }
 
@@ -888,8 +884,7 @@ int syev_block_min(ccz_ctx*) { return 2; }
 // solve) and the remaining sweeps run on B -- their rounding is all that is left in the result.
 int syev_block(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_dev, double* Vrows, int64_t ldv, int max_sweeps) {
   if (d < 1) fail(CCZ_EINVAL, "syev_block: d >= 1 required");
-  static const int refresh_min = [] { const char* e = getenv("CCZ_EVD_REFRESH_MIN"); return e ? atoi(e) : 1536; }();
-  const bool want_refresh = d >= refresh_min;
+  const bool want_refresh = d >= env::once(env::EVD_REFRESH_MIN);
   const int64_t dp = (d + BJP - 1) / BJP * BJP, plane = dp * dp;
   const int nb = int(dp / BJB), np = nb / 2;
   // Fused schedule (default from 4 blocks on): the pair kernel of round g + 1 re-derives its cross block from the OLD tile
@@ -934,7 +929,7 @@ int syev_block(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_de
   int sweeps = -1;
   bool refreshed = false;
   long long g_total = 0, direct_g = 0;                    // (fused) global round counter; the round that reads its cross blocks directly
-  static const bool dbg_on = getenv("CCZ_BJ_DEBUG") != nullptr;
+  const bool dbg_on = env::once(env::BJ_DEBUG);
   DBuf dbgb(c, dbg_on ? 192 : 0);
   for (int sweep = 1; sweep <= max_sweeps; ++sweep) {
     CCZ_HIP(hipMemsetAsync(&sb.dev->rotations, 0, sizeof(int), st));

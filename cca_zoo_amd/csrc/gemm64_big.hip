@@ -486,19 +486,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f64_pipe(int64_t M, int64_t N, 
 // a k-step of X'X is two full row segments); gathering 16 - 64-byte pieces from 16 - 32 different rows per instruction runs
 // the texture path at a fraction of that rate, and a cooperative, coalesced stage + LDS transpose wins.  (Measured on the
 // GPU and dropped before it was ever committed; DESIGN.md section 4 keeps the numbers.)
-static int64_t env_ll(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
-
 // Shapes the 128x128-tile kernel takes: products with at least 128 rows and columns and enough tiles.
 // Products with few tiles and deep K (subspace-iteration applies S X with 128 <= N < 256) run split-K.
 // Narrower outputs (N < 128) stay on the 64x64-tile kernel: measured 23 vs 15 TFLOP/s at N = 80.
 bool gemm_f64_big_eligible(bool tA, bool tB, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                            const double* B, int64_t ldb, const double* C, int64_t ldc) {
   (void)tA; (void)tB;
-  static const int64_t min_tiles = env_ll("CCZ_GEMM_BIG_MIN_TILES", 32);
-  static const int64_t min_k = env_ll("CCZ_GEMM_BIG_MIN_K", 64);
+  const int64_t min_tiles = env::once(env::GEMM_BIG_MIN_TILES), min_k = env::once(env::GEMM_BIG_MIN_K);
   if (K % DK != 0 || K < min_k) return false;
   if ((lda | ldb | ldc) & 1) return false;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 15) return false;
@@ -524,14 +518,12 @@ void gemm_f64_big(ccz_ctx* c, bool tA, bool tB, int64_t M, int64_t N, int64_t K,
   int splits = 1;
   // (split-K with an fp64-atomic epilogue only where the tiles leave at least half of the chip idle: at one workgroup per CU the
   // pipelined kernel runs at 0.89 of the peak, and a 256-tile product measured 541 us split four ways against 272 us for rocBLAS)
-  static const int64_t pipe_sel = env_ll("CCZ_GEMM64_PIPE", 1);
-  if (!lower_only && tm * tn * (pipe_sel ? 2 : 1) < 2 * int64_t(ncu) && K >= 2048) {
+  const bool pipe_on = env::once(env::GEMM64_PIPE) != 0;
+  if (!lower_only && tm * tn * (pipe_on ? 2 : 1) < 2 * int64_t(ncu) && K >= 2048) {
     splits = int(std::min<int64_t>({int64_t(16), (4 * ncu) / (tm * tn), K / 512}));
     if (splits < 2) splits = 1;
   }
-  static const int64_t half_on = env_ll("CCZ_GEMM_HALF_TILE", 1);
-  static const int64_t pipe_on = env_ll("CCZ_GEMM64_PIPE", 1);      // 0: the round-2 kernels (A/B)
-  const bool use_half = half_on && splits == 1 && !lower_only && tm * tn < int64_t(ncu) && M > HM;
+  const bool use_half = env::once(env::GEMM_HALF_TILE) && splits == 1 && !lower_only && tm * tn < int64_t(ncu) && M > HM;
   if (pipe_on) {
     int64_t kps = K;
     if (splits > 1) {

@@ -204,7 +204,7 @@ __global__ void k_scale2d_skinny(int64_t total, int64_t cols, double* __restrict
 
 bool gemm_f64_skinny_eligible(bool tA, bool tB, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                               const double* B, int64_t ldb) {
-  static const char* off = getenv("CCZ_GEMM_SKINNY_OFF");
+  const char* off = env::once(env::GEMM_SKINNY_OFF);
   if (off && off[0] == '1') return false;
   if (tB) return false;
   if (N <= 48 || N > 192 || (N & 1)) return false;

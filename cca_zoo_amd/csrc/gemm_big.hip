@@ -657,10 +657,8 @@ void gemm_f32_big(ccz_ctx* c, int64_t M, int64_t N, int64_t K, double alpha, con
                        N, int64_t(TN), B, ldb, B32);
     if (bias_row)
       hipLaunchKernelGGL(k_f64_to_f32_pad, dim3(1), dim3(256), 0, st, int64_t(1), N, int64_t(TN), bias_row, N, bias32);
-    const char* tall_env = getenv("CCZ_TALL_IMPL");     // 3: whole-line loads, 128 rows per workgroup (default); 2: 256 rows; 1: a row per lane
-    const int tall_impl = tall_env ? atoi(tall_env) : 3;
-    const char* nj_env = getenv("CCZ_TALL_NJ1");         // 0: always two column tiles (A/B switch of the N <= 32 form)
-    const bool nj1 = N <= 32 && !(nj_env && atoi(nj_env) == 0);
+    const int tall_impl = env::live(env::TALL_IMPL);
+    const bool nj1 = N <= 32 && env::live(env::TALL_NJ1) != 0;
     if (tall_impl == 3 && K % BK2 == 0 && (M + 127) / 128 < (int64_t(1) << 31)) {
       const size_t lds_bytes = size_t(BK2) * (128 + 2 + (nj1 ? 32 : TN)) * 4;
       auto kern = nj1 ? &k_gemm_f32_nn_tall2<1, 1> : &k_gemm_f32_nn_tall2<1, 2>;
@@ -688,7 +686,7 @@ void gemm_f32_big(ccz_ctx* c, int64_t M, int64_t N, int64_t K, double alpha, con
     if (bias_row)
       hipLaunchKernelGGL(k_f64_to_f32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, N, bias_row, N, bias32, N);
   }
-  static const int nn_impl = [] { const char* e = getenv("CCZ_GEMM_NN_IMPL"); return e ? atoi(e) : 1; }();   // 1: LDS-DMA FIFO, 0: staged tile
+  const int nn_impl = env::once(env::GEMM_NN_IMPL);
   const int64_t tmb = (M + BT - 1) / BT, tnb = N / BT;
   const bool fifo_ok = nn_impl != 0 && K % 32 == 0 && int64_t(128) * lda * 4 < (int64_t(1) << 31) &&
                        (tmb + 7) / 8 * 8 * tnb < (int64_t(1) << 31);

@@ -166,10 +166,8 @@ size_t split_scratch_budget(ccz_ctx* c);
 
 bool gemm_split_pair_eligible(int64_t M, int64_t N, int64_t K, int64_t K1, int64_t nsplit, const void* A1, int64_t lda1, const void* A2,
                               int64_t lda2, const void* C1, int64_t ldc1, const void* C2, int64_t ldc2) {
-  const char* e_on = getenv("CCZ_LOSS_BWD_SPLIT");            // (read per call: tests lower the pay-off threshold)
-  const char* e_fl = getenv("CCZ_SPLIT_MIN_FLOP");
-  const int on = e_on ? atoi(e_on) : 1;
-  const double min_flop = e_fl ? atof(e_fl) : 1e11;
+  const int on = env::live(env::LOSS_BWD_SPLIT);
+  const double min_flop = env::live(env::SPLIT_MIN_FLOP);
   // Large products (the metric shape) by default; with CCZ_LOSS_BWD_SPLIT=2 also DCCA batches from 4096 rows on (2 M N K >= 1e10, the half-tile form):
   // a gradient element is a random-walk sum over K, its split error (~ 5e-6 of the gradient's scale) does not depend on M --
   // the float32 bar of the path is 1e-3, and the reference's own fp32 autograd gradient agrees with the closed form to 5e-2

@@ -1002,7 +1002,7 @@ TileTable build_tile_table(ccz_ctx* c, const ccz_view* views, int n_views, void*
   // 32 consecutive tiles have uniform cost and shared panels: first the complete 4 x 8 supertiles (no diagonal tiles:
   // 12 panels per 32 tiles), then all diagonal tiles together (they cost ~65% of a full tile -- mixed into other
   // rounds they would stagger the XCD's workgroups for good), then the off-diagonal rest of the ragged supertiles.
-  static const int map_mode = [] { const char* e = getenv("CCZ_GRAM_MAP"); return e ? atoi(e) : 1; }();
+  const int map_mode = env::once(env::GRAM_MAP);
   if (map_mode == 1) {
     std::vector<GramTile> full, dg, rest;
     size_t pos = 0;
@@ -1109,9 +1109,9 @@ template <typename T>
 RowPlan plan_rows(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, int ntiles, bool fast) {
   Impl* im = impl(c);
   constexpr bool is32 = sizeof(T) == 4;
-  static const int map_mode = [] { const char* e = getenv("CCZ_GRAM_MAP"); return e ? atoi(e) : 1; }();
+  const int map_mode = env::once(env::GRAM_MAP);
   const int ncu = std::max(1, im->props.multiProcessorCount);
-  static const int64_t rows_env = [] { const char* e = getenv("CCZ_GRAM_ROWS"); return e ? atoll(e) : 0LL; }();
+  const int64_t rows_env = env::once(env::GRAM_ROWS);
   int64_t max_rows = rows_env > 0 ? rows_env : 16384;
   if (fast) {   // keep (rows + FIFO run-ahead) * ld * sizeof(T) inside the 32-bit buffer descriptor
     int64_t cap = max_rows;
@@ -1185,26 +1185,21 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   // (Round 3 tried to hide this 5.4 ms HBM-bound pass under the MFMA-bound K1 on a second stream, with the pilot decided
   // from a strided sample: K1 then ran 7 ms LONGER -- the column-sum workgroups share the CUs' issue slots with K1's one
   // wave per SIMD -- so the pass stays in front.)
-  static const int pilot_env = [] { const char* e = getenv("CCZ_GRAM_PILOT"); return e ? atoi(e) : -1; }();   // -1: caller's mode
+  const int pilot_env = env::once(env::GRAM_PILOT);
   if (pilot_env == 0 || pilot_env == 1) pilot_mode = pilot_env == 1 ? 2 : 0;
   if (!is32) pilot_mode = 0;                                  // fp64 views accumulate in fp64: nothing to protect
   // arithmetic route of fp32 views (ccz_k1_route): the split-bf16 route always shifts by the pilot -- the subtraction rides
   // in its split pass for free and needs no read-back
   bool split = false;
   if (is32) {
-    static const int route_env = [] {
-      const char* e = getenv("CCZ_K1_ROUTE");
-      if (!e) return 0;
-      if (!strcmp(e, "fp32")) return int(CCZ_K1_FP32);
-      if (!strcmp(e, "bf16x2")) return int(CCZ_K1_BF16X2);
-      return 0;
-    }();
+    const char* e = env::once(env::K1_ROUTE);
+    const int route_env = !e ? 0 : !strcmp(e, "fp32") ? int(CCZ_K1_FP32) : !strcmp(e, "bf16x2") ? int(CCZ_K1_BF16X2) : 0;
     const int route = c->k1_route != CCZ_K1_AUTO ? c->k1_route : route_env;
     split = (route == CCZ_K1_BF16X2 || (route == CCZ_K1_AUTO && gram_split_worthwhile(n, D))) && n_views <= 16;
     if (split) pilot_mode = 2;
   }
   c->last_route = !is32 ? CCZ_K1_FP64 : (split ? CCZ_K1_BF16X2 : CCZ_K1_FP32);
-  static const double pilot_thr = [] { const char* e = getenv("CCZ_GRAM_PILOT_RATIO"); return e ? atof(e) : 2.0; }();
+  const double pilot_thr = env::once(env::GRAM_PILOT_RATIO);
   double* s_launch = s;            // column sums of THIS launch's rows (separate from the running sums in pilot modes)
   double* sq = nullptr;
   if (pilot_mode != 0) {
@@ -1273,19 +1268,18 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   }
 
   if (time_it) CCZ_HIP(hipEventRecord(im->ev[0], st));
-  static const int impl_sel = [] { const char* e = getenv("CCZ_GRAM_IMPL"); return e ? atoi(e) : 1; }();   // 1: wave-private FIFO (default), 0: register-staged shared tile
+  const int impl_sel = env::once(env::GRAM_IMPL);
   // pilot-shifted data on a chip-filling grid: the FIFO kernel with the subtraction at the fragment read, on the rows
   // that form whole ring periods; the (< 32) rows left over go through the staged kernel, same pilot
-  static const int fifo_pilot_env = [] { const char* e = getenv("CCZ_GRAM_FIFO_PILOT"); return e ? atoi(e) : 1; }();
+  const int fifo_pilot_env = env::once(env::GRAM_FIFO_PILOT);
   const int64_t n_main = n / (FB * FR) * (FB * FR);
   const bool fifo_pilot = is32 && fast && impl_sel != 0 && use_pilot && fifo_pilot_env != 0 && sliced && n_main >= rows_per_wg;
   // staged fp32 kernel on a small grid: per-(chunk, tile) partial sums + one reduce instead of contended atomics
   float* partial = nullptr;
   const bool staged32 = is32 && !(fast && impl_sel != 0 && !use_pilot) && !fifo_pilot;
   if (staged32 && ksplit >= 2 && !sliced && !split) {
-    static const int64_t partial_cap = [] { const char* e = getenv("CCZ_GRAM_PARTIAL_MB"); return (e ? atoll(e) : 192LL) << 20; }();
     const int64_t bytes = ksplit * int64_t(ntiles) * T32 * T32 * 4;
-    if (bytes <= partial_cap) partial = static_cast<float*>(dev_alloc(c, size_t(bytes)));
+    if (bytes <= env::gram_partial_cap()) partial = static_cast<float*>(dev_alloc(c, size_t(bytes)));
   }
   if (split) {
     gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it);
@@ -1313,8 +1307,7 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
       hipLaunchKernelGGL(k_gram_f32<false>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D, pilot, partial, int64_t(0));
     }
   } else {
-    static const int impl64 = [] { const char* e = getenv("CCZ_GRAM64_IMPL"); return e ? atoi(e) : 1; }();   // 1: FIFO, 0: staged
-    if (fast && impl64 != 0) {
+    if (fast && env::once(env::GRAM64_IMPL) != 0) {
       const size_t fifo_bytes = size_t(4) * FR * FSLOT;
       CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64_fifo), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
       hipLaunchKernelGGL(k_gram_f64_fifo, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D);
@@ -1457,12 +1450,12 @@ bool gram_partials_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n
   if (gram_partials_split_f32(c, views, n_views, n, out)) return true;      // DCCA batches from 4096 rows on: the split route
   const TileTable tt = build_tile_table<float>(c, views, n_views, nullptr);
   const RowPlan rp = plan_rows<float>(c, views, n_views, n, tt.ntiles, tt.fast);
-  static const int64_t partial_cap = [] { const char* e = getenv("CCZ_GRAM_PARTIAL_MB"); return (e ? atoll(e) : 192LL) << 20; }();
+  const int64_t partial_cap = env::gram_partial_cap();
   int64_t bytes = rp.ksplit * int64_t(tt.ntiles) * T32 * T32 * 4;
   if (rp.sliced || bytes > partial_cap) return false;
   const int ncu = std::max(1, im->props.multiProcessorCount);
   // ---- the FIFO kernel with a per-tile row split (k_gram_f32_fifo_small), when every chunk can be whole ring periods ----
-  static const int fifo_env = [] { const char* e = getenv("CCZ_LOSS_K1_FIFO"); return e ? atoi(e) : 1; }();
+  const int fifo_env = env::once(env::LOSS_K1_FIFO);
   bool fifo_plan_ok = false;
   int fifo_wgs = 0;
   int* fifo_plan_dev = nullptr;
@@ -1587,12 +1580,9 @@ void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int
   // refuses pinned memory, take the plain copy-then-compute loop.
   int64_t row_bytes = 0;
   for (int v = 0; v < n_views; ++v) row_bytes += views[v].cols * int64_t(es);
-  const int64_t chunk_mb = [] { const char* e = getenv("CCZ_H2D_CHUNK_MB"); return e ? std::max<int64_t>(1, atoll(e)) : 1024LL; }();
-  const int n_threads = [] {
-    const char* e = getenv("CCZ_H2D_THREADS");
-    if (e) return std::max(1, atoi(e));
-    return int(std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
-  }();
+  const int64_t chunk_mb = std::max<int64_t>(1, env::live(env::H2D_CHUNK_MB));
+  const int n_threads = env::is_set(env::H2D_THREADS) ? std::max(1, env::live(env::H2D_THREADS))
+                                                      : int(std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
   int64_t chunk = std::max<int64_t>(64, (chunk_mb << 20) / row_bytes / 64 * 64);
   chunk = std::min(chunk, n_rows);
   const bool piped = n_rows * row_bytes >= (int64_t(64) << 20) && n_rows > chunk / 2 && ensure_pipe(c, size_t(chunk) * row_bytes);
@@ -1612,8 +1602,7 @@ void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int
       else src_pinned = a2.type == hipMemoryTypeHost;
     }
   }
-  static const bool pinned_direct = [] { const char* e = getenv("CCZ_H2D_PINNED_DIRECT"); return !e || atoi(e) != 0; }();
-  src_pinned = src_pinned && pinned_direct;
+  src_pinned = src_pinned && env::once(env::H2D_PINNED_DIRECT) != 0;
   std::vector<void*> stage(size_t(nslots) * n_views, nullptr);
   std::vector<ccz_view> dv(size_t(nslots) * n_views);
   void* tile_tab[2] = {nullptr, nullptr};

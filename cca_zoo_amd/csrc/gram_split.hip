@@ -319,8 +319,7 @@ std::vector<std::pair<int, int>> split_tile_order(int np) {
 }  // namespace
 
 size_t split_scratch_budget(ccz_ctx* c) {
-  const char* e = getenv("CCZ_SPLIT_SCRATCH_GB");         // read per call: tests shrink it to force several row super-chunks
-  const double env_gb = e ? atof(e) : 48.0;
+  const double env_gb = env::live(env::SPLIT_SCRATCH_GB);
   const double cap = 0.4 * double(impl(c)->props.totalGlobalMem);
   return size_t(std::max(8.0 * 1048576.0, std::min(env_gb * 1073741824.0, cap)));
 }
@@ -416,13 +415,11 @@ static void launch_split_pass(ccz_ctx* c, const SplitTables& tb, const SplitView
   if (!st) st = stream(c);
   const int rb = split_rows_per_block(ksteps * SP_K, tb.np, std::max(1, impl(c)->props.multiProcessorCount));
   const unsigned nrb = (unsigned)((ksteps * SP_K + rb - 1) / rb);
-  // panels fastest in the grid (default; CCZ_SPLIT_ORDER=0: row blocks fastest, the first form; read per call).  Measured at the
+  // panels fastest in the grid (CCZ_SPLIT_ORDER=0: row blocks fastest, the first form).  Measured at the
   // metric shape, alternating runs (tools/r6_split_order.sh): 12.1 / 10.7 / 10.6 ms against 12.6 / 12.3 / 11.9 -- never slower.
-  const char* oe = getenv("CCZ_SPLIT_ORDER");
-  const int panel_fast = (!(oe && atoi(oe) == 0) && nrb <= 65535u) ? 1 : 0;
+  const int panel_fast = (env::live(env::SPLIT_ORDER) != 0 && nrb <= 65535u) ? 1 : 0;
   const dim3 grid = panel_fast ? dim3((unsigned)tb.np, nrb) : dim3(nrb, (unsigned)tb.np);
-  const char* xe = getenv("CCZ_SPLIT_XCH");                  // 0: direct 16-byte stores at a stride of 64 bytes (the first form); read per call
-  const bool xch = !(xe && atoi(xe) == 0);
+  const bool xch = env::live(env::SPLIT_XCH) != 0;
   auto kern = aligned ? (xch ? &k_split_bf16x2<true, true> : &k_split_bf16x2<true, false>)
                       : (xch ? &k_split_bf16x2<false, true> : &k_split_bf16x2<false, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, tb.panels, vws, r0, rows, ksteps, pilot, planes, msq, colsum, rb, panel_fast);
@@ -461,8 +458,7 @@ static SplitRowPlan split_row_plan(int64_t ksteps, int ntiles, int64_t max_steps
   rp.steps_per_wg = (ksteps + best_k - 1) / best_k;
   rp.ksplit = (ksteps + rp.steps_per_wg - 1) / rp.steps_per_wg;
   const bool sliced = int64_t(ntiles) * rp.ksplit >= 16 * int64_t(ncu);
-  const char* e_walk = getenv("CCZ_SPLIT_WALK");          // A/B: 1 = every XCD on the SAME row chunk (slices of the tile list) also when ksplit % 8 == 0
-  const bool xchunks = sliced && rp.ksplit % 8 == 0 && !(e_walk && atoi(e_walk) == 1);
+  const bool xchunks = sliced && rp.ksplit % 8 == 0 && env::live(env::SPLIT_WALK) != 1;      // (1: slices of the tile list instead)
   rp.per_xcd = xchunks ? -1 : (sliced ? (ntiles + 7) / 8 : 0);
   rp.nblocks = xchunks ? int64_t(ntiles) * rp.ksplit : (sliced ? int64_t(8) * rp.per_xcd * rp.ksplit : int64_t(ntiles) * rp.ksplit);
   if (rp.nblocks > 0x7fffffffLL) fail(CCZ_EUNSUP, "gram (split route): grid too large");
@@ -481,8 +477,7 @@ static SplitRowPlan split_row_plan(int64_t ksteps, int ntiles, int64_t max_steps
 // (2.50 -> 2.60 ms): the bf16 MFMA bursts pull the chip's clock down and the encoders' GEMMs next to them run ~10 % longer
 // (profiles/r06_loss_c4.md).  So small batches keep the fp32 kernels unless asked.  CCZ_LOSS_K1_SPLIT=0: never.
 bool gram_partials_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, GramPartials* out) {
-  const char* e_on = getenv("CCZ_LOSS_K1_SPLIT");
-  const int mode = e_on ? atoi(e_on) : 1;
+  const int mode = env::live(env::LOSS_K1_SPLIT);
   if (mode == 0 || c->k1_route == CCZ_K1_FP32) return false;
   if (n_views < 1 || n_views > 8 || n < (mode >= 2 ? 4096 : 32768)) return false;
   int64_t D = 0;
@@ -495,9 +490,8 @@ bool gram_partials_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int
   const SplitTables tb = split_tables(c, cols, n_views);
   const int64_t ksteps = (n + SP_K - 1) / SP_K;
   const SplitRowPlan rp = split_row_plan(ksteps, tb.ntiles, 16384 / SP_K, ncu);
-  static const int64_t partial_cap = [] { const char* e = getenv("CCZ_GRAM_PARTIAL_MB"); return (e ? atoll(e) : 192LL) << 20; }();
   const int64_t partial_bytes = rp.ksplit * int64_t(tb.ntiles) * (SP_T * SP_T * 4);
-  if (rp.per_xcd != 0 || partial_bytes > partial_cap) return false;           // a chip-filling grid: the general route through ccz_moments
+  if (rp.per_xcd != 0 || partial_bytes > env::gram_partial_cap()) return false;           // a chip-filling grid: the general route through ccz_moments
   SplitViews vws{};
   const bool aligned = split_views_arg(views, n_views, &vws);
   double* msq = static_cast<double*>(dev_alloc(c, size_t(D) * 8));
@@ -528,8 +522,7 @@ bool gram_partials_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int
 // Does the split route pay for this launch?  (auto mode)  It carries an HBM pass over the rows, a reduce over the partial
 // tiles and two small table uploads; below ~1e11 algorithmic flops the fp32 kernel's single launch wins.
 bool gram_split_worthwhile(int64_t n, int64_t D) {
-  const char* e_fl = getenv("CCZ_SPLIT_MIN_FLOP");
-  const double min_flop = e_fl ? atof(e_fl) : 1e11;
+  const double min_flop = env::live(env::SPLIT_MIN_FLOP);
   // n >= 32768: from there on the route's error against float64 moments is at or below the fp32 kernel's on the same rows
   // (the dropped 2^-16 terms average out over the rows, the fp32 kernel's accumulation error grows with them; measured
   // crossover 20k - 30k rows, tools/k1_route_check.py) -- below it the route is only taken when asked for
@@ -547,7 +540,7 @@ bool gram_split_worthwhile(int64_t n, int64_t D) {
 // 131072 rows stay whole).
 static std::vector<int64_t> split_pieces(int64_t rows, int64_t unit) {
   std::vector<double> fr;
-  if (const char* e = getenv("CCZ_SPLIT_PIPE")) {
+  if (const char* e = env::live(env::SPLIT_PIPE)) {
     fr.clear();
     for (const char* q = e; *q;) {
       char* end = nullptr;
@@ -580,8 +573,7 @@ static std::vector<int64_t> split_pieces(int64_t rows, int64_t unit) {
 static hipStream_t split_side_stream(ccz_ctx* c) {
   Impl* im = impl(c);
   const int ncu = std::max(1, im->props.multiProcessorCount);
-  const char* e = getenv("CCZ_SPLIT_PIPE_CUS");                  // read per call (an A/B switch): a new width makes a new stream
-  const int cus = e ? atoi(e) : 64;
+  const int cus = env::live(env::SPLIT_PIPE_CUS);
   if (im->split_stream_tried && cus == im->split_stream_req) return im->split_stream;
   if (im->split_stream) {
     (void)hipStreamSynchronize(im->split_stream);
@@ -640,8 +632,7 @@ void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   try {
     // ---- rows per launch (scratch budget) and per workgroup ----
     const int ncu = std::max(1, im->props.multiProcessorCount);
-    const char* rows_env = getenv("CCZ_SPLIT_ROWS");       // fp32 accumulation length (rows per workgroup), default 16384
-    const int64_t max_steps = std::max<int64_t>(1, (rows_env ? atoll(rows_env) : 16384LL) / SP_K);
+    const int64_t max_steps = std::max<int64_t>(1, env::live(env::SPLIT_ROWS) / SP_K);
     const double per_row = double(np) * SP_PSTEP / SP_K + double(ntiles) * (SP_T * SP_T * 4) / double(max_steps * SP_K);
     const size_t budget = split_scratch_budget(c);
     int64_t launch_rows = int64_t(double(budget) / per_row) / (max_steps * SP_K) * (max_steps * SP_K);

@@ -29,7 +29,7 @@ struct Impl {
   // are captured once per (shape, pointers) into a hipGraph and replayed
   std::vector<GraphEntry> graphs;
   uint64_t tick = 0;
-  int graphs_on = 1;
+  int graphs_on = 0;            // set by ccz_create (CCZ_GRAPHS); cleared for good when a capture fails
   hipStream_t own_stream = nullptr;   // the handle's default stream (blocking: ordered with the null stream)
   hipEvent_t ev[4];
   int* d_flag = nullptr;      // small device scratch: ints

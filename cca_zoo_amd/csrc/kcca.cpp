@@ -10,9 +10,8 @@
 // top-k eigenvectors are the top-k right singular vectors of G' (formed directly).  Host work: the n eigenvalues per view and k-sized
 // bookkeeping.  This file is not part of the host test double (tests/hostsim builds solve.cpp only).
 //
-// CCZ_TRACE_PHASES=1: synchronise at the phase boundaries and print the wall time of each phase to stderr.
+// CCZ_TRACE_PHASES=1 times the phases of both drivers (ops.h: PhaseTimer).
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,31 +25,6 @@
 
 namespace ccz {
 namespace {
-
-struct KPhases {
-  ccz_ctx* c;
-  bool on;
-  const char* what;
-  std::chrono::steady_clock::time_point t;
-  std::string line;
-  KPhases(ccz_ctx* c_, const char* w) : c(c_), what(w) {
-    static const int env = [] { const char* e = getenv("CCZ_TRACE_PHASES"); return e ? atoi(e) : 0; }();
-    on = env == 1;
-    if (on) { sync(c); t = std::chrono::steady_clock::now(); }
-  }
-  void mark(const char* name) {
-    if (!on) return;
-    sync(c);
-    const auto now = std::chrono::steady_clock::now();
-    char buf[64];
-    snprintf(buf, sizeof(buf), " %s %.2f", name, std::chrono::duration<double, std::milli>(now - t).count());
-    line += buf;
-    t = now;
-  }
-  ~KPhases() {
-    if (on) fprintf(stderr, "[ccz] %s phases (ms):%s\n", what, line.c_str());
-  }
-};
 
 void check_common(double* const* K, int m, int64_t n, int k, int min_views) {
   if (!K || m < min_views || n < 2 || k < 1) fail(CCZ_EINVAL, "bad argument");
@@ -93,7 +67,7 @@ void kcca_solve_impl(ccz_ctx* c, double* const* K, int m, int64_t n, const doubl
   if (m > 2 && int64_t(m) * n > 16384)
     fail(CCZ_EINVAL, "KCCA with %d views solves a dense (n_views * n_samples)-sized eigenproblem: %lld > 16384", m,
          (long long)(int64_t(m) * n));
-  KPhases ph(c, "kcca");
+  PhaseTimer ph(c, "kcca");
   std::vector<DBuf> E;
   std::vector<std::vector<double>> l(m);
   for (int i = 0; i < m; ++i) {
@@ -177,7 +151,7 @@ void kgcca_solve_impl(ccz_ctx* c, double* const* K, int m, int64_t n, const doub
   if (!cr || !mu) fail(CCZ_EINVAL, "null argument");
   for (int i = 0; i < m; ++i)
     if (!(mu[i] >= 0.0)) fail(CCZ_EINVAL, "view_weights must be non-negative (view %d: %g)", i, mu[i]);
-  KPhases ph(c, "kgcca");
+  PhaseTimer ph(c, "kgcca");
   std::vector<DBuf> E;
   std::vector<std::vector<double>> l(m);
   for (int i = 0; i < m; ++i) {

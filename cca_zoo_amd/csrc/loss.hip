@@ -292,8 +292,7 @@ constexpr int64_t kFusedMaxD = 2048;     // per-view width served by the batched
 bool narrow_ok(const int64_t* dims, int m) {
   for (int a = 0; a < m; ++a)
     if (dims[a] > kFusedMaxD) return false;
-  static const int on = [] { const char* e = getenv("CCZ_LOSS_FUSED"); return e ? atoi(e) : 1; }();
-  return on != 0;
+  return env::once(env::LOSS_FUSED) != 0;
 }
 
 // Gamma (D x D), mean (D) and the loss accumulator tr(A A) (one double, zeroed here) from the moments, for ANY number
@@ -328,7 +327,7 @@ void pair_core(ccz_ctx* c, const double* mom, int64_t n, const int64_t* dims, in
   // (split-K destinations of the product stages below are cleared by the same pass -- see there)
   int64_t dmin = dims[0];
   for (int a = 1; a < m; ++a) dmin = std::min(dmin, dims[a]);
-  static const int split_env = [] { const char* e = getenv("CCZ_LOSS_SPLITK"); return e ? atoi(e) : 2; }();   // 2: 256 workgroups per two-view stage, half the atomics of 4 (profiles/r05_loss_c4.md)
+  const int split_env = env::once(env::LOSS_SPLITK);   // 2: 256 workgroups per two-view stage, half the atomics of 4 (profiles/r05_loss_c4.md)
   const int ks = (narrow && dmin >= 256 && split_env > 1) ? split_env : 1;
   if (ks > 1) {
     for (int a = 0; a < m; ++a) pa.zero_v[a] = Sinv[a].get();
@@ -550,7 +549,7 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
   PoolPtr info(c, LMAXV * sizeof(int));
   // fp32 DCCA batch: K1's partial sums feed the preparation directly (no moments, no gather, no fills, no atomics).
   // Embeddings (post-ReLU, un-normalised) routinely sit far from zero, so the Gram is always pilot-shifted here.
-  static const int fast_env = [] { const char* e = getenv("CCZ_LOSS_FAST"); return e ? atoi(e) : 1; }();
+  const int fast_env = env::once(env::LOSS_FAST);
   GramPartials gp;
   bool fast = false;
   if (fast_env && narrow && dtype == CCZ_F32) fast = gram_partials_f32(c, z, m, n, &gp);

@@ -12,6 +12,7 @@
 // elements.  Functions throw ccz::Error; the C ABI layer converts to codes.
 #pragma once
 
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <functional>
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ccz.h"
+#include "env.h"
 
 struct ccz_ctx {
   int device = 0;
@@ -216,6 +218,22 @@ void wait_deferred(ccz_ctx* c);
 // print, per phase, device time, host time and the shader clock at its end.  No-ops on the host backend.
 void trace_mark(ccz_ctx* c, const char* name);
 void trace_flush(ccz_ctx* c, const char* what);
+
+// Phase timer of a solve driver (solve.cpp; `what` = "rcca", "kcca", "kgcca").  CCZ_TRACE_PHASES=1: synchronise at the phase
+// boundaries and print the wall time of each phase to stderr (this changes the overlap between host and device);
+// =2, for a driver that passes marks = true (the launch-bound rCCA chain): no synchronisation -- trace_mark / trace_flush.
+struct PhaseTimer {
+  ccz_ctx* c;
+  const char* what;
+  int mode;               // 0 off, 1 synchronising wall times, 2 marks
+  std::chrono::steady_clock::time_point t;
+  std::string line;
+  PhaseTimer(ccz_ctx* c, const char* what, bool marks = false);
+  ~PhaseTimer();
+  void mark(const char* name);
+  PhaseTimer(const PhaseTimer&) = delete;
+  PhaseTimer& operator=(const PhaseTimer&) = delete;
+};
 
 // ---- solver drivers (solve.cpp) used by other translation units -------------
 // full symmetric EVD of A (d x d, destroyed): w_host (d, descending), V rows = eigenvectors

@@ -39,8 +39,7 @@ void* dev_alloc(ccz_ctx* c, size_t bytes) {
     return im->pool[best].p;
   }
   void* p = nullptr;
-  static const bool trace = getenv("CCZ_TRACE_POOL") != nullptr;
-  if (trace) fprintf(stderr, "[ccz] pool miss: hipMalloc(%zu) (%zu blocks cached)\n", bytes, im->pool.size());
+  if (env::once(env::TRACE_POOL)) fprintf(stderr, "[ccz] pool miss: hipMalloc(%zu) (%zu blocks cached)\n", bytes, im->pool.size());
   hipError_t e = hipMalloc(&p, bytes);
   if (e != hipSuccess) {
     // release cached blocks and retry once
@@ -114,10 +113,7 @@ void h2d_small(ccz_ctx* c, void* dst, const void* src, size_t bytes) {
 // time of the phase was unchanged, the host sat in the wait.  Waits that are expected to be short therefore POLL the
 // completion event (hipEventQuery) for up to `spin_ms` before they fall back to the blocking call.
 // CCZ_SPIN_WAIT_MS=0 restores the blocking waits.
-static double spin_budget_ms() {
-  static const double v = [] { const char* e = getenv("CCZ_SPIN_WAIT_MS"); return e ? atof(e) : 50.0; }();
-  return v;
-}
+static double spin_budget_ms() { return env::once(env::SPIN_WAIT_MS); }
 struct WaitStats { double total_ms = 0.0, max_ms = 0.0; long count = 0, fell_back = 0; };
 static WaitStats& wait_stats() { static WaitStats w; return w; }
 
@@ -173,12 +169,8 @@ void d2h(ccz_ctx* c, void* dst, const void* src, size_t bytes) {
         im->d2h_pin_dev = nullptr;
       }
     }
-    // CCZ_D2H_MODE (a measurement switch, tools/d2h_probe.py): 0 copy kernel, 8-byte lanes, up to 2048 workgroups (default) |
-    // 1 copy kernel, 16-byte lanes | 2 hipMemcpyAsync into the pinned buffer + polled event | 3 the same + hipStreamSynchronize |
-    // 4 one blocking hipMemcpy into the destination
-    const char* me = std::getenv("CCZ_D2H_MODE");
-    const int mode = me ? std::atoi(me) : 0;
-    const bool trace = std::getenv("CCZ_TRACE_D2H") != nullptr;
+    const int mode = env::live(env::D2H_MODE);
+    const bool trace = env::live(env::TRACE_D2H);
     hipEvent_t* tev = im->d2h_tev;
     const auto th0 = std::chrono::steady_clock::now();
     if (trace) {
@@ -1130,8 +1122,7 @@ static void graph_run(ccz_ctx* c, uint64_t key, F&& fn) {
       CCZ_HIP(hipGraphLaunch(g.exec, st));
       return;
     }
-  static const bool trace = getenv("CCZ_TRACE_POOL") != nullptr;
-  if (trace) fprintf(stderr, "[ccz] graph miss: capturing key %016llx (%zu cached)\n", (unsigned long long)key, im->graphs.size());
+  if (env::once(env::TRACE_POOL)) fprintf(stderr, "[ccz] graph miss: capturing key %016llx (%zu cached)\n", (unsigned long long)key, im->graphs.size());
   if (hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) != hipSuccess) {
     (void)hipGetLastError();
     im->graphs_on = 0;
@@ -1279,10 +1270,8 @@ static void trsm_right_lower_iter(ccz_ctx* c, bool trans, int64_t r, int64_t d, 
 //    inverse rows) -- 8 x (r x 512 x 512 product + rank-512 trailing update) at the big-GEMM rate instead of 64
 //    rank-64 updates that were bound by HBM.
 // ---------------------------------------------------------------------------
-// (CCZ_POTRF_SB: a measurement switch, read once -- 256 / 512 / 1024; every user of the kept inverses sees the same value)
 static const int64_t SB = [] {
-  const char* e = getenv("CCZ_POTRF_SB");
-  const int64_t v = e ? atoll(e) : 512;
+  const int64_t v = env::live(env::POTRF_SB);
   return (v == 256 || v == 1024) ? v : int64_t(512);
 }();
 
@@ -1324,10 +1313,7 @@ static void potrf_lower_batched_steps(ccz_ctx* c, int count, double* const* A, c
 //
 // keep[i] (optional, nsb * 512 * 512 doubles): receives the inverses of matrix i's diagonal super-blocks for later
 // triangular solves with the factor (trsm_right_lower_aux).
-static int potrf_lookahead() {
-  static const int m = [] { const char* e = getenv("CCZ_POTRF_LOOKAHEAD"); return e ? atoi(e) : 1; }();
-  return m;
-}
+static int potrf_lookahead() { return env::once(env::POTRF_LOOKAHEAD); }
 
 struct StreamSwap {
   ccz_ctx* c;
@@ -1460,10 +1446,9 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
         {
           StreamSwap sw(c, s_aux);
           // the chain kernel's helper workgroups spin while they wait: next to the update GEMMs of the main stream they get a
-          // bounded share of the chip (CCZ_CHAIN_WGS_LA, default 64 workgroups)
-          static const int la_cap = [] { const char* e = getenv("CCZ_CHAIN_WGS_LA"); return e ? atoi(e) : 64; }();
+          // bounded share of the chip
           const int cap0 = im->chain_cap;
-          im->chain_cap = la_cap;
+          im->chain_cap = env::once(env::CHAIN_WGS_LA);
           try { factor(J + 1); } catch (...) { im->chain_cap = cap0; throw; }
           im->chain_cap = cap0;
         }
@@ -1603,15 +1588,8 @@ static void trsm_right_lower_sb(ccz_ctx* c, bool trans, int64_t r, int64_t d, co
 
 // Dispatch: the recursive forms put the flops into large-K GEMMs but issue ~40% more (tiny) launches;
 // they pay off once the matrices are big enough for the GEMMs to dominate the launch latency.
-static int solver_mode() {
-  static const int m = [] { const char* e = getenv("CCZ_SOLVER_RECURSIVE"); return e ? atoi(e) : -1; }();
-  return m;   // -1: automatic, 0: iterative, 1: recursive
-}
-
-static int solver_legacy() {
-  static const int m = [] { const char* e = getenv("CCZ_SOLVER_LEGACY"); return e ? atoi(e) : 0; }();
-  return m;   // 1: the round-1 blocked Cholesky / rank-64 triangular solves
-}
+static int solver_mode() { return env::once(env::SOLVER_RECURSIVE); }
+static int solver_legacy() { return env::once(env::SOLVER_LEGACY); }
 
 void potrf_lower_batched(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info) {
   int64_t dmax = 0;
@@ -1662,8 +1640,7 @@ void potrf_lower_batched_aux(ccz_ctx* c, int count, double* const* A, const int6
 
 bool potrf_lower_batched_aux_rider(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info,
                                    double* const* aux, const TrsmRider* rider) {
-  static const int rider_on = [] { const char* e = getenv("CCZ_POTRF_RIDER"); return e ? atoi(e) : 1; }();
-  if (solver_legacy() || !aux || !rider_on || !rider) { potrf_lower_batched_aux(c, count, A, d, lda, info, aux); return false; }
+  if (solver_legacy() || !aux || !env::once(env::POTRF_RIDER) || !rider) { potrf_lower_batched_aux(c, count, A, d, lda, info, aux); return false; }
   return potrf_lower_batched_new(c, count, A, d, lda, info, aux, rider);
 }
 
@@ -1696,7 +1673,7 @@ void trsm_right_lower_aux_multi(ccz_ctx* c, int count, bool trans, const int64_t
     for (int b = 0; b < count; ++b) trsm_right_lower_aux(c, trans, r[b], d[b], L[b], ldl[b], X[b], ldx[b], aux ? aux[b] : nullptr);
     return;
   }
-  static const int bp_split = [] { const char* e = getenv("CCZ_BACKPROJ_SPLIT"); return e ? atoi(e) : 4; }();
+  const int bp_split = env::once(env::BACKPROJ_SPLIT);
   int64_t total = 0, offs[8], nsb[8], max_nsb = 0;
   for (int b = 0; b < count; ++b) {
     offs[b] = total;
@@ -1892,8 +1869,7 @@ int jacobi_rows(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double
     if (sw < 0) fail(CCZ_ENOCONV, "Jacobi did not converge in %d sweeps (p=%lld, q=%lld)", max_sweeps, (long long)p, (long long)q);
     return sw;
   }
-  static const bool legacy = [] { const char* e = getenv("CCZ_EVD_LEGACY"); return e && atoi(e) != 0; }();
-  if (!legacy) {
+  if (env::once(env::EVD_LEGACY) == 0) {
     // evd_block.hip: 32-row blocks, Gram blocks + rotations as MFMA tiles.  It wants a multiple of 64 rows and even
     // leading dimensions (16-byte row pieces): pad with zero rows (they never rotate) when the caller's shape differs.
     const int64_t pp = (p + 63) / 64 * 64;
@@ -2458,10 +2434,7 @@ static size_t syev_small_lds(int64_t d) {
   return size_t(2 * pe * sd + 18 + 4 * np) * 8;          // H, V', 16 maxima, 2 counters (+ pad), 2 x np (c, s)
 }
 
-static int syev_mode() {   // 0: one-sided rows (round 1), 1: fused two-sided LDS kernel (d <= 96), 2: packed H + replayed V' (d <= 160)
-  static const int m = [] { const char* e = getenv("CCZ_SYEV_TWOSIDED"); return e ? atoi(e) : 2; }();
-  return m;
-}
+static int syev_mode() { return env::once(env::SYEV_TWOSIDED); }
 
 int syev_small_max(ccz_ctx*) { return syev_mode() == 2 ? 160 : (syev_mode() == 1 ? 96 : 0); }
 
@@ -2481,8 +2454,7 @@ int syev_small(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_de
       hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds_need, stream(c), int(d), A, lda, w_dev, log, tol,
                          max_sweeps, im->d_flag + 2);
     };
-    static const int chase_on = [] { const char* e = getenv("CCZ_SYEV_CHASE"); return e ? atoi(e) : 1; }();
-    if (chase_on && Vrows) {
+    if (env::once(env::SYEV_CHASE) && Vrows) {
       // one launch: the solve and, next to it, the replay chasing its log (k_syev_chase)
       unsigned* sync = reinterpret_cast<unsigned*>(im->d_flag + 32);      // (words 8 .. 15 are the pivot flags of the factorizations)
       CCZ_HIP(hipMemsetAsync(sync, 0, 2 * sizeof(unsigned), stream(c)));

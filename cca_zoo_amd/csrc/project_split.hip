@@ -209,8 +209,7 @@ __global__ __launch_bounds__(256, 1) void k_project_split(const float* __restric
 }
 
 bool project_split_eligible(ccz_ctx* c, int64_t n, int64_t d, int64_t k, int64_t ld, const void* X, int64_t ldo) {
-  const char* e_on = getenv("CCZ_PROJECT_SPLIT");
-  if (e_on && atoi(e_on) == 0) return false;
+  if (env::live(env::PROJECT_SPLIT) == 0) return false;
   // OPT-IN: only when the handle's route was set to CCZ_K1_BF16X2 explicitly.  A projection is a random-walk sum, so the dropped
   // 2^-17 terms do not average out as in K1's coherent sums: outputs agree with a float64 product to 4.5e-6 (two planes) / 2.9e-6
   // (three planes, five products) of their scale against the fp32 kernel's 1.3e-6 -- inside the path's 1e-3 bar, but narrower
@@ -228,8 +227,7 @@ void project_split(ccz_ctx* c, const float* X, int64_t n, int64_t d, int64_t ld,
   hipStream_t st = stream(c);
   const int64_t nsteps = d / 16;
   // two planes / three products by default (4.07 ms, 4.5e-6); CCZ_PROJECT_PLANES=3: three planes / five products (4.63 ms, 2.9e-6)
-  const char* e_pl = getenv("CCZ_PROJECT_PLANES");
-  const int nplanes = (e_pl && atoi(e_pl) == 3) ? 3 : 2;
+  const int nplanes = env::live(env::PROJECT_PLANES) == 3 ? 3 : 2;
   char* planes = static_cast<char*>(dev_alloc(c, size_t(nsteps) * size_t(nplanes) * 2048));
   float* pilot = static_cast<float*>(dev_alloc(c, size_t(d) * 4));
   double* corr = static_cast<double*>(dev_alloc(c, 64 * 8));

@@ -64,10 +64,7 @@ std::vector<int64_t> offsets(const int64_t* dims, int m) {
 //     tests/test_gpu_seams_r5.py::test_rank_detection_between_the_kernels holds the detected rank at d = 320 / 256 / 700.
 // The legacy route below (CCZ_EVD_LEGACY=1): rows of (A + shift I) orthogonalised, shift = ||A||_inf so that +lam / -lam
 // pairs (MCCA with two views has them exactly) cannot mix; psd skips the shift.
-static bool legacy_evd() {   // CCZ_EVD_LEGACY=1: rounds 1-3's launch-per-round one-sided Jacobi above d = 160 (A/B)
-  static const bool v = [] { const char* e = getenv("CCZ_EVD_LEGACY"); return e && atoi(e) != 0; }();
-  return v;
-}
+static bool legacy_evd() { return env::once(env::EVD_LEGACY) != 0; }
 static int syev_full_impl(ccz_ctx* c, double* A, int64_t d, bool psd, std::vector<double>& w,
                           double* Vrows, int64_t ldv, double small_tol = 2.220446049250313e-16) {
   if (!psd && d >= 2 && d <= syev_small_max(c)) {
@@ -232,8 +229,7 @@ void rayleigh_ritz(ccz_ctx* c, const SymOp& op, int64_t b, double*& X, double*& 
   transpose(c, b, b, H, b, Hs, b);
   axpby2d(c, b, b, 0.5, H, b, 0.5, Hs, b);            // symmetrise
   const int jsw = syev_full_impl(c, H, b, false, st.theta, Vr, b, jac_tol);      // rows of Vr = Ritz coefficient vectors
-  static const bool trace_rr = getenv("CCZ_TRACE_SOLVER") != nullptr;
-  if (trace_rr) fprintf(stderr, "[ccz] rayleigh_ritz b=%lld: %d Jacobi sweeps at threshold %.1e\n", (long long)b, jsw, jac_tol);
+  if (env::once(env::TRACE_SOLVER)) fprintf(stderr, "[ccz] rayleigh_ritz b=%lld: %d Jacobi sweeps at threshold %.1e\n", (long long)b, jsw, jac_tol);
   gemm(c, false, true, p, b, b, 1.0, X, b, Vr, b, 0.0, tmp, b);
   std::swap(X, tmp);                                    // X = X C ; tmp = old X (free)
   gemm(c, false, true, p, b, b, 1.0, Y, b, Vr, b, 0.0, tmp, b);
@@ -299,7 +295,7 @@ void topk_symmetric(ccz_ctx* c, const SymOp& op, int k, std::vector<double>& the
   RitzState st;
   // the first Rayleigh-Ritz feeds the filter design, not the answer (unless the block spans everything): a Jacobi threshold of
   // 1e-9 leaves Ritz values good to 1e-18 of the scale and saves the last one or two of its ~8 sweeps (CCZ_RR1_TOL; 0 = full)
-  static const double rr1_tol = [] { const char* e = getenv("CCZ_RR1_TOL"); return e ? atof(e) : 1e-9; }();
+  const double rr1_tol = env::once(env::RR1_TOL);
   rayleigh_ritz(c, op, b, X, Y, Z, st, (b < p && rr1_tol > 2.220446049250313e-16) ? rr1_tol : 2.220446049250313e-16);
   const double tol = 1e-11;
   const int max_cycles = 200;
@@ -310,8 +306,7 @@ void topk_symmetric(ccz_ctx* c, const SymOp& op, int k, std::vector<double>& the
     double worst = 0.0;
     for (int i = 0; i < k; ++i) worst = std::max(worst, st.resid[i]);
     if (worst <= tol * scale) {
-      static const bool trace_done = getenv("CCZ_TRACE_SOLVER") != nullptr;
-      if (trace_done)
+      if (env::once(env::TRACE_SOLVER))
         fprintf(stderr, "[ccz] topk p=%lld k=%d b=%lld done after %d cycle(s): worst/scale %.3e\n", (long long)p, k, (long long)b, cycle, worst / scale);
       theta.assign(st.theta.begin(), st.theta.begin() + k);
       copy2d(c, p, k, X, b, Xout, k);
@@ -333,21 +328,18 @@ void topk_symmetric(ccz_ctx* c, const SymOp& op, int k, std::vector<double>& the
     if (x > 1.0 + 1e-12) {
       // x1000 margin: the cosh estimate is optimistic by ~10x in practice, and landing a hair above the tolerance
       // costs a whole extra filter + orthonormalise + Rayleigh-Ritz cycle (one more degree costs two GEMMs)
-      static const double margin = [] { const char* e = getenv("CCZ_CHEB_MARGIN"); return e ? atof(e) : 1e3; }();
-      const double need = std::max(worst / (tol * scale), 2.0) * margin;
+      const double need = std::max(worst / (tol * scale), 2.0) * env::once(env::CHEB_MARGIN);
       degree = int(std::ceil(std::acosh(need) / std::acosh(x)));
     }
-    static const int max_degree = [] { const char* e = getenv("CCZ_CHEB_MAXDEG"); return e ? atoi(e) : 40; }();
+    const int max_degree = env::once(env::CHEB_MAXDEG);
     // The FIRST filter is sized from the Ritz values of two power steps: where the wanted end of the spectrum is dense (x close to
     // 1: MCCA 4 x 2048 x = 1.13, GCCA D = 16384 x = 1.09) those underestimate the gap badly -- the estimate asked for 63 / 70 degrees,
     // the cap of 40 converged both to 4e-14 / 9e-14 in one cycle, and so did 22 (MCCA) and 26 (GCCA: 9e-12), measured in round 6
     // (tools/solve_probe.py with CCZ_TRACE_SOLVER=1 and CCZ_CHEB_MAXDEG).  A filter that falls short costs one more, cheap cycle
     // (accurate Ritz values then: degree 7 at GCCA's shape, 157 ms against 166 with the old cap) -- so the first cycle is capped lower.
-    static const int first_cap = [] { const char* e = getenv("CCZ_CHEB_FIRSTCAP"); return e ? atoi(e) : 28; }();
-    const int cap = cycle == 0 ? std::min(max_degree, std::max(2, first_cap)) : max_degree;
+    const int cap = cycle == 0 ? std::min(max_degree, std::max(2, env::once(env::CHEB_FIRSTCAP))) : max_degree;
     degree = std::min(cap, std::max(2, degree) + boost);
-    static const bool trace = getenv("CCZ_TRACE_SOLVER") != nullptr;
-    if (trace)
+    if (env::once(env::TRACE_SOLVER))
       fprintf(stderr, "[ccz] topk p=%lld k=%d b=%lld cycle %d: worst/scale %.3e  x %.6f  degree %d\n", (long long)p, k,
               (long long)b, cycle, worst / scale, x, degree);
     chebyshev_filter(c, op, b, degree, a, cut, aL, X, Y, Z);
@@ -648,35 +640,26 @@ void chol_solve_inplace(ccz_ctx* c, int64_t d, int64_t r, const double* L, int64
 // ===========================================================================
 // rCCA / CCA / PLS      reference: cca_zoo/linear/_rcca.py:69-101
 // ===========================================================================
-// CCZ_TRACE_PHASES=1: synchronise at the phase boundaries of the rCCA solve and print the wall time of each phase;
-// CCZ_TRACE_PHASES=2: no synchronisation -- events, host time stamps and shader-clock probes (ops.h::trace_mark).
-// (Measurement aids for the launch-bound chain; mode 1 changes the overlap between host and device.)
-struct PhaseTrace {
-  ccz_ctx* c;
-  int mode;
-  std::chrono::steady_clock::time_point t;
-  std::string line;
-  explicit PhaseTrace(ccz_ctx* c_) : c(c_) {
-    static const int env = [] { const char* e = getenv("CCZ_TRACE_PHASES"); return e ? atoi(e) : 0; }();
-    mode = env;
-    if (mode == 1) { sync(c); t = std::chrono::steady_clock::now(); }
-    if (mode == 2) trace_mark(c, "start");
-  }
-  void mark(const char* name) {
-    if (mode == 2) { trace_mark(c, name); return; }
-    if (mode != 1) return;
-    sync(c);
-    const auto now = std::chrono::steady_clock::now();
-    char buf[64];
-    snprintf(buf, sizeof(buf), " %s %.2f", name, std::chrono::duration<double, std::milli>(now - t).count());
-    line += buf;
-    t = now;
-  }
-  ~PhaseTrace() {
-    if (mode == 1) fprintf(stderr, "[ccz] rcca phases (ms):%s\n", line.c_str());
-    if (mode == 2) { try { trace_flush(c, "rcca"); } catch (...) {} }
-  }
-};
+PhaseTimer::PhaseTimer(ccz_ctx* c_, const char* what_, bool marks) : c(c_), what(what_) {
+  mode = env::once(env::TRACE_PHASES);
+  if (mode == 2 && !marks) mode = 0;
+  if (mode == 1) { sync(c); t = std::chrono::steady_clock::now(); }
+  if (mode == 2) trace_mark(c, "start");
+}
+void PhaseTimer::mark(const char* name) {
+  if (mode == 2) { trace_mark(c, name); return; }
+  if (mode != 1) return;
+  sync(c);
+  const auto now = std::chrono::steady_clock::now();
+  char buf[64];
+  snprintf(buf, sizeof(buf), " %s %.2f", name, std::chrono::duration<double, std::milli>(now - t).count());
+  line += buf;
+  t = now;
+}
+PhaseTimer::~PhaseTimer() {
+  if (mode == 1) fprintf(stderr, "[ccz] %s phases (ms):%s\n", what, line.c_str());
+  if (mode == 2) { try { trace_flush(c, what); } catch (...) {} }
+}
 
 static void rcca_solve_impl(ccz_ctx* c, const double* mom, int64_t n, const int64_t dims[2],
                             const double cc[2], int center, int k, double* W_host, double* means_host,
@@ -692,7 +675,7 @@ static void rcca_solve_impl(ccz_ctx* c, const double* mom, int64_t n, const int6
   // reference: k = min(latent, rank1, rank2); ranks are at most min(n, d)
   int kk = int(std::min<int64_t>({int64_t(k), d1, d2, n}));
 
-  PhaseTrace pt(c);
+  PhaseTimer pt(c, "rcca", /*marks=*/true);
   std::vector<DBuf> Rv(2);
   Rv[0] = DBuf(c, d1 * d1);
   Rv[1] = DBuf(c, d2 * d2);

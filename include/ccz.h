@@ -14,6 +14,8 @@
  *   - matrices are row-major, leading dimension in ELEMENTS, sizes int64_t
  *   - a handle is bound to one device and one HIP stream; not thread-safe
  *   - no C++/torch types cross this boundary
+ *   - the CCZ_* environment variables the library reads (two are named below) are listed, with their defaults and the
+ *     moment each is read, in the one table of cca_zoo_amd/csrc/env.h
  */
 #ifndef CCZ_H
 #define CCZ_H
