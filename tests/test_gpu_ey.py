@@ -25,9 +25,13 @@ def _model(g, **over):
 
 # ---- kernels through the C ABI --------------------------------------------------------------------------------------
 class _Fit:
-    """A raw fit state on rows uploaded to the device (ld > p when pad > 0)."""
+    """A raw fit state on rows uploaded to the device (ld > p when pad > 0).  ``pad``: one int or one per view, filled
+    with ``pad_value``.  ``means``: "auto" (the column means when ``center``), None (``means_dev == NULL``) or a list of
+    vectors whose None entries become NULL entries.  ``offset``: the view starts this many elements into its device
+    buffer, so its base pointer is 4 (float32) or 8 (float64) bytes off a 16-byte boundary when ``offset`` is 1."""
 
-    def __init__(self, views, k, bs, c=0.3, lr=0.01, mom=0.9, center=True, pad=0, chunk=4):
+    def __init__(self, views, k, bs, c=0.3, lr=0.01, mom=0.9, center=True, pad=0, chunk=4, means="auto", offset=0,
+                 pad_value=0.0, tol=0.0):
         from cca_zoo_amd import _backend
 
         self.h = h = _backend.default_handle()
@@ -37,19 +41,23 @@ class _Fit:
         self.n = views[0].shape[0]
         self.bufs, self.mbufs = [], []
         self.varr = (_backend.View * self.m)()
+        pads = list(pad) if isinstance(pad, (list, tuple)) else [pad] * self.m
+        if isinstance(means, str):
+            means = [v.mean(axis=0).astype(v.dtype) for v in views] if center else None
         for i, v in enumerate(views):
-            ld = v.shape[1] + pad
-            padded = np.zeros((v.shape[0], ld), dtype=v.dtype)
+            ld = v.shape[1] + pads[i]
+            padded = np.full((v.shape[0], ld), pad_value, dtype=v.dtype)
             padded[:, : v.shape[1]] = v
-            b = h.to_device(padded)
+            flat = np.concatenate([np.full(offset, pad_value, dtype=v.dtype), padded.reshape(-1)])
+            b = h.to_device(flat)
             self.bufs.append(b)
-            self.varr[i].data, self.varr[i].cols, self.varr[i].ld = b.ptr, v.shape[1], ld
-            if center:
-                self.mbufs.append(h.to_device(v.mean(axis=0).astype(v.dtype)))
-        self.marr = (C.c_void_p * self.m)(*[b.ptr for b in self.mbufs]) if center else None
+            self.varr[i].data, self.varr[i].cols, self.varr[i].ld = b.ptr + offset * v.dtype.itemsize, v.shape[1], ld
+            if means is not None:
+                self.mbufs.append(None if means[i] is None else h.to_device(np.asarray(means[i], dtype=v.dtype)))
+        self.marr = (C.c_void_p * self.m)(*[None if b is None else b.ptr for b in self.mbufs]) if means is not None else None
         self.state = C.c_void_p()
         h.check(h.lib.ccz_ey_create(h.raw, _backend.F32 if self.f32 else _backend.F64, self.m,
-                                    (C.c_int64 * self.m)(*self.p), k, bs, chunk, c, lr, mom, 0.0, C.byref(self.state)))
+                                    (C.c_int64 * self.m)(*self.p), k, bs, chunk, c, lr, mom, tol, C.byref(self.state)))
 
     def set_weights(self, W):
         flat = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in W]))
@@ -67,6 +75,7 @@ class _Fit:
         a, b = C.c_int64(0), C.c_int(0)
         self.h.check(self.h.lib.ccz_ey_steps(self.h.raw, self.state, self.varr, self.marr, self.n, ip, s, C.byref(a),
                                              C.byref(b)))
+        return a.value, b.value
 
     def weights(self):
         out = np.empty(sum(self.p) * self.k)
