@@ -1,0 +1,931 @@
+// ALS models with deflation (PLS_ALS / SCCA_PMD / ParkhomenkoCCA / SCCA_Span): whole sweeps on the device.
+//
+// Reference: cca_zoo/linear/_iterative.py:38-158 (the loop, _target_score), :166-223 (PLS_ALS), :231-380 (SCCA_PMD and its
+// bisection), :631-722 (SCCA_Span), :839-930 (ParkhomenkoCCA), cca_zoo/_utils/_linalg.py:76-116 (soft_threshold, deflate).
+// The reference rewrites a float64 copy of every view once per latent dimension.  After d dimensions that copy equals
+// (I - Q_i Q_i') (X_i - mu_i) with Q_i (n x d) the normalised scores of the earlier dimensions, so here the rows are read
+// where they lie, in their own precision, and the two n-vectors of an update are corrected instead:
+//   X_d w  = s - Q_i (Q_i' s),  s = (X_i - mu_i) w            k_als_score (raw s) + the correction in the next prologue
+//   X_d' t = (X_i - mu_i)' (t - Q_i (Q_i' t))                 k_als_prologue (t~) + k_als_xt
+// One sweep, for M views (Gauss-Seidel: view i's new w_i feeds view i + 1's target):
+//   M x  k_als_score          first sweep of a dimension only (the scores of the initial vectors); returns at once otherwise
+//   per view i:
+//     k_als_prologue          one workgroup: t = sum_{j != i} (s_j - Q_j Q_j' s_j), guarded normalisation, t~ = t - Q_i Q_i' t
+//     k_als_xt                column strips x row chunks: per-chunk partial sums of (X_i - mu_i)' t~
+//     k_als_fold              raw = sum of the chunk partials in chunk order; per-workgroup |raw|_1, max |raw|, sum of squares
+//     k_als_levels x 10 / 13  soft-threshold-at-L1 and top-s only: 31 candidate levels per pass over raw (5 halvings of the
+//                             bisection / 5 bits of the s-th largest magnitude's bit pattern)
+//     k_als_norm              the same two rules: the final level, the sum of squares of the thresholded vector
+//     k_als_apply             w_i = rule(raw) (guarded normalisation), per-workgroup partial |w_i - w_i_old|^2
+//     k_als_score             s_i = (X_i - mu_i) w_i
+//   k_als_finish              one workgroup: delta, the tol / max_iter test; at the end of a dimension the normalised corrected
+//                             scores become column d of every Q_i (guarded), the dimension counter advances
+//   k_als_advance             at the end of a dimension only: column d of the weights <- w, w <- the next initial vectors
+// Every kernel reads the status word first and returns at once when the fit has stopped; the host never waits inside a chunk.
+// All reductions run in a fixed order (per-thread strided sums, wave butterflies, waves and workgroups in index order):
+// two fits of the same inputs give the same bits.
+//
+// Precision: x - mu is rounded in the views' precision (the reference's own `v - v.mean(0)`), then widened; every product
+// and sum is fp64 (the reference's fp64 initial w promotes every product, cca_zoo/linear/_iterative.py:88-89).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "hip_common.h"
+#include "abi_guard.h"
+
+namespace ccz {
+
+namespace {
+
+constexpr int ALS_MAXV = 8;          // views per fit
+constexpr int ALS_MAXK = 32;         // latent dimensions per fit
+constexpr int ALS_STRIP = 1024;      // k_als_xt: columns per workgroup (256 threads x 4)
+constexpr int ALS_SROWS = 4;         // k_als_score: rows per workgroup
+constexpr int ALS_MAXG = 128;        // rule kernels: workgroups per p-vector
+constexpr int ALS_NC = 31;           // candidate levels per k_als_levels pass
+constexpr int ALS_PMD_PASSES = 10;   // 50 halvings, 5 per pass
+constexpr int ALS_SPAN_PASSES = 13;  // bits 62..0 of a non-negative double: 12 passes of 5 bits, one of 3
+
+enum { RULE_NORMALISE = 0, RULE_SOFT_FIXED = 1, RULE_SOFT_L1 = 2, RULE_TOP_S = 3 };
+
+struct AlsStatus {
+  double last_delta[ALS_MAXK];     // delta of the last sweep of each dimension
+  long long iters[ALS_MAXK];       // sweeps taken per dimension
+  long long total;                 // sweeps applied in all
+  int dim;                         // current dimension (== k once stopped)
+  int sweep;                       // sweeps done in the current dimension
+  int stopped;
+  int advance;                     // the last finish ended a dimension (read by k_als_advance)
+};
+
+struct AlsViews {
+  const void* X[ALS_MAXV];
+  const void* mu[ALS_MAXV];
+  int64_t ld[ALS_MAXV];
+  int64_t p[ALS_MAXV];
+  int64_t off[ALS_MAXV];           // offset of view i in the concatenated p-vectors
+  int cs[ALS_MAXV];                // column splits of k_als_score
+  int ng[ALS_MAXV];                // rule workgroups
+  double par[ALS_MAXV];            // rule parameter: tau (soft fixed), the L1 bound (soft at L1), s (top s)
+  int rule[ALS_MAXV];              // the rule of this view (top s with s >= p is plain normalisation)
+};
+
+// the device buffers of one fit
+struct AlsBuf {
+  double* w;        // ptot: current vectors
+  double* raw;      // ptot
+  double* init;     // k x ptot: initial vectors of every dimension
+  double* Wout;     // ptot x k row-major: finished columns
+  double* spart;    // M x csmax x n: column-split partial scores
+  double* Q;        // M x k x n: Q_i column a at (i k + a) n
+  double* tt;       // n: corrected, normalised target
+  double* xpart;    // nchunk x pmax: row-chunk partial sums of X' t~
+  double* fstat;    // M x ALS_MAXG x 3: fold partials (L1, max, sum of squares)
+  double* lpart;    // 2 x ALS_MAXG x ALS_NC: level-pass partials (ping-pong by pass parity)
+  double* lstate;   // (passes + 1) x 2: bracket after each pass (lo, hi) / (bit prefix, unused)
+  double* nstat;    // ALS_MAXG: k_als_norm partial sums of squares
+  double* thr;      // M x 2: final level of view i's last update, 1.0 when thresholding applied
+  double* dpart;    // M x ALS_MAXG: partial |w - w_old|^2
+  int n, M, k, csmax, nchunk, rc;
+  int64_t ptot, pmax;
+};
+
+__device__ __forceinline__ bool als_stopped(const AlsStatus* st) { return st->stopped != 0; }
+
+template <typename T>
+__device__ __forceinline__ bool als_vec_ok(const T* X, int64_t ld, const T* mu) {
+  constexpr int64_t V = 16 / sizeof(T);
+  return (reinterpret_cast<uintptr_t>(X) % 16 == 0) && (ld % V == 0) && (!mu || reinterpret_cast<uintptr_t>(mu) % 16 == 0);
+}
+
+// v[q] = p4[q], q < 4, by 16-byte loads (p4 16-byte aligned)
+__device__ __forceinline__ void als_ld4(const float* p4, float* v) {
+  const float4 a = *reinterpret_cast<const float4*>(p4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+}
+__device__ __forceinline__ void als_ld4(const double* p4, double* v) {
+  const double2 a = *reinterpret_cast<const double2*>(p4), b = *reinterpret_cast<const double2*>(p4 + 2);
+  v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+}
+
+// four consecutive entries starting at f0 (zero beyond p); whole-line loads when `vec` and the four lie inside p
+template <typename T>
+__device__ __forceinline__ void als_load4(const T* base, int64_t f0, int64_t p, bool vec, T* v) {
+  if (vec && f0 + 3 < p) {
+    als_ld4(base + f0, v);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = f0 + q < p ? base[f0 + q] : T(0);
+  }
+}
+
+// deterministic sums / maxima over a wave and over a workgroup of NW waves (every thread gets the result)
+__device__ __forceinline__ double als_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double als_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int NW>
+__device__ __forceinline__ double als_block_sum(double v, double* sh) {
+  v = als_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) t += sh[w];
+  return t;
+}
+template <int NW>
+__device__ __forceinline__ double als_block_max(double v, double* sh) {
+  v = als_wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = sh[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t = fmax(t, sh[w]);
+  return t;
+}
+
+__device__ __forceinline__ double als_soft(double x, double t) {
+  const double a = fabs(x) - t;
+  return a > 0.0 ? copysign(a, x) : 0.0;
+}
+
+// ---- score: column-split partial sums of s = (X - mu) w ----------------------------------------------------------------
+// grid (ceil(n / 4), cs), 256 threads: 4 rows x one column range per workgroup, 4 consecutive columns per thread and step.
+// first_only: the scores of a dimension's initial vectors -- runs only while no sweep of the dimension is done.
+template <typename T>
+__global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
+                                                  const double* __restrict__ w, double* __restrict__ spart, int first_only,
+                                                  const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  if (first_only && st->sweep != 0) return;
+  __shared__ double sh[4];
+  const int r0 = blockIdx.x * ALS_SROWS;
+  const int cs = gridDim.y;
+  // column range of this split, in units of 4 columns so that every split starts on a whole line
+  const int64_t units = (p + 3) / 4, per = (units + cs - 1) / cs;
+  const int64_t c0 = 4 * per * blockIdx.y, c1 = c0 + 4 * per < p ? c0 + 4 * per : p;
+  const bool vec = als_vec_ok(X, ld, mu);
+  const bool wvec = reinterpret_cast<uintptr_t>(w) % 16 == 0;
+  double acc[ALS_SROWS] = {0.0, 0.0, 0.0, 0.0};
+  const T* rowp[ALS_SROWS];
+  bool live[ALS_SROWS];
+#pragma unroll
+  for (int t = 0; t < ALS_SROWS; ++t) {
+    live[t] = r0 + t < n;
+    rowp[t] = X + int64_t(live[t] ? r0 + t : 0) * ld;
+  }
+#pragma unroll 2
+  for (int64_t f0 = c0 + 4 * threadIdx.x; f0 < c1; f0 += 1024) {
+    double wv[4];
+    T m[4] = {T(0), T(0), T(0), T(0)};
+    als_load4<double>(w, f0, c1, wvec, wv);
+    if (mu) als_load4<T>(mu, f0, c1, vec, m);
+#pragma unroll
+    for (int t = 0; t < ALS_SROWS; ++t) {
+      if (!live[t]) continue;
+      T x[4];
+      als_load4<T>(rowp[t], f0, c1, vec, x);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[t] += double(T(x[q] - m[q])) * wv[q];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < ALS_SROWS; ++t) {
+    const double s = als_block_sum<4>(acc[t], sh);
+    if (threadIdx.x == 0 && live[t]) spart[int64_t(blockIdx.y) * n + r0 + t] = s;
+  }
+}
+
+// ---- the one-workgroup kernels: prologue and finish ------------------------------------------------------------------
+constexpr int ALS_PT = 1024;   // threads of the one-workgroup kernels
+
+// dst[r] (+)= s_j[r] - (Q_j Q_j' s_j)[r] over all rows, s_j = the sum of view j's column-split partials, d columns of Q_j
+__device__ void als_corrected_score(const AlsBuf& B, const AlsViews& vw, int j, int d, double* dst, bool accumulate, double* coef,
+                                    double* sh) {
+  const int n = B.n, cs = vw.cs[j];
+  const double* sp = B.spart + int64_t(j) * B.csmax * n;
+  const double* Q = B.Q + int64_t(j) * B.k * n;
+  for (int a = 0; a < d; ++a) {
+    double acc = 0.0;
+    for (int r = threadIdx.x; r < n; r += ALS_PT) {
+      double s = 0.0;
+      for (int c = 0; c < cs; ++c) s += sp[int64_t(c) * n + r];
+      acc += Q[int64_t(a) * n + r] * s;
+    }
+    const double c = als_block_sum<ALS_PT / 64>(acc, sh);
+    if (threadIdx.x == 0) coef[a] = c;
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < n; r += ALS_PT) {
+    double s = 0.0;
+    for (int c = 0; c < cs; ++c) s += sp[int64_t(c) * n + r];
+    double corr = 0.0;
+    for (int a = 0; a < d; ++a) corr += Q[int64_t(a) * n + r] * coef[a];
+    dst[r] = (accumulate ? dst[r] : 0.0) + (s - corr);
+  }
+  __syncthreads();
+}
+
+// t~ of view i into B.tt (cca_zoo/linear/_iterative.py:138-158 on the deflated views)
+__global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  const int n = B.n, d = st->dim;
+  bool first = true;
+  for (int j = 0; j < B.M; ++j) {
+    if (j == i) continue;
+    als_corrected_score(B, vw, j, d, B.tt, !first, coef, sh);
+    first = false;
+  }
+  if (first) {                           // a single view has no target
+    for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] = 0.0;
+    __syncthreads();
+  }
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < n; r += ALS_PT) acc += B.tt[r] * B.tt[r];
+  const double nrm = sqrt(als_block_sum<ALS_PT / 64>(acc, sh));
+  if (nrm > 1e-12)
+    for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] /= nrm;     // every thread rereads only its own rows below
+  const double* Q = B.Q + int64_t(i) * B.k * n;
+  for (int a = 0; a < d; ++a) {
+    double q = 0.0;
+    for (int r = threadIdx.x; r < n; r += ALS_PT) q += Q[int64_t(a) * n + r] * B.tt[r];
+    const double c = als_block_sum<ALS_PT / 64>(q, sh);
+    if (threadIdx.x == 0) coef[a] = c;
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < n; r += ALS_PT) {
+    double corr = 0.0;
+    for (int a = 0; a < d; ++a) corr += Q[int64_t(a) * n + r] * coef[a];
+    B.tt[r] -= corr;
+  }
+}
+
+// once per sweep: delta, the stop test, the end of a dimension (cca_zoo/linear/_iterative.py:109-117, :91-93, _linalg.py:108-116)
+__global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, double tol, int max_iter, AlsStatus* st) {
+  if (als_stopped(st)) {
+    if (threadIdx.x == 0) st->advance = 0;
+    return;
+  }
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  __shared__ int end_dim;
+  const int n = B.n, d = st->dim;
+  double delta = 0.0;
+  for (int i = 0; i < B.M; ++i) {
+    const double s = als_block_sum<ALS_PT / 64>(int(threadIdx.x) < vw.ng[i] ? B.dpart[i * ALS_MAXG + threadIdx.x] : 0.0, sh);
+    const double di = sqrt(s);
+    if (di > delta) delta = di;             // Python's max(): a NaN after the first entry never wins ...
+    if (i == 0 && di != di) delta = di;     // ... and a NaN first entry always does
+  }
+  if (threadIdx.x == 0) {
+    const int sweep = st->sweep + 1;
+    st->total += 1;
+    st->last_delta[d] = delta;
+    st->iters[d] = sweep;
+    end_dim = (delta < tol || sweep >= max_iter) ? 1 : 0;
+    st->sweep = end_dim ? 0 : sweep;
+    st->advance = end_dim;
+  }
+  __syncthreads();
+  if (!end_dim) return;
+  // column d of every Q_i: the corrected score over its norm when |s|^2 > 1e-12, else zeros (no deflation)
+  for (int i = 0; i < B.M; ++i) {
+    double* q = B.Q + (int64_t(i) * B.k + d) * n;
+    als_corrected_score(B, vw, i, d, q, false, coef, sh);
+    double acc = 0.0;
+    for (int r = threadIdx.x; r < n; r += ALS_PT) acc += q[r] * q[r];
+    const double ns = als_block_sum<ALS_PT / 64>(acc, sh);
+    const double nrm = sqrt(ns);
+    for (int r = threadIdx.x; r < n; r += ALS_PT) q[r] = ns > 1e-12 ? q[r] / nrm : 0.0;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    st->dim = d + 1;
+    if (d + 1 >= B.k) st->stopped = 1;
+  }
+}
+
+// at the end of a dimension: Wout[:, dim - 1] <- w, w <- init[dim]
+__global__ void __launch_bounds__(256) k_als_advance(AlsBuf B, const AlsStatus* st) {
+  if (!st->advance) return;
+  const int d = st->dim - 1;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < B.ptot; f += int64_t(gridDim.x) * 256) {
+    B.Wout[f * B.k + d] = B.w[f];
+    if (d + 1 < B.k) B.w[f] = B.init[int64_t(d + 1) * B.ptot + f];
+  }
+}
+
+// ---- xt: per-chunk partial sums of (X - mu)' t~ ------------------------------------------------------------------------
+// grid (ceil(p / 1024), nchunk), 256 threads: thread t owns columns 1024 bx + 4 t .. + 3 over rows [rc by, rc (by + 1))
+template <typename T>
+__global__ void __launch_bounds__(256) k_als_xt(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n, int rc,
+                                               const double* __restrict__ tt, double* __restrict__ xpart, const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  const int64_t f0 = int64_t(blockIdx.x) * ALS_STRIP + 4 * threadIdx.x;
+  if (f0 >= p) return;
+  const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
+  const bool vec = als_vec_ok(X, ld, mu);
+  T m[4] = {T(0), T(0), T(0), T(0)};
+  if (mu) als_load4<T>(mu, f0, p, vec, m);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int r = r0; r < r1; ++r) {
+    T x[4];
+    als_load4<T>(X + int64_t(r) * ld, f0, p, vec, x);
+    const double t = tt[r];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] += double(T(x[q] - m[q])) * t;
+  }
+  double* out = xpart + int64_t(blockIdx.y) * p;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (f0 + q < p) out[f0 + q] = acc[q];
+}
+
+// ---- the rule -------------------------------------------------------------------------------------------------------
+// raw = the chunk partials summed in chunk order; per-workgroup (|raw|_1, max |raw|, sum of squares of raw -- of
+// soft(raw, tau) for the fixed soft threshold)
+__global__ void __launch_bounds__(256) k_als_fold(const double* __restrict__ xpart, int nchunk, int64_t p, double* __restrict__ raw,
+                                                 int rule, double par, double* __restrict__ fstat, const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  __shared__ double sh[4];
+  double l1 = 0.0, mx = 0.0, ss = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    double v = 0.0;
+    for (int c = 0; c < nchunk; ++c) v += xpart[int64_t(c) * p + f];
+    raw[f] = v;
+    const double a = fabs(v);
+    l1 += a;
+    mx = fmax(mx, a);
+    const double u = rule == RULE_SOFT_FIXED ? als_soft(v, par) : v;
+    ss += u * u;
+  }
+  l1 = als_block_sum<4>(l1, sh);
+  mx = als_block_max<4>(mx, sh);
+  ss = als_block_sum<4>(ss, sh);
+  if (threadIdx.x == 0) {
+    fstat[3 * blockIdx.x + 0] = l1;
+    fstat[3 * blockIdx.x + 1] = mx;
+    fstat[3 * blockIdx.x + 2] = ss;
+  }
+}
+
+// the fold statistics of one view over its ng <= 256 workgroups, by a whole workgroup of 256 threads (fixed order: one
+// partial per thread, wave butterflies, waves in index order); every thread gets the result
+__device__ __forceinline__ void als_fold_totals(const double* fstat, int ng, double* l1, double* mx, double* ss, double* sh) {
+  const int t = threadIdx.x;
+  *l1 = als_block_sum<4>(t < ng ? fstat[3 * t + 0] : 0.0, sh);
+  *mx = als_block_max<4>(t < ng ? fstat[3 * t + 1] : 0.0, sh);
+  *ss = als_block_sum<4>(t < ng ? fstat[3 * t + 2] : 0.0, sh);
+}
+
+// the sums of the previous level pass's partials over the workgroups in index order: thread c < 31 owns candidate c
+__device__ __forceinline__ void als_level_totals(const double* lpart, int pass, int ng, double* tot) {
+  if (pass > 0 && threadIdx.x < ALS_NC) {
+    const double* prev = lpart + size_t((pass - 1) & 1) * ALS_MAXG * ALS_NC;
+    double s = 0.0;
+    for (int g = 0; g < ng; ++g) s += prev[g * ALS_NC + threadIdx.x];
+    tot[threadIdx.x] = s;
+  }
+  __syncthreads();
+}
+
+// The bracket after `pass` passes, by thread 0 of every workgroup (all compute the same bits): from the bracket after
+// pass - 1 (lstate) and the sums `tot` of pass - 1's partials (als_level_totals).  Soft at L1 (cca_zoo/linear/_iterative.py:245-253): five halvings
+// walk the heap of 31 mids, lo = mid when |soft(raw, mid)|_1 > bound, else hi = mid.  Top s: the largest 5-bit digit v whose
+// candidate prefix | v << shift still has at least s magnitudes at or above it.
+__device__ void als_bracket(int rule, int pass, double par, double mx, const double* lstate, const double* tot, double* lo,
+                            double* hi) {
+  if (pass == 0) {
+    *lo = 0.0;
+    *hi = rule == RULE_SOFT_L1 ? mx : 0.0;
+    return;
+  }
+  double l = lstate[2 * (pass - 1)], h = lstate[2 * (pass - 1) + 1];
+  if (rule == RULE_SOFT_L1) {
+    int node = 1;
+    for (int lev = 0; lev < 5; ++lev) {
+      const double mid = (l + h) / 2.0;
+      if (tot[node - 1] > par) { l = mid; node = 2 * node + 1; }
+      else { h = mid; node = 2 * node; }
+    }
+  } else {
+    const int shift = pass - 1 < 12 ? 58 - 5 * (pass - 1) : 0;
+    const int nv = pass - 1 < 12 ? 31 : 7;
+    unsigned long long pre = (unsigned long long)__double_as_longlong(l);
+    int best = 0;
+    for (int v = 1; v <= nv; ++v)
+      if (tot[v - 1] >= par) best = v;
+    pre |= (unsigned long long)best << shift;
+    l = __longlong_as_double((long long)pre);
+  }
+  *lo = l;
+  *hi = h;
+}
+
+// the 31 candidate levels of pass `pass` from the bracket (lo, hi)
+__device__ void als_candidates(int rule, int pass, double lo, double hi, double* cand) {
+  if (rule == RULE_SOFT_L1) {
+    double l[ALS_NC + 1], h[ALS_NC + 1];
+    l[1] = lo; h[1] = hi;
+    for (int node = 1; node <= ALS_NC; ++node) {
+      const double mid = (l[node] + h[node]) / 2.0;
+      cand[node - 1] = mid;
+      if (2 * node + 1 <= ALS_NC) {
+        l[2 * node] = l[node]; h[2 * node] = mid;          // |soft|_1 <= bound: hi = mid
+        l[2 * node + 1] = mid; h[2 * node + 1] = h[node];  // |soft|_1 >  bound: lo = mid
+      }
+    }
+  } else {
+    const int shift = pass < 12 ? 58 - 5 * pass : 0;
+    const int nv = pass < 12 ? 31 : 7;
+    const unsigned long long pre = (unsigned long long)__double_as_longlong(lo);
+    for (int v = 1; v <= ALS_NC; ++v)
+      cand[v - 1] = v <= nv ? __longlong_as_double((long long)(pre | ((unsigned long long)v << shift))) : INFINITY;
+  }
+}
+
+// one pass over raw against 31 levels: sum_f max(|raw_f| - level, 0) (soft at L1) or the count of |raw_f| >= level (top s)
+__global__ void __launch_bounds__(256) k_als_levels(const double* __restrict__ raw, int64_t p, int rule, double par, int pass,
+                                                   const double* __restrict__ fstat, int ng, double* __restrict__ lstate,
+                                                   double* __restrict__ lpart, const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  __shared__ double cand[ALS_NC];
+  __shared__ double tot[ALS_NC];
+  __shared__ double red[4][ALS_NC];
+  __shared__ double sh[4];
+  __shared__ int skip;
+  double l1, mx, ss;
+  als_fold_totals(fstat, ng, &l1, &mx, &ss, sh);
+  als_level_totals(lpart, pass, ng, tot);
+  if (threadIdx.x == 0) {
+    skip = (rule == RULE_SOFT_L1 && l1 <= par) ? 1 : 0;     // within the bound: no thresholding (:243-244)
+    if (!skip) {
+      double lo, hi;
+      als_bracket(rule, pass, par, mx, lstate, tot, &lo, &hi);
+      if (blockIdx.x == 0) {
+        lstate[2 * pass] = lo;
+        lstate[2 * pass + 1] = hi;
+      }
+      als_candidates(rule, pass, lo, hi, cand);
+    }
+  }
+  __syncthreads();
+  if (skip) return;
+  double lev[ALS_NC], acc[ALS_NC];
+#pragma unroll
+  for (int c = 0; c < ALS_NC; ++c) { lev[c] = cand[c]; acc[c] = 0.0; }
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    const double a = fabs(raw[f]);
+    if (rule == RULE_SOFT_L1) {
+#pragma unroll
+      for (int c = 0; c < ALS_NC; ++c) acc[c] += fmax(a - lev[c], 0.0);
+    } else {
+#pragma unroll
+      for (int c = 0; c < ALS_NC; ++c) acc[c] += a >= lev[c] ? 1.0 : 0.0;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < ALS_NC; ++c) {
+    const double s = als_wave_sum(acc[c]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < ALS_NC)
+    lpart[(size_t(pass & 1) * ALS_MAXG + blockIdx.x) * ALS_NC + threadIdx.x] =
+        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// the final level -- (lo + hi) / 2 after 50 halvings (:254), the s-th largest magnitude -- and the partial sums of squares of
+// the thresholded vector
+__global__ void __launch_bounds__(256) k_als_norm(const double* __restrict__ raw, int64_t p, int rule, double par, int passes,
+                                                 const double* __restrict__ fstat, int ng, const double* __restrict__ lstate,
+                                                 const double* __restrict__ lpart, double* __restrict__ thr,
+                                                 double* __restrict__ nstat, const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  __shared__ double sh[4];
+  __shared__ double tot[ALS_NC];
+  __shared__ double level;
+  __shared__ int skip;
+  double l1, mx, ss0;
+  als_fold_totals(fstat, ng, &l1, &mx, &ss0, sh);
+  als_level_totals(lpart, passes, ng, tot);
+  if (threadIdx.x == 0) {
+    skip = (rule == RULE_SOFT_L1 && l1 <= par) ? 1 : 0;
+    double lv = 0.0;
+    if (!skip) {
+      double lo, hi;
+      als_bracket(rule, passes, par, mx, lstate, tot, &lo, &hi);
+      lv = rule == RULE_SOFT_L1 ? (lo + hi) / 2.0 : lo;
+    }
+    level = lv;
+    if (blockIdx.x == 0) {
+      thr[0] = lv;
+      thr[1] = skip ? 0.0 : 1.0;
+    }
+  }
+  __syncthreads();
+  if (skip) return;
+  const double lv = level;
+  double ss = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    const double v = raw[f];
+    const double u = rule == RULE_SOFT_L1 ? als_soft(v, lv) : (fabs(v) >= lv ? v : 0.0);
+    ss += u * u;
+  }
+  ss = als_block_sum<4>(ss, sh);
+  if (threadIdx.x == 0) nstat[blockIdx.x] = ss;
+}
+
+// w = rule(raw), normalised when its norm exceeds 1e-12 (the unthresholded branch of soft at L1 divides unguarded, :244);
+// per-workgroup partial |w - w_old|^2
+__global__ void __launch_bounds__(256) k_als_apply(const double* __restrict__ raw, int64_t p, int rule, double par,
+                                                  const double* __restrict__ fstat, int ng, const double* __restrict__ thr,
+                                                  const double* __restrict__ nstat, double* __restrict__ w, double* __restrict__ dpart,
+                                                  const AlsStatus* st) {
+  if (als_stopped(st)) return;
+  __shared__ double sh[4];
+  double l1, mx, ss;
+  als_fold_totals(fstat, ng, &l1, &mx, &ss, sh);
+  const bool levels = rule == RULE_SOFT_L1 || rule == RULE_TOP_S;
+  const bool thresholded = levels && thr[1] != 0.0;
+  double lv = 0.0;
+  if (thresholded) {                     // uniform over the workgroup
+    lv = thr[0];
+    ss = als_block_sum<4>(int(threadIdx.x) < ng ? nstat[threadIdx.x] : 0.0, sh);
+  } else if (rule == RULE_SOFT_FIXED) {
+    lv = par;
+  }
+  const double nrm = sqrt(ss);
+  const bool divide = (rule == RULE_SOFT_L1 && !thresholded) || nrm > 1e-12;
+  double dd = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    const double v = raw[f];
+    double u = v;
+    if (rule == RULE_SOFT_FIXED || (rule == RULE_SOFT_L1 && thresholded)) u = als_soft(v, lv);
+    else if (rule == RULE_TOP_S && thresholded) u = fabs(v) >= lv ? v : 0.0;
+    if (divide) u /= nrm;
+    const double diff = u - w[f];
+    dd += diff * diff;
+    w[f] = u;
+  }
+  dd = als_block_sum<4>(dd, sh);
+  if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
+}
+
+// ---- column means as the reference forms them ----------------------------------------------------------------------------
+// NumPy's v.mean(axis=0) of a row-major array adds the rows in order in the array's own precision and divides by n
+// (cca_zoo/_base.py:97-99); one thread per column does exactly that, so the means of device rows equal the reference's bit for bit.
+template <typename T>
+__global__ void __launch_bounds__(256) k_als_colmeans(const T* __restrict__ X, int64_t ld, int64_t p, int64_t n, T* __restrict__ mean) {
+  const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (f >= p) return;
+  T acc = T(0);
+#pragma unroll 8
+  for (int64_t r = 0; r < n; ++r) acc = acc + X[r * ld + f];
+  mean[f] = acc / T(n);
+}
+
+// ---- host driver ----------------------------------------------------------------------------------------------------
+struct AlsState {
+  int dtype, M, rule, max_iter;
+  int64_t n, k, chunk;
+  double tol;
+  std::vector<int64_t> p;
+  std::vector<double> par;
+  AlsBuf B;
+  AlsStatus* st = nullptr;
+  AlsStatus* st_pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool ev_used[2] = {false, false};
+  int slot = 0;
+  bool has_init = false;
+  int last_cs[ALS_MAXV] = {};
+  std::vector<void*> allocs;
+};
+
+AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const* means) {
+  if (!views) fail(CCZ_EINVAL, "als: null views");
+  AlsViews vw;
+  memset(&vw, 0, sizeof(vw));
+  int64_t off = 0;
+  for (int i = 0; i < S.M; ++i) {
+    if (!views[i].data) fail(CCZ_EINVAL, "als: null view %d", i);
+    if (views[i].cols != S.p[i])
+      fail(CCZ_EINVAL, "als: view %d has %lld columns, the fit state %lld", i, (long long)views[i].cols, (long long)S.p[i]);
+    if (views[i].ld < views[i].cols) fail(CCZ_EINVAL, "als: view %d: ld < cols", i);
+    vw.X[i] = views[i].data;
+    vw.mu[i] = means ? means[i] : nullptr;
+    vw.ld[i] = views[i].ld;
+    vw.p[i] = S.p[i];
+    vw.off[i] = off;
+    off += S.p[i];
+    // enough score workgroups to fill the device when there are few rows; every split at least 4096 columns wide
+    const int64_t rowgroups = (S.n + ALS_SROWS - 1) / ALS_SROWS;
+    int64_t cs = std::min<int64_t>((2048 + rowgroups - 1) / rowgroups, std::max<int64_t>(1, S.p[i] / 4096));
+    vw.cs[i] = int(std::max<int64_t>(1, std::min<int64_t>(cs, S.B.csmax)));
+    vw.ng[i] = int(std::max<int64_t>(1, std::min<int64_t>(ALS_MAXG, (S.p[i] + 2047) / 2048)));
+    vw.par[i] = S.par[i];
+    vw.rule[i] = (S.rule == RULE_TOP_S && S.par[i] >= double(S.p[i])) ? int(RULE_NORMALISE) : S.rule;
+  }
+  return vw;
+}
+
+template <typename T>
+void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
+  const dim3 grid(unsigned((S.n + ALS_SROWS - 1) / ALS_SROWS), unsigned(vw.cs[i]));
+  hipLaunchKernelGGL((k_als_score<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
+                     vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.st);
+  CCZ_LAUNCH_CHECK();
+}
+
+template <typename T>
+void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const dim3 grid(unsigned((vw.p[i] + ALS_STRIP - 1) / ALS_STRIP), unsigned(S.B.nchunk));
+  hipLaunchKernelGGL((k_als_xt<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
+                     vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.st);
+  CCZ_LAUNCH_CHECK();
+}
+
+// fold .. apply of view i (the rule's passes over raw: 2, or 13 for soft at L1, 16 for top s)
+void launch_rule(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const AlsBuf& B = S.B;
+  const int rule = vw.rule[i], ng = vw.ng[i];
+  const int64_t p = vw.p[i];
+  double* raw = B.raw + vw.off[i];
+  double* fstat = B.fstat + size_t(i) * ALS_MAXG * 3;
+  hipLaunchKernelGGL(k_als_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, B.nchunk, p, raw, rule, vw.par[i], fstat, S.st);
+  CCZ_LAUNCH_CHECK();
+  if (rule == RULE_SOFT_L1 || rule == RULE_TOP_S) {
+    const int passes = rule == RULE_SOFT_L1 ? ALS_PMD_PASSES : ALS_SPAN_PASSES;
+    for (int q = 0; q < passes; ++q) {
+      hipLaunchKernelGGL(k_als_levels, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], q, fstat, ng, B.lstate, B.lpart, S.st);
+      CCZ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_als_norm, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], passes, fstat, ng, B.lstate, B.lpart,
+                       B.thr + 2 * i, B.nstat, S.st);
+    CCZ_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_als_apply, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], fstat, ng, B.thr + 2 * i, B.nstat, B.w + vw.off[i],
+                     B.dpart + size_t(i) * ALS_MAXG, S.st);
+  CCZ_LAUNCH_CHECK();
+}
+
+void launch_prologue(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  hipLaunchKernelGGL(k_als_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, i, S.st);
+  CCZ_LAUNCH_CHECK();
+}
+
+void score_any(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
+  if (S.dtype == CCZ_F32) launch_score<float>(c, S, vw, i, first_only);
+  else launch_score<double>(c, S, vw, i, first_only);
+}
+
+void xt_any(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  if (S.dtype == CCZ_F32) launch_xt<float>(c, S, vw, i);
+  else launch_xt<double>(c, S, vw, i);
+}
+
+void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
+  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 1);
+  for (int i = 0; i < S.M; ++i) {
+    launch_prologue(c, S, vw, i);
+    xt_any(c, S, vw, i);
+    launch_rule(c, S, vw, i);
+    score_any(c, S, vw, i, 0);
+  }
+  hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, S.tol, S.max_iter, S.st);
+  CCZ_LAUNCH_CHECK();
+  const int ga = int(std::max<int64_t>(1, std::min<int64_t>(256, (S.B.ptot + 2047) / 2048)));
+  hipLaunchKernelGGL(k_als_advance, dim3(ga), dim3(256), 0, stream(c), S.B, S.st);
+  CCZ_LAUNCH_CHECK();
+}
+
+void als_free(ccz_ctx* c, AlsState* S) {
+  sync(c);
+  for (void* a : S->allocs) dev_free(c, a);
+  for (int i = 0; i < 2; ++i) {
+    if (S->st_pin[i]) (void)hipHostFree(S->st_pin[i]);
+    if (S->ev[i]) (void)hipEventDestroy(S->ev[i]);
+  }
+  delete S;
+}
+
+AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, int64_t k, int rule, const double* par, double tol,
+                     int64_t max_iter, int64_t chunk) {
+  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "als: dtype must be CCZ_F32 or CCZ_F64");
+  if (M < 1 || M > ALS_MAXV) fail(CCZ_EUNSUP, "als: 1 to %d views are supported, got %d", ALS_MAXV, M);
+  if (k < 1 || k > ALS_MAXK) fail(CCZ_EUNSUP, "als: 1 to %d latent dimensions are supported, got %lld", ALS_MAXK, (long long)k);
+  if (!p || n < 1 || n > (int64_t(1) << 30) || max_iter < 1 || max_iter > (int64_t(1) << 30) || chunk < 1 || !(tol >= 0.0))
+    fail(CCZ_EINVAL, "als: bad argument");
+  if (rule < RULE_NORMALISE || rule > RULE_TOP_S) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
+  if (rule != RULE_NORMALISE && !par) fail(CCZ_EINVAL, "als: the rule needs one parameter per view");
+  AlsState* S = new AlsState();
+  S->dtype = dtype; S->M = M; S->rule = rule; S->max_iter = int(max_iter);
+  S->n = n; S->k = k; S->chunk = chunk; S->tol = tol;
+  AlsBuf& B = S->B;
+  memset(&B, 0, sizeof(B));
+  B.n = int(n); B.M = M; B.k = int(k);
+  for (int i = 0; i < M; ++i) {
+    if (p[i] < 1) { delete S; fail(CCZ_EINVAL, "als: view %d has no columns", i); }
+    const double q = par ? par[i] : 0.0;
+    if (rule == RULE_TOP_S && !(q >= 1.0)) { delete S; fail(CCZ_EINVAL, "als: top-s needs s >= 1 (view %d)", i); }
+    if (rule != RULE_NORMALISE && !(q == q)) { delete S; fail(CCZ_EINVAL, "als: the parameter of view %d is NaN", i); }
+    S->p.push_back(p[i]);
+    S->par.push_back(q);
+    B.ptot += p[i];
+    B.pmax = std::max(B.pmax, p[i]);
+  }
+  B.csmax = 16;
+  B.nchunk = int(std::min<int64_t>(64, (n + 63) / 64));
+  B.rc = int((n + B.nchunk - 1) / B.nchunk);
+  B.nchunk = int((n + B.rc - 1) / B.rc);
+  try {
+    auto get = [&](size_t doubles) {
+      void* a = dev_alloc(c, std::max<size_t>(doubles, 1) * 8);
+      S->allocs.push_back(a);
+      return static_cast<double*>(a);
+    };
+    B.w = get(size_t(B.ptot));
+    B.raw = get(size_t(B.ptot));
+    B.init = get(size_t(B.ptot) * k);
+    B.Wout = get(size_t(B.ptot) * k);
+    B.spart = get(size_t(M) * B.csmax * n);
+    B.Q = get(size_t(M) * k * n);
+    B.tt = get(size_t(n));
+    B.xpart = get(size_t(B.nchunk) * B.pmax);
+    B.fstat = get(size_t(M) * ALS_MAXG * 3);
+    B.lpart = get(size_t(2) * ALS_MAXG * ALS_NC);
+    B.lstate = get(size_t(2) * (ALS_SPAN_PASSES + 1));
+    B.nstat = get(ALS_MAXG);
+    B.thr = get(size_t(M) * 2);
+    B.dpart = get(size_t(M) * ALS_MAXG);
+    S->st = static_cast<AlsStatus*>(dev_alloc(c, sizeof(AlsStatus)));
+    S->allocs.push_back(S->st);
+    for (int i = 0; i < 2; ++i) {
+      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S->st_pin[i]), sizeof(AlsStatus), hipHostMallocDefault));
+      CCZ_HIP(hipEventCreateWithFlags(&S->ev[i], hipEventDisableTiming));
+    }
+  } catch (...) {
+    als_free(c, S);
+    throw;
+  }
+  return S;
+}
+
+AlsState* as_als(void* st) {
+  if (!st) fail(CCZ_EINVAL, "als: null fit state");
+  return static_cast<AlsState*>(st);
+}
+
+void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
+  if (!w0) fail(CCZ_EINVAL, "als: null initial vectors");
+  const AlsBuf& B = S.B;
+  h2d(c, B.init, w0, size_t(B.ptot) * S.k * 8);
+  h2d(c, B.w, w0, size_t(B.ptot) * 8);
+  zero(c, B.Wout, size_t(B.ptot) * S.k * 8);
+  zero(c, B.Q, size_t(S.M) * S.k * S.n * 8);
+  zero(c, B.thr, size_t(S.M) * 16);
+  AlsStatus st0;
+  memset(&st0, 0, sizeof(st0));
+  h2d(c, S.st, &st0, sizeof(st0));
+  S.has_init = true;
+}
+
+}  // namespace
+}  // namespace ccz
+
+extern "C" {
+
+int ccz_als_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t n_rows, int64_t k, int rule,
+                   const double* rule_param, double tol, int64_t max_iter, int64_t chunk_sweeps, void** state_out) {
+  CCZ_GUARD(h, {
+    if (!state_out) ccz::fail(CCZ_EINVAL, "null argument");
+    *state_out = nullptr;
+    *state_out = ccz::als_create(h, dtype, n_views, p, n_rows, k, rule, rule_param, tol, max_iter, chunk_sweeps);
+  })
+}
+
+int ccz_als_destroy(ccz_handle h, void* state) {
+  CCZ_GUARD(h, {
+    if (state) ccz::als_free(h, static_cast<ccz::AlsState*>(state));
+  })
+}
+
+int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::sync(h);   // the pinned status slots may still be in use by an earlier fit on this state
+    S.ev_used[0] = S.ev_used[1] = false;
+    ccz::als_set_init(h, S, w0_host);
+  })
+}
+
+int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_sweeps,
+                   int64_t* sweeps_known, int* stopped_known) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_als(state);
+    if (!S.has_init) ccz::fail(CCZ_EINVAL, "als: ccz_als_set_init has not been called");
+    if (n_sweeps < 0 || n_sweeps > S.chunk) ccz::fail(CCZ_EINVAL, "als: n_sweeps must be 0..%lld", (long long)S.chunk);
+    const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
+    for (int i = 0; i < S.M; ++i) S.last_cs[i] = vw.cs[i];
+    const int slot = S.slot;
+    if (S.ev_used[slot]) {
+      CCZ_HIP(hipEventSynchronize(S.ev[slot]));
+      if (sweeps_known) *sweeps_known = S.st_pin[slot]->total;
+      if (stopped_known) *stopped_known = S.st_pin[slot]->stopped;
+    } else {
+      if (sweeps_known) *sweeps_known = -1;
+      if (stopped_known) *stopped_known = 0;
+    }
+    for (int64_t t = 0; t < n_sweeps; ++t) ccz::enqueue_sweep(h, S, vw);
+    CCZ_HIP(hipMemcpyAsync(S.st_pin[slot], S.st, sizeof(ccz::AlsStatus), hipMemcpyDeviceToHost, ccz::stream(h)));
+    CCZ_HIP(hipEventRecord(S.ev[slot], ccz::stream(h)));
+    S.ev_used[slot] = true;
+    S.slot ^= 1;
+  })
+}
+
+int ccz_als_status(ccz_handle h, void* state, int* dims_done, int* stopped, int64_t* sweeps_per_dim, double* last_delta) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsStatus st;
+    ccz::d2h(h, &st, S.st, sizeof(st));
+    if (dims_done) *dims_done = st.dim;
+    if (stopped) *stopped = st.stopped;
+    for (int64_t d = 0; d < S.k; ++d) {
+      if (sweeps_per_dim) sweeps_per_dim[d] = st.iters[d];
+      if (last_delta) last_delta[d] = st.last_delta[d];
+    }
+  })
+}
+
+int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, void* mean_dev) {
+  CCZ_GUARD(h, {
+    if (!view || !view->data || !mean_dev || n_rows < 1 || view->cols < 1 || view->ld < view->cols) ccz::fail(CCZ_EINVAL, "als: bad argument");
+    if (dtype != CCZ_F32 && dtype != CCZ_F64) ccz::fail(CCZ_EUNSUP, "als: dtype must be CCZ_F32 or CCZ_F64");
+    const dim3 grid(unsigned((view->cols + 255) / 256));
+    if (dtype == CCZ_F32)
+      hipLaunchKernelGGL((ccz::k_als_colmeans<float>), grid, dim3(256), 0, ccz::stream(h), static_cast<const float*>(view->data), view->ld,
+                         view->cols, n_rows, static_cast<float*>(mean_dev));
+    else
+      hipLaunchKernelGGL((ccz::k_als_colmeans<double>), grid, dim3(256), 0, ccz::stream(h), static_cast<const double*>(view->data), view->ld,
+                         view->cols, n_rows, static_cast<double*>(mean_dev));
+    CCZ_LAUNCH_CHECK();
+  })
+}
+
+int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_als(state);
+    const ccz::AlsBuf& B = S.B;
+    if (!out_host || view < 0 || view >= S.M) ccz::fail(CCZ_EINVAL, "als: bad argument");
+    int64_t off = 0;
+    for (int i = 0; i < view; ++i) off += S.p[i];
+    const int64_t n = S.n, p = S.p[view];
+    switch (what) {
+      case CCZ_ALS_PEEK_W: ccz::d2h(h, out_host, B.w + off, size_t(p) * 8); break;
+      case CCZ_ALS_PEEK_RAW: ccz::d2h(h, out_host, B.raw + off, size_t(p) * 8); break;
+      case CCZ_ALS_PEEK_TARGET: ccz::d2h(h, out_host, B.tt, size_t(n) * 8); break;
+      case CCZ_ALS_PEEK_Q: ccz::d2h(h, out_host, B.Q + int64_t(view) * S.k * n, size_t(S.k) * n * 8); break;
+      case CCZ_ALS_PEEK_LEVEL: ccz::d2h(h, out_host, B.thr + 2 * view, 16); break;
+      case CCZ_ALS_PEEK_SCORE: {
+        // the column-split partial sums, added in split order as the device adds them; the split count is that of the
+        // last ccz_als_sweeps call
+        std::vector<double> part(size_t(B.csmax) * n);
+        ccz::d2h(h, part.data(), B.spart + int64_t(view) * B.csmax * n, part.size() * 8);
+        const int cs = S.last_cs[view] > 0 ? S.last_cs[view] : 1;
+        for (int64_t r = 0; r < n; ++r) {
+          double v = 0.0;
+          for (int c = 0; c < cs; ++c) v += part[size_t(c) * n + r];
+          out_host[r] = v;
+        }
+        break;
+      }
+      default: ccz::fail(CCZ_EINVAL, "als: unknown buffer %d", what);
+    }
+  })
+}
+
+int ccz_als_get_weights(ccz_handle h, void* state, double* W_host) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_als(state);
+    if (!W_host) ccz::fail(CCZ_EINVAL, "null argument");
+    ccz::d2h(h, W_host, S.B.Wout, size_t(S.B.ptot) * S.k * 8);
+  })
+}
+
+}  // extern "C"

@@ -1,0 +1,336 @@
+"""ALS models with deflation, run on the device: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span.
+
+Reference: ``cca_zoo/linear/_iterative.py:38-158`` (the loop and the target score), ``:166-223`` (PLS_ALS),
+``:231-380`` (SCCA_PMD and its bisection), ``:631-722`` (SCCA_Span), ``:839-930`` (ParkhomenkoCCA) and
+``cca_zoo/_utils/_linalg.py:76-116`` (soft threshold, deflation).  The four models share one sweep: for every view,
+``t = normalise(sum_{j != i} X_j w_j)``, ``raw = X_i' t``, then the model's rule turns ``raw`` into ``w_i``.  Every sweep
+runs in libccz (``csrc/als.hip``); the host draws the initial vectors of all dimensions up front (they do not depend on
+results), uploads them and enqueues sweeps in chunks behind a device stop word.
+
+The views are never copied or rewritten.  After ``d`` dimensions the reference's deflated view is
+``(I - Q_i Q_i') (X_i - mu_i)`` with ``Q_i`` the normalised scores, so the device reads the original rows in their own
+precision and corrects the two n-vectors of an update instead (DESIGN.md "ALS models").
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from numbers import Integral, Real
+from typing import Any, ClassVar
+
+import numpy as np
+from sklearn.utils._param_validation import Interval
+
+from cca_zoo_amd._base import BaseModel
+from cca_zoo_amd._utils._validation import is_device_tensor, perview_parameter, validate_views
+
+#: sweeps per ``ccz_als_sweeps`` call: one host wait (for the chunk two calls back) per chunk
+CHUNK_SWEEPS = 8
+#: limits of the device path (``csrc/als.hip``)
+MAX_DIMS, MAX_VIEWS = 32, 8
+#: rule codes of ``ccz_als_create`` (``include/ccz.h``)
+RULE_NORMALISE, RULE_SOFT_FIXED, RULE_SOFT_L1, RULE_TOP_S = 0, 1, 2, 3
+
+
+def initial_vectors(random_state, p, k):
+    """The reference's initial vectors of all ``k`` dimensions, (k, sum p): one ``default_rng(random_state)``; per
+    dimension and view one ``standard_normal(p_i)``, normalised (``_iterative.py:80-89``)."""
+    rng = np.random.default_rng(random_state)
+    out = np.empty((k, sum(p)))
+    for d in range(k):
+        off = 0
+        for pi in p:
+            w = rng.standard_normal(pi)
+            out[d, off:off + pi] = w / np.linalg.norm(w)
+            off += pi
+    return out
+
+
+class _BaseIterative(BaseModel):
+    """Alternating updates with deflation on the device (see module docstring).
+
+    Differences from the reference, on purpose:
+
+    - ``fit`` inside :func:`cca_zoo_amd.row_sharded` raises ``NotImplementedError``.
+    - At most 32 latent dimensions and 8 views.
+    - The views are never copied: the reference rewrites a float64 copy of every view once per dimension; here the
+      rows are read where they lie (float32 views as float32) and device tensors are left bit-unchanged.
+
+    As in the reference, everything after centring is float64 for float32 views too: ``weights_`` are float64,
+    ``means_`` keep the input dtype.
+
+    ``n_iter_`` (not in the reference) lists the sweeps taken per latent dimension; ``last_delta_`` the largest weight
+    change of each dimension's last sweep.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **BaseModel._parameter_constraints,
+        "max_iter": [Interval(Integral, 1, None, closed="left")],
+        "tol": [Interval(Real, 0, None, closed="left")],
+        "random_state": [Integral, None],
+    }
+    _rule = RULE_NORMALISE
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center)
+        self.max_iter = max_iter
+        self.tol = tol
+        self.random_state = random_state
+
+    def _rule_parameters(self, p) -> list[float]:
+        """One number per view for the rule (``ccz_als_create``'s ``rule_param``)."""
+        return [0.0] * len(p)
+
+    def fit(self, views, y=None):
+        from cca_zoo_amd import _backend, _dist
+
+        if _dist.is_sharded():
+            raise NotImplementedError(
+                f"{type(self).__name__} alternates over whole feature vectors, which this build does not shard by rows: "
+                "fit it outside row_sharded()"
+            )
+        self._validate_params()
+        validated = validate_views(views, check_finite=False)
+        dev = [is_device_tensor(v) for v in validated]
+        if any(dev) and not all(dev):
+            raise ValueError("views must be all host arrays or all CUDA tensors")
+        validated = [v if d or v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+                     for v, d in zip(validated, dev)]
+        m = len(validated)
+        n = int(validated[0].shape[0])
+        p = [int(v.shape[1]) for v in validated]
+        k = int(self.latent_dimensions)
+        if k > MAX_DIMS:
+            raise ValueError(f"latent_dimensions={k}: the device path supports at most {MAX_DIMS}")
+        if m > MAX_VIEWS:
+            raise ValueError(f"{m} views: the device path supports at most {MAX_VIEWS} views")
+        if n < 1:
+            raise ValueError("at least 1 sample is required")
+        self.n_views_, self.n_features_in_, self.n_samples_ = m, p, n
+        par = self._rule_parameters(p)
+        f32 = all((v.element_size() == 4) if d else (v.dtype == np.float32) for v, d in zip(validated, dev))
+        code = _backend.F32 if f32 else _backend.F64
+        h = _backend.handle_for(validated)
+
+        # dtype, contiguity and the means (the reference's _setup_fit: v.mean(axis=0) in the input dtype), in HBM
+        if all(dev):
+            import torch
+
+            tdt = torch.float32 if f32 else torch.float64
+            xs = [v.to(tdt) for v in validated]
+            xs = [x if (x.stride(1) == 1 and x.stride(0) >= x.shape[1]) else x.contiguous() for x in xs]
+            # the means are formed on the device in NumPy's own order of summation (ccz_als_colmeans, below): torch's
+            # tree-ordered float32 mean differs from v.mean(axis=0) in the last bits, and with it the whole trajectory
+            mus = [torch.empty(pi, dtype=tdt, device=x.device) for x, pi in zip(xs, p)] if self.center else None
+            ptrs = [(int(x.data_ptr()), int(x.stride(0))) for x in xs]
+            mptrs = [int(mu.data_ptr()) for mu in mus] if mus is not None else None
+            means_host = [np.zeros(pi) for pi in p]
+            keep = [xs, mus]
+        else:
+            ndt = np.float32 if f32 else np.float64
+            xs = [np.ascontiguousarray(v, dtype=ndt) for v in validated]
+            if not all(np.all(np.isfinite(x)) for x in xs):
+                raise ValueError("Input contains NaN or infinity.")
+            means_host = [x.mean(axis=0) for x in xs] if self.center else [np.zeros(pi) for pi in p]
+            bufs = [h.to_device(x) for x in xs]
+            mbufs = [h.to_device(np.ascontiguousarray(mu, dtype=ndt)) for mu in means_host] if self.center else None
+            ptrs = [(int(b.ptr), pi) for b, pi in zip(bufs, p)]
+            mptrs = [int(b.ptr) for b in mbufs] if mbufs is not None else None
+            keep = [bufs, mbufs]
+        varr = (_backend.View * m)()
+        for i, ((ptr, ld), pi) in enumerate(zip(ptrs, p)):
+            varr[i].data, varr[i].cols, varr[i].ld = ptr, pi, ld
+        marr = (C.c_void_p * m)(*mptrs) if mptrs is not None else None
+
+        total = k * int(self.max_iter)
+        chunk = max(1, min(CHUNK_SWEEPS, total))
+        state = C.c_void_p()
+        sp = None
+        if all(dev):
+            import torch
+
+            sp = int(torch.cuda.current_stream(validated[0].device).cuda_stream)
+            h.acquire(sp)
+        try:
+            if sp is not None and mptrs is not None:
+                for i in range(m):
+                    h.check(h.lib.ccz_als_colmeans(h.raw, code, C.byref(varr[i]), n, C.c_void_p(mptrs[i])))
+            h.check(h.lib.ccz_als_create(h.raw, code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
+                                         (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter),
+                                         chunk, C.byref(state)))
+            w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
+            h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
+            done = 0
+            known, stopped = C.c_int64(-1), C.c_int(0)
+            while done < total and not stopped.value:
+                s = min(chunk, total - done)
+                h.check(h.lib.ccz_als_sweeps(h.raw, state, varr, marr, s, C.byref(known), C.byref(stopped)))
+                done += s
+            dims, stop = C.c_int(0), C.c_int(0)
+            iters = (C.c_int64 * k)()
+            deltas = (C.c_double * k)()
+            h.check(h.lib.ccz_als_status(h.raw, state, C.byref(dims), C.byref(stop), iters, deltas))
+            if not stop.value or dims.value != k:
+                raise RuntimeError(f"ALS fit ended after {dims.value} of {k} dimensions")   # cannot happen: k * max_iter sweeps
+            wflat = np.empty(sum(p) * k)
+            h.check(h.lib.ccz_als_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
+        finally:
+            if state:
+                h.lib.ccz_als_destroy(h.raw, state)
+            if sp is not None:
+                h.release(sp)
+        if all(dev) and self.center:
+            means_host = [mu.cpu().numpy() for mu in keep[1]]
+        del keep
+        self.n_iter_ = [int(x) for x in iters]
+        self.last_delta_ = [float(x) for x in deltas]
+        weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
+        self._store(weights, means_host, "f32" if f32 else "f64", weights_like_input=False)
+        return self
+
+
+class PLS_ALS(_BaseIterative):
+    r"""Alternating power iteration for PLS (multiset NIPALS), every sweep on the device.
+
+    $w_i \leftarrow X_i^\top \bar s_{\neg i} / \|X_i^\top \bar s_{\neg i}\|_2$ with $\bar s_{\neg i}$ the normalised
+    sum of the other views' scores (reference: ``cca_zoo/linear/_iterative.py:166-223``).
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance on the largest weight change of a sweep. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+
+class SCCA_PMD(_BaseIterative):
+    r"""Sparse CCA by penalised matrix decomposition (Witten 2009), every sweep on the device.
+
+    Each update soft-thresholds $X_i^\top \bar s_{\neg i}$ at the level that 50 halvings of $[0, \max|raw|]$ end on
+    for the L1 bound $\tau_i \sqrt{p_i}$ (reference: ``cca_zoo/linear/_iterative.py:231-380``).  As in the reference
+    the bound is compared with the L1 norm of the *unnormalised* ``raw``: on data of ordinary scale ``raw`` is far
+    larger than the bound and the columns come out very sparse (often one or two entries); scale the inputs down for
+    denser supports.  When ``||raw||_1`` is within the bound the update is ``raw / ||raw||_2``.
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        tau: L1 bound factor(s); the bound of view ``i`` is ``tau_i * sqrt(p_i)``. Default is 1.
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **_BaseIterative._parameter_constraints,
+        "tau": [Real, list],
+    }
+    _rule = RULE_SOFT_L1
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        tau: float | list[float] = 1.0,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.tau = tau
+
+    def _rule_parameters(self, p):
+        tau = perview_parameter("tau", self.tau, 1.0, len(p))
+        return [float(t * np.sqrt(pi)) for t, pi in zip(tau, p)]
+
+
+class ParkhomenkoCCA(_BaseIterative):
+    r"""Sparse CCA by soft-thresholded power iteration (Parkhomenko 2009), every sweep on the device.
+
+    $w_i \leftarrow S_{\tau_i}(X_i^\top \bar s_{\neg i})$, normalised when its norm exceeds 1e-12 (reference:
+    ``cca_zoo/linear/_iterative.py:839-930``).
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        tau: Soft-threshold level(s). Default is 0.1.
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **_BaseIterative._parameter_constraints,
+        "tau": [Real, list],
+    }
+    _rule = RULE_SOFT_FIXED
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        tau: float | list[float] = 0.1,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.tau = tau
+
+    def _rule_parameters(self, p):
+        return [float(t) for t in perview_parameter("tau", self.tau, 0.1, len(p))]
+
+
+class SCCA_Span(_BaseIterative):
+    r"""SpanCCA: truncated power iteration keeping the ``span`` largest entries per view, every sweep on the device.
+
+    Entries with $|raw| \ge$ the s-th largest magnitude are kept (ties at that magnitude are all kept), then the
+    vector is normalised (reference: ``cca_zoo/linear/_iterative.py:631-722``).  As in the reference the default of
+    ``span`` is the width of the *first* view, for every view.
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        span: Entries to keep per view (int or list). ``None`` keeps the width of the first view; 0 keeps every entry,
+            as in the reference. A negative ``span`` raises (the reference indexes the sorted magnitudes from the small
+            end with it).
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **_BaseIterative._parameter_constraints,
+        "span": [Integral, list, None],
+    }
+    _rule = RULE_TOP_S
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        span: int | list[int] | None = None,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.span = span
+
+    def _rule_parameters(self, p):
+        span = perview_parameter("span", p[0] if self.span is None else self.span, p[0], len(p))
+        if any(int(s) < 0 for s in span):
+            raise ValueError("span must not be negative")
+        # span = 0 keeps every entry, as the reference's ``np.sort(np.abs(raw))[-0]`` (the smallest magnitude) does
+        return [float(int(s)) if int(s) > 0 else float(pi) for s, pi in zip(span, p)]

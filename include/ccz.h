@@ -463,6 +463,70 @@ CCZ_API int ccz_ey_status(ccz_handle h, void* state, int64_t* steps_done, int* s
 /* Copy the current weights (W blocks, float64) to the host.  Synchronises. */
 CCZ_API int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host);
 
+/* ---- ALS models with deflation: PLS_ALS / SCCA_PMD / ParkhomenkoCCA / SCCA_Span (csrc/als.hip) -------------------------
+ * Whole Gauss-Seidel sweeps on the device, no host wait inside a chunk of sweeps.  For every view i of a sweep:
+ * t = normalise(sum_{j != i} X_j w_j), raw = X_i' t, w_i = rule(raw); after the sweep delta = max_i |w_i - w_i_old|_2 and
+ * the dimension ends when delta < tol or after max_iter sweeps.  The views are never copied or written: the deflated view
+ * of dimension d is (I - Q_i Q_i') (X_i - mu_i) with Q_i the normalised scores of the earlier dimensions, applied to the
+ * n-vectors of an update (DESIGN.md "ALS models").  Views are ccz_view's of DEVICE rows (all CCZ_F32 or all CCZ_F64);
+ * means_dev as for ccz_ey_steps.  x - mu is rounded in the views' precision, everything after it is float64.
+ * Rules: CCZ_ALS_NORMALISE raw / |raw|_2; CCZ_ALS_SOFT_FIXED soft(raw, rule_param[i]); CCZ_ALS_SOFT_L1 raw / |raw|_2 when
+ * |raw|_1 <= rule_param[i], else soft(raw, level) at the level 50 halvings of [0, max |raw|] end on; CCZ_ALS_TOP_S entries
+ * with |raw| >= the rule_param[i]-th largest magnitude (ties kept).  Results are normalised when their norm exceeds 1e-12.
+ * cca_zoo/linear/_iterative.py:38-158, :166-223, :231-380, :631-722, :839-930, cca_zoo/_utils/_linalg.py:76-116 */
+#define CCZ_ALS_NORMALISE 0
+#define CCZ_ALS_SOFT_FIXED 1
+#define CCZ_ALS_SOFT_L1 2
+#define CCZ_ALS_TOP_S 3
+
+/* Create a fit state: n_views (1..8) views of widths p[i] and n_rows rows, k (1..32) latent dimensions, the rule and its
+ * per-view parameter (NULL for CCZ_ALS_NORMALISE), tol and max_iter per dimension as in the reference
+ * (cca_zoo/linear/_iterative.py:52-63), up to chunk_sweeps sweeps per ccz_als_sweeps call. */
+CCZ_API int ccz_als_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t n_rows, int64_t k, int rule,
+                           const double* rule_param, double tol, int64_t max_iter, int64_t chunk_sweeps, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op. */
+CCZ_API int ccz_als_destroy(ccz_handle h, void* state);
+
+/* Upload the initial vectors of all dimensions (host, float64, k x sum p: dimension d's vectors of all views back to
+ * back) and reset the fit (cca_zoo/linear/_iterative.py:80-89: the draws do not depend on results). */
+CCZ_API int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host);
+
+/* Enqueue n_sweeps (<= chunk_sweeps) sweeps (cca_zoo/linear/_iterative.py:86-117).  Returns without waiting for the
+ * device; the only host wait is for the chunk that used the same status slot two calls earlier, whose state is returned
+ * in sweeps_known / stopped_known (-1 / 0 when there is none yet).  Sweeps after the last dimension are no-ops. */
+CCZ_API int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_sweeps,
+                           int64_t* sweeps_known, int* stopped_known);
+
+/* Dimensions finished, whether the fit is complete, and per dimension (k entries each) the sweeps taken and the delta
+ * of the last sweep.  Synchronises. */
+CCZ_API int ccz_als_status(ccz_handle h, void* state, int* dims_done, int* stopped, int64_t* sweeps_per_dim,
+                           double* last_delta);
+
+/* mean_dev (device, the view's dtype, cols entries) = the column means of one view of DEVICE rows exactly as NumPy's
+ * v.mean(axis=0) forms them: the rows added in order in the view's own precision, then divided by n_rows
+ * (cca_zoo/_base.py:97-99).  A tree-ordered float32 mean differs from it by up to ~1e-6 relative, which would move the
+ * centred rows and with them the trajectory.  Asynchronous on the handle's stream. */
+CCZ_API int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, void* mean_dev);
+
+/* Copy one working buffer of view `view` to the host (float64) -- what the kernel tests compare with NumPy one kernel at
+ * a time: the current vector w_i (p_i), raw_i = X_d' t of its last update (p_i), its uncorrected score (X_i - mu_i) w_i
+ * (n_rows), the corrected target t~ of the LAST update of any view (n_rows), Q_i (k x n_rows, column a at a n_rows:
+ * the normalised scores of the finished dimensions, cca_zoo/_utils/_linalg.py:108-116), the level of its last update (2:
+ * the level the bisection of cca_zoo/linear/_iterative.py:245-254 ended on or the s-th largest magnitude of :717, then
+ * 1.0 when that level was applied and 0.0 when the rule has no level or |raw|_1 was within the bound).  Synchronises. */
+#define CCZ_ALS_PEEK_W 0
+#define CCZ_ALS_PEEK_RAW 1
+#define CCZ_ALS_PEEK_SCORE 2
+#define CCZ_ALS_PEEK_TARGET 3
+#define CCZ_ALS_PEEK_Q 4
+#define CCZ_ALS_PEEK_LEVEL 5
+CCZ_API int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host);
+
+/* Copy the finished columns (W blocks as in ccz_ey_get_weights: view i's p_i x k row-major float64 weights, views back
+ * to back; unfinished columns are zero) to the host (cca_zoo/linear/_iterative.py:91-92).  Synchronises. */
+CCZ_API int ccz_als_get_weights(ccz_handle h, void* state, double* W_host);
+
 #ifdef __cplusplus
 }
 #endif
