@@ -34,6 +34,8 @@
 
 #include "hip_common.h"
 #include "abi_guard.h"
+#include "fit_driver.h"
+#include "row_load.h"
 
 namespace ccz {
 
@@ -92,35 +94,6 @@ struct AlsBuf {
   int64_t ptot, pmax;
 };
 
-__device__ __forceinline__ bool als_stopped(const AlsStatus* st) { return st->stopped != 0; }
-
-template <typename T>
-__device__ __forceinline__ bool als_vec_ok(const T* X, int64_t ld, const T* mu) {
-  constexpr int64_t V = 16 / sizeof(T);
-  return (reinterpret_cast<uintptr_t>(X) % 16 == 0) && (ld % V == 0) && (!mu || reinterpret_cast<uintptr_t>(mu) % 16 == 0);
-}
-
-// v[q] = p4[q], q < 4, by 16-byte loads (p4 16-byte aligned)
-__device__ __forceinline__ void als_ld4(const float* p4, float* v) {
-  const float4 a = *reinterpret_cast<const float4*>(p4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-}
-__device__ __forceinline__ void als_ld4(const double* p4, double* v) {
-  const double2 a = *reinterpret_cast<const double2*>(p4), b = *reinterpret_cast<const double2*>(p4 + 2);
-  v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
-
-// four consecutive entries starting at f0 (zero beyond p); whole-line loads when `vec` and the four lie inside p
-template <typename T>
-__device__ __forceinline__ void als_load4(const T* base, int64_t f0, int64_t p, bool vec, T* v) {
-  if (vec && f0 + 3 < p) {
-    als_ld4(base + f0, v);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = f0 + q < p ? base[f0 + q] : T(0);
-  }
-}
-
 // deterministic sums / maxima over a wave and over a workgroup of NW waves (every thread gets the result)
 __device__ __forceinline__ double als_wave_sum(double v) {
 #pragma unroll
@@ -167,7 +140,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
                                                   const double* __restrict__ w, double* __restrict__ spart, int first_only,
                                                   const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   if (first_only && st->sweep != 0) return;
   __shared__ double sh[4];
   const int r0 = blockIdx.x * ALS_SROWS;
@@ -175,7 +148,7 @@ __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, cons
   // column range of this split, in units of 4 columns so that every split starts on a whole line
   const int64_t units = (p + 3) / 4, per = (units + cs - 1) / cs;
   const int64_t c0 = 4 * per * blockIdx.y, c1 = c0 + 4 * per < p ? c0 + 4 * per : p;
-  const bool vec = als_vec_ok(X, ld, mu);
+  const bool vec = vec_ok(X, ld, mu);
   const bool wvec = reinterpret_cast<uintptr_t>(w) % 16 == 0;
   double acc[ALS_SROWS] = {0.0, 0.0, 0.0, 0.0};
   const T* rowp[ALS_SROWS];
@@ -189,13 +162,13 @@ __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, cons
   for (int64_t f0 = c0 + 4 * threadIdx.x; f0 < c1; f0 += 1024) {
     double wv[4];
     T m[4] = {T(0), T(0), T(0), T(0)};
-    als_load4<double>(w, f0, c1, wvec, wv);
-    if (mu) als_load4<T>(mu, f0, c1, vec, m);
+    load4<double>(w, f0, c1, wvec, wv);
+    if (mu) load4<T>(mu, f0, c1, vec, m);
 #pragma unroll
     for (int t = 0; t < ALS_SROWS; ++t) {
       if (!live[t]) continue;
       T x[4];
-      als_load4<T>(rowp[t], f0, c1, vec, x);
+      load4<T>(rowp[t], f0, c1, vec, x);
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[t] += double(T(x[q] - m[q])) * wv[q];
     }
@@ -239,7 +212,7 @@ __device__ void als_corrected_score(const AlsBuf& B, const AlsViews& vw, int j, 
 
 // t~ of view i into B.tt (cca_zoo/linear/_iterative.py:138-158 on the deflated views)
 __global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double sh[ALS_PT / 64];
   __shared__ double coef[ALS_MAXK];
   const int n = B.n, d = st->dim;
@@ -275,7 +248,7 @@ __global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, 
 
 // once per sweep: delta, the stop test, the end of a dimension (cca_zoo/linear/_iterative.py:109-117, :91-93, _linalg.py:108-116)
 __global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, double tol, int max_iter, AlsStatus* st) {
-  if (als_stopped(st)) {
+  if (fit_stopped(st)) {
     if (threadIdx.x == 0) st->advance = 0;
     return;
   }
@@ -333,18 +306,18 @@ __global__ void __launch_bounds__(256) k_als_advance(AlsBuf B, const AlsStatus* 
 template <typename T>
 __global__ void __launch_bounds__(256) k_als_xt(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n, int rc,
                                                const double* __restrict__ tt, double* __restrict__ xpart, const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   const int64_t f0 = int64_t(blockIdx.x) * ALS_STRIP + 4 * threadIdx.x;
   if (f0 >= p) return;
   const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
-  const bool vec = als_vec_ok(X, ld, mu);
+  const bool vec = vec_ok(X, ld, mu);
   T m[4] = {T(0), T(0), T(0), T(0)};
-  if (mu) als_load4<T>(mu, f0, p, vec, m);
+  if (mu) load4<T>(mu, f0, p, vec, m);
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
   for (int r = r0; r < r1; ++r) {
     T x[4];
-    als_load4<T>(X + int64_t(r) * ld, f0, p, vec, x);
+    load4<T>(X + int64_t(r) * ld, f0, p, vec, x);
     const double t = tt[r];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] += double(T(x[q] - m[q])) * t;
@@ -360,7 +333,7 @@ __global__ void __launch_bounds__(256) k_als_xt(const T* __restrict__ X, const T
 // soft(raw, tau) for the fixed soft threshold)
 __global__ void __launch_bounds__(256) k_als_fold(const double* __restrict__ xpart, int nchunk, int64_t p, double* __restrict__ raw,
                                                  int rule, double par, double* __restrict__ fstat, const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double sh[4];
   double l1 = 0.0, mx = 0.0, ss = 0.0;
   for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
@@ -462,7 +435,7 @@ __device__ void als_candidates(int rule, int pass, double lo, double hi, double*
 __global__ void __launch_bounds__(256) k_als_levels(const double* __restrict__ raw, int64_t p, int rule, double par, int pass,
                                                    const double* __restrict__ fstat, int ng, double* __restrict__ lstate,
                                                    double* __restrict__ lpart, const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double cand[ALS_NC];
   __shared__ double tot[ALS_NC];
   __shared__ double red[4][ALS_NC];
@@ -515,7 +488,7 @@ __global__ void __launch_bounds__(256) k_als_norm(const double* __restrict__ raw
                                                  const double* __restrict__ fstat, int ng, const double* __restrict__ lstate,
                                                  const double* __restrict__ lpart, double* __restrict__ thr,
                                                  double* __restrict__ nstat, const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double sh[4];
   __shared__ double tot[ALS_NC];
   __shared__ double level;
@@ -556,7 +529,7 @@ __global__ void __launch_bounds__(256) k_als_apply(const double* __restrict__ ra
                                                   const double* __restrict__ fstat, int ng, const double* __restrict__ thr,
                                                   const double* __restrict__ nstat, double* __restrict__ w, double* __restrict__ dpart,
                                                   const AlsStatus* st) {
-  if (als_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double sh[4];
   double l1, mx, ss;
   als_fold_totals(fstat, ng, &l1, &mx, &ss, sh);
@@ -607,26 +580,18 @@ struct AlsState {
   std::vector<int64_t> p;
   std::vector<double> par;
   AlsBuf B;
-  AlsStatus* st = nullptr;
-  AlsStatus* st_pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ev_used[2] = {false, false};
-  int slot = 0;
+  ChunkDriver<AlsStatus> drv;
   bool has_init = false;
   int last_cs[ALS_MAXV] = {};
   std::vector<void*> allocs;
 };
 
 AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const* means) {
-  if (!views) fail(CCZ_EINVAL, "als: null views");
+  check_views("als", views, S.p);
   AlsViews vw;
   memset(&vw, 0, sizeof(vw));
   int64_t off = 0;
   for (int i = 0; i < S.M; ++i) {
-    if (!views[i].data) fail(CCZ_EINVAL, "als: null view %d", i);
-    if (views[i].cols != S.p[i])
-      fail(CCZ_EINVAL, "als: view %d has %lld columns, the fit state %lld", i, (long long)views[i].cols, (long long)S.p[i]);
-    if (views[i].ld < views[i].cols) fail(CCZ_EINVAL, "als: view %d: ld < cols", i);
     vw.X[i] = views[i].data;
     vw.mu[i] = means ? means[i] : nullptr;
     vw.ld[i] = views[i].ld;
@@ -648,7 +613,7 @@ template <typename T>
 void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
   const dim3 grid(unsigned((S.n + ALS_SROWS - 1) / ALS_SROWS), unsigned(vw.cs[i]));
   hipLaunchKernelGGL((k_als_score<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                     vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.st);
+                     vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.drv.dev);
   CCZ_LAUNCH_CHECK();
 }
 
@@ -656,7 +621,7 @@ template <typename T>
 void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const dim3 grid(unsigned((vw.p[i] + ALS_STRIP - 1) / ALS_STRIP), unsigned(S.B.nchunk));
   hipLaunchKernelGGL((k_als_xt<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                     vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.st);
+                     vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.drv.dev);
   CCZ_LAUNCH_CHECK();
 }
 
@@ -667,25 +632,25 @@ void launch_rule(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const int64_t p = vw.p[i];
   double* raw = B.raw + vw.off[i];
   double* fstat = B.fstat + size_t(i) * ALS_MAXG * 3;
-  hipLaunchKernelGGL(k_als_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, B.nchunk, p, raw, rule, vw.par[i], fstat, S.st);
+  hipLaunchKernelGGL(k_als_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, B.nchunk, p, raw, rule, vw.par[i], fstat, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   if (rule == RULE_SOFT_L1 || rule == RULE_TOP_S) {
     const int passes = rule == RULE_SOFT_L1 ? ALS_PMD_PASSES : ALS_SPAN_PASSES;
     for (int q = 0; q < passes; ++q) {
-      hipLaunchKernelGGL(k_als_levels, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], q, fstat, ng, B.lstate, B.lpart, S.st);
+      hipLaunchKernelGGL(k_als_levels, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], q, fstat, ng, B.lstate, B.lpart, S.drv.dev);
       CCZ_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_als_norm, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], passes, fstat, ng, B.lstate, B.lpart,
-                       B.thr + 2 * i, B.nstat, S.st);
+                       B.thr + 2 * i, B.nstat, S.drv.dev);
     CCZ_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_als_apply, dim3(ng), dim3(256), 0, stream(c), raw, p, rule, vw.par[i], fstat, ng, B.thr + 2 * i, B.nstat, B.w + vw.off[i],
-                     B.dpart + size_t(i) * ALS_MAXG, S.st);
+                     B.dpart + size_t(i) * ALS_MAXG, S.drv.dev);
   CCZ_LAUNCH_CHECK();
 }
 
 void launch_prologue(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
-  hipLaunchKernelGGL(k_als_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, i, S.st);
+  hipLaunchKernelGGL(k_als_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, i, S.drv.dev);
   CCZ_LAUNCH_CHECK();
 }
 
@@ -707,20 +672,17 @@ void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
     launch_rule(c, S, vw, i);
     score_any(c, S, vw, i, 0);
   }
-  hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, S.tol, S.max_iter, S.st);
+  hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, S.tol, S.max_iter, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   const int ga = int(std::max<int64_t>(1, std::min<int64_t>(256, (S.B.ptot + 2047) / 2048)));
-  hipLaunchKernelGGL(k_als_advance, dim3(ga), dim3(256), 0, stream(c), S.B, S.st);
+  hipLaunchKernelGGL(k_als_advance, dim3(ga), dim3(256), 0, stream(c), S.B, S.drv.dev);
   CCZ_LAUNCH_CHECK();
 }
 
 void als_free(ccz_ctx* c, AlsState* S) {
   sync(c);
   for (void* a : S->allocs) dev_free(c, a);
-  for (int i = 0; i < 2; ++i) {
-    if (S->st_pin[i]) (void)hipHostFree(S->st_pin[i]);
-    if (S->ev[i]) (void)hipEventDestroy(S->ev[i]);
-  }
+  S->drv.destroy(c);
   delete S;
 }
 
@@ -773,22 +735,12 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
     B.nstat = get(ALS_MAXG);
     B.thr = get(size_t(M) * 2);
     B.dpart = get(size_t(M) * ALS_MAXG);
-    S->st = static_cast<AlsStatus*>(dev_alloc(c, sizeof(AlsStatus)));
-    S->allocs.push_back(S->st);
-    for (int i = 0; i < 2; ++i) {
-      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S->st_pin[i]), sizeof(AlsStatus), hipHostMallocDefault));
-      CCZ_HIP(hipEventCreateWithFlags(&S->ev[i], hipEventDisableTiming));
-    }
+    S->drv.create(c);
   } catch (...) {
     als_free(c, S);
     throw;
   }
   return S;
-}
-
-AlsState* as_als(void* st) {
-  if (!st) fail(CCZ_EINVAL, "als: null fit state");
-  return static_cast<AlsState*>(st);
 }
 
 void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
@@ -801,7 +753,7 @@ void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
   zero(c, B.thr, size_t(S.M) * 16);
   AlsStatus st0;
   memset(&st0, 0, sizeof(st0));
-  h2d(c, S.st, &st0, sizeof(st0));
+  h2d(c, S.drv.dev, &st0, sizeof(st0));
   S.has_init = true;
 }
 
@@ -827,9 +779,9 @@ int ccz_als_destroy(ccz_handle h, void* state) {
 
 int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host) {
   CCZ_GUARD(h, {
-    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     ccz::sync(h);   // the pinned status slots may still be in use by an earlier fit on this state
-    S.ev_used[0] = S.ev_used[1] = false;
+    S.drv.reset();
     ccz::als_set_init(h, S, w0_host);
   })
 }
@@ -837,33 +789,24 @@ int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host) {
 int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_sweeps,
                    int64_t* sweeps_known, int* stopped_known) {
   CCZ_GUARD(h, {
-    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     if (!S.has_init) ccz::fail(CCZ_EINVAL, "als: ccz_als_set_init has not been called");
     if (n_sweeps < 0 || n_sweeps > S.chunk) ccz::fail(CCZ_EINVAL, "als: n_sweeps must be 0..%lld", (long long)S.chunk);
     const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
     for (int i = 0; i < S.M; ++i) S.last_cs[i] = vw.cs[i];
-    const int slot = S.slot;
-    if (S.ev_used[slot]) {
-      CCZ_HIP(hipEventSynchronize(S.ev[slot]));
-      if (sweeps_known) *sweeps_known = S.st_pin[slot]->total;
-      if (stopped_known) *stopped_known = S.st_pin[slot]->stopped;
-    } else {
-      if (sweeps_known) *sweeps_known = -1;
-      if (stopped_known) *stopped_known = 0;
-    }
+    const ccz::AlsStatus* seen = S.drv.wait(S.drv.slot);
+    if (sweeps_known) *sweeps_known = seen ? seen->total : -1;
+    if (stopped_known) *stopped_known = seen ? seen->stopped : 0;
     for (int64_t t = 0; t < n_sweeps; ++t) ccz::enqueue_sweep(h, S, vw);
-    CCZ_HIP(hipMemcpyAsync(S.st_pin[slot], S.st, sizeof(ccz::AlsStatus), hipMemcpyDeviceToHost, ccz::stream(h)));
-    CCZ_HIP(hipEventRecord(S.ev[slot], ccz::stream(h)));
-    S.ev_used[slot] = true;
-    S.slot ^= 1;
+    S.drv.publish(h);
   })
 }
 
 int ccz_als_status(ccz_handle h, void* state, int* dims_done, int* stopped, int64_t* sweeps_per_dim, double* last_delta) {
   CCZ_GUARD(h, {
-    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     ccz::AlsStatus st;
-    ccz::d2h(h, &st, S.st, sizeof(st));
+    ccz::d2h(h, &st, S.drv.dev, sizeof(st));
     if (dims_done) *dims_done = st.dim;
     if (stopped) *stopped = st.stopped;
     for (int64_t d = 0; d < S.k; ++d) {
@@ -890,7 +833,7 @@ int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_ro
 
 int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host) {
   CCZ_GUARD(h, {
-    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     const ccz::AlsBuf& B = S.B;
     if (!out_host || view < 0 || view >= S.M) ccz::fail(CCZ_EINVAL, "als: bad argument");
     int64_t off = 0;
@@ -922,7 +865,7 @@ int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host
 
 int ccz_als_get_weights(ccz_handle h, void* state, double* W_host) {
   CCZ_GUARD(h, {
-    ccz::AlsState& S = *ccz::as_als(state);
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     if (!W_host) ccz::fail(CCZ_EINVAL, "null argument");
     ccz::d2h(h, W_host, S.B.Wout, size_t(S.B.ptot) * S.k * 8);
   })

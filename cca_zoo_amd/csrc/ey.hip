@@ -34,6 +34,8 @@
 
 #include "hip_common.h"
 #include "abi_guard.h"
+#include "fit_driver.h"
+#include "row_load.h"
 
 namespace ccz {
 
@@ -86,8 +88,6 @@ template <> struct Mfma<double> {
   __device__ static int row(int lane, int r) { return (lane >> 4) + 4 * r; }
 };
 
-__device__ __forceinline__ bool ey_stopped(const EyStatus* st) { return st->stopped != 0; }
-
 // x - mu in the input precision (no centring when mu is null)
 template <typename T>
 __device__ __forceinline__ T ey_load(const T* row, const T* mu, int64_t f, int64_t p) {
@@ -95,14 +95,7 @@ __device__ __forceinline__ T ey_load(const T* row, const T* mu, int64_t f, int64
   return mu ? T(row[f] - mu[f]) : row[f];
 }
 
-// 16-byte loads of 4 consecutive features when every row start (and mu) is 16-byte aligned
-template <typename T>
-__device__ __forceinline__ bool ey_vec_ok(const T* X, int64_t ld, const T* mu) {
-  constexpr int64_t V = 16 / sizeof(T);
-  return (reinterpret_cast<uintptr_t>(X) % 16 == 0) && (ld % V == 0) && (!mu || reinterpret_cast<uintptr_t>(mu) % 16 == 0);
-}
-
-// x[t][q] = row_t[f0 + q] - mu[f0 + q] (zero beyond p or for dead rows); one or two 16-byte loads per row when allowed
+// x[t][q] = row_t[f0 + q] - mu[f0 + q] (zero beyond p or for dead rows); one or two 16-byte loads per row when `vec` (vec_ok)
 template <typename T, int NR>
 __device__ __forceinline__ void ey_load4(const T* const* rowp, const bool* live, const T* mu, int64_t f0, int64_t p, bool vec,
                                          T (*x)[4]) {
@@ -110,23 +103,8 @@ __device__ __forceinline__ void ey_load4(const T* const* rowp, const bool* live,
   for (int t = 0; t < NR; ++t) {
     if (vec && live[t] && f0 + 3 < p) {
       T v[4], m[4] = {T(0), T(0), T(0), T(0)};
-      if constexpr (sizeof(T) == 4) {
-        const float4 a = *reinterpret_cast<const float4*>(rowp[t] + f0);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        if (mu) {
-          const float4 b = *reinterpret_cast<const float4*>(mu + f0);
-          m[0] = b.x; m[1] = b.y; m[2] = b.z; m[3] = b.w;
-        }
-      } else {
-        const double2 a0 = *reinterpret_cast<const double2*>(rowp[t] + f0);
-        const double2 a1 = *reinterpret_cast<const double2*>(rowp[t] + f0 + 2);
-        v[0] = a0.x; v[1] = a0.y; v[2] = a1.x; v[3] = a1.y;
-        if (mu) {
-          const double2 b0 = *reinterpret_cast<const double2*>(mu + f0);
-          const double2 b1 = *reinterpret_cast<const double2*>(mu + f0 + 2);
-          m[0] = b0.x; m[1] = b0.y; m[2] = b1.x; m[3] = b1.y;
-        }
-      }
+      ld4(rowp[t] + f0, v);
+      if (mu) ld4(mu + f0, m);
 #pragma unroll
       for (int q = 0; q < 4; ++q) x[t][q] = mu ? T(v[q] - m[q]) : v[q];
     } else {
@@ -141,7 +119,7 @@ __device__ __forceinline__ void ey_load4(const T* const* rowp, const bool* live,
 template <typename T, int KT>
 __global__ void __launch_bounds__(256) k_ey_project(EyViews vw, const T* __restrict__ Wt, int64_t k, const int* __restrict__ idx,
                                                    int64_t bs, double* __restrict__ Z, const EyStatus* st) {
-  if (st && ey_stopped(st)) return;
+  if (st && fit_stopped(st)) return;
   typedef typename Mfma<T>::acc_t acc_t;
   __shared__ double red[4][EY_ROWS][16];
   const int v = blockIdx.y;
@@ -171,7 +149,7 @@ __global__ void __launch_bounds__(256) k_ey_project(EyViews vw, const T* __restr
 #pragma unroll
       for (int r = 0; r < 4; ++r) sum[t][kt][r] = 0.0;
     }
-  const bool vec = ey_vec_ok(X, ld, mu);
+  const bool vec = vec_ok(X, ld, mu);
   const int64_t nslice = (p + 15) / 16;
   int staged = 0;
   for (int64_t s = wave; s < nslice; s += 4) {
@@ -228,7 +206,7 @@ __device__ __forceinline__ double ey_half_sum(double v) {
 
 __global__ void __launch_bounds__(1024) k_ey_moments(const double* __restrict__ Z, int M, int64_t bs, int64_t k, double c,
                                                     EyScratch s, const EyStatus* st) {
-  if (ey_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double part[32];
   const int tid = threadIdx.x, sl = tid & 31, grp = tid >> 5;   // 32 groups of 32 lanes
   const double inv_bs = 1.0 / double(bs), norm = 1.0 / (double(M) * double(bs - 1));
@@ -295,7 +273,7 @@ __global__ void __launch_bounds__(256) k_ey_update(EyViews vw, const double* __r
                                                   const int* __restrict__ idx, int64_t bs, const double* __restrict__ Z,
                                                   EyScratch s, int M, double c, double lr, double mom,
                                                   double* __restrict__ Bpart, int bstride, const EyStatus* st) {
-  if (ey_stopped(st)) return;
+  if (fit_stopped(st)) return;
   typedef typename Mfma<T>::acc_t acc_t;
   extern __shared__ double ey_lds[];
   T* Ts = reinterpret_cast<T*>(ey_lds);                      // EY_TROWS x (16 KT)
@@ -310,7 +288,7 @@ __global__ void __launch_bounds__(256) k_ey_update(EyViews vw, const double* __r
   const T* mu = static_cast<const T*>(vw.mu[v]);
   const int64_t fw = int64_t(blockIdx.x) * 64 * Q + 16 * Q * wave;   // this wave's first feature
   const double scale = 4.0 / (double(M) * double(bs - 1));
-  const bool vec = ey_vec_ok(X, ld, mu);
+  const bool vec = vec_ok(X, ld, mu);
   acc_t acc[Q][KT];
   double sum[Q][KT][4];
 #pragma unroll
@@ -415,7 +393,7 @@ __global__ void __launch_bounds__(256) k_ey_update(EyViews vw, const double* __r
 // ---- launch 4: B(W_new), the objective, the stop test (one workgroup) -----------------------------------------------
 __global__ void __launch_bounds__(256) k_ey_finish(EyViews vw, const double* __restrict__ Bpart, int bstride, int M, int64_t k,
                                                   double c, double tol, EyScratch s, EyStatus* st, long long step) {
-  if (ey_stopped(st)) return;
+  if (fit_stopped(st)) return;
   __shared__ double part[256];
   const int tid = threadIdx.x;
   double tr = 0.0;
@@ -463,14 +441,11 @@ struct EyState {
   double* Z = nullptr;
   double* small = nullptr;   // zmean | V | vblend | B | reward
   double* Bpart = nullptr;
-  EyStatus* st = nullptr;
-  int* idx_dev[2] = {nullptr, nullptr};
+  ChunkDriver<EyStatus> drv;
+  int* idx_dev[2] = {nullptr, nullptr};   // the chunk's row indices ride on the driver's slots and events
   int* idx_pin[2] = {nullptr, nullptr};
-  EyStatus* st_pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ev_used[2] = {false, false};
-  int slot = 0;
   long long enqueued = 0;    // steps enqueued since the last set_weights
+  std::vector<void*> allocs;
   EyScratch scratch() const {
     EyScratch s;
     s.zmean = small;
@@ -488,14 +463,10 @@ int kt_for(int64_t k) {
 }
 
 EyViews make_views(const EyState& S, const ccz_view* views, const void* const* means) {
-  if (!views) fail(CCZ_EINVAL, "ey: null views");
+  check_views("ey", views, S.p);
   EyViews vw;
   memset(&vw, 0, sizeof(vw));
   for (int i = 0; i < S.M; ++i) {
-    if (!views[i].data) fail(CCZ_EINVAL, "ey: null view %d", i);
-    if (views[i].cols != S.p[i]) fail(CCZ_EINVAL, "ey: view %d has %lld columns, the fit state %lld", i, (long long)views[i].cols,
-                                      (long long)S.p[i]);
-    if (views[i].ld < views[i].cols) fail(CCZ_EINVAL, "ey: view %d: ld < cols", i);
     vw.X[i] = views[i].data;
     vw.mu[i] = means ? means[i] : nullptr;
     vw.ld[i] = views[i].ld;
@@ -525,7 +496,7 @@ void launch_update_q(ccz_ctx* c, const EyState& S, const EyViews& vw, int cur, c
   if constexpr (sizeof(T) == 4) Wt = S.Wf;
   const dim3 grid(unsigned(S.nblk_max), unsigned(S.M));
   const size_t lds = size_t(EY_TROWS) * 16 * KT * sizeof(T);
-  hipLaunchKernelGGL((k_ey_update<T, KT, Q>), grid, dim3(256), lds, stream(c), vw, S.W[cur], S.W[cur ^ 1], S.vel, Wt, S.k, idx, S.bs, S.Z, S.scratch(), S.M, S.c, S.lr, S.mom, S.Bpart, S.nblk_max, S.st);
+  hipLaunchKernelGGL((k_ey_update<T, KT, Q>), grid, dim3(256), lds, stream(c), vw, S.W[cur], S.W[cur ^ 1], S.vel, Wt, S.k, idx, S.bs, S.Z, S.scratch(), S.M, S.c, S.lr, S.mom, S.Bpart, S.nblk_max, S.drv.dev);
 }
 
 template <typename T>
@@ -542,13 +513,13 @@ void launch_update(ccz_ctx* c, const EyState& S, const EyViews& vw, int cur, con
 void enqueue_step(ccz_ctx* c, EyState& S, const EyViews& vw, const int* idx) {
   const int cur = int(S.enqueued & 1);
   const EyScratch s = S.scratch();
-  if (S.dtype == CCZ_F32) launch_project<float>(c, S, vw, S.Wf, idx, S.bs, S.Z, S.st);
-  else launch_project<double>(c, S, vw, S.W[cur], idx, S.bs, S.Z, S.st);
-  hipLaunchKernelGGL(k_ey_moments, dim3(1), dim3(1024), 0, stream(c), S.Z, S.M, S.bs, S.k, S.c, s, S.st);
+  if (S.dtype == CCZ_F32) launch_project<float>(c, S, vw, S.Wf, idx, S.bs, S.Z, S.drv.dev);
+  else launch_project<double>(c, S, vw, S.W[cur], idx, S.bs, S.Z, S.drv.dev);
+  hipLaunchKernelGGL(k_ey_moments, dim3(1), dim3(1024), 0, stream(c), S.Z, S.M, S.bs, S.k, S.c, s, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   if (S.dtype == CCZ_F32) launch_update<float>(c, S, vw, cur, idx);
   else launch_update<double>(c, S, vw, cur, idx);
-  hipLaunchKernelGGL(k_ey_finish, dim3(1), dim3(256), 0, stream(c), vw, S.Bpart, S.nblk_max, S.M, S.k, S.c, S.tol, s, S.st,
+  hipLaunchKernelGGL(k_ey_finish, dim3(1), dim3(256), 0, stream(c), vw, S.Bpart, S.nblk_max, S.M, S.k, S.c, S.tol, s, S.drv.dev,
                      (long long)S.enqueued);
   CCZ_LAUNCH_CHECK();
   ++S.enqueued;
@@ -556,19 +527,10 @@ void enqueue_step(ccz_ctx* c, EyState& S, const EyViews& vw, const int* idx) {
 
 void ey_free(ccz_ctx* c, EyState* S) {
   sync(c);
-  for (int i = 0; i < 2; ++i) {
-    dev_free(c, S->W[i]);
-    dev_free(c, S->idx_dev[i]);
+  for (void* a : S->allocs) dev_free(c, a);
+  S->drv.destroy(c);
+  for (int i = 0; i < 2; ++i)
     if (S->idx_pin[i]) (void)hipHostFree(S->idx_pin[i]);
-    if (S->st_pin[i]) (void)hipHostFree(S->st_pin[i]);
-    if (S->ev[i]) (void)hipEventDestroy(S->ev[i]);
-  }
-  dev_free(c, S->vel);
-  dev_free(c, S->Wf);
-  dev_free(c, S->Z);
-  dev_free(c, S->small);
-  dev_free(c, S->Bpart);
-  dev_free(c, S->st);
   delete S;
 }
 
@@ -601,30 +563,24 @@ EyState* ey_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t k, in
   S->nblk_max = 0;
   for (int i = 0; i < M; ++i) S->nblk_max = std::max<int>(S->nblk_max, int((p[i] + S->cols_per_blk - 1) / S->cols_per_blk));
   try {
+    auto get = [&](size_t bytes) { S->allocs.push_back(dev_alloc(c, bytes)); return S->allocs.back(); };
     const size_t wn = size_t(S->ptot * k);
-    for (int i = 0; i < 2; ++i) S->W[i] = static_cast<double*>(dev_alloc(c, wn * 8));
-    S->vel = static_cast<double*>(dev_alloc(c, wn * 8));
-    if (dtype == CCZ_F32) S->Wf = static_cast<float*>(dev_alloc(c, wn * 4));
-    S->Z = static_cast<double*>(dev_alloc(c, size_t(M) * bs * k * 8));
-    S->small = static_cast<double*>(dev_alloc(c, (size_t(M) * k + 3 * k * k + 1) * 8));
-    S->Bpart = static_cast<double*>(dev_alloc(c, size_t(M) * S->nblk_max * k * k * 8));
-    S->st = static_cast<EyStatus*>(dev_alloc(c, sizeof(EyStatus)));
+    for (int i = 0; i < 2; ++i) S->W[i] = static_cast<double*>(get(wn * 8));
+    S->vel = static_cast<double*>(get(wn * 8));
+    if (dtype == CCZ_F32) S->Wf = static_cast<float*>(get(wn * 4));
+    S->Z = static_cast<double*>(get(size_t(M) * bs * k * 8));
+    S->small = static_cast<double*>(get((size_t(M) * k + 3 * k * k + 1) * 8));
+    S->Bpart = static_cast<double*>(get(size_t(M) * S->nblk_max * k * k * 8));
+    S->drv.create(c);
     for (int i = 0; i < 2; ++i) {
-      S->idx_dev[i] = static_cast<int*>(dev_alloc(c, size_t(chunk) * bs * 4));
+      S->idx_dev[i] = static_cast<int*>(get(size_t(chunk) * bs * 4));
       CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S->idx_pin[i]), size_t(chunk) * bs * 4, hipHostMallocDefault));
-      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S->st_pin[i]), sizeof(EyStatus), hipHostMallocDefault));
-      CCZ_HIP(hipEventCreateWithFlags(&S->ev[i], hipEventDisableTiming));
     }
   } catch (...) {
     ey_free(c, S);
     throw;
   }
   return S;
-}
-
-EyState* as_state(void* st) {
-  if (!st) fail(CCZ_EINVAL, "ey: null fit state");
-  return static_cast<EyState*>(st);
 }
 
 void ey_set_weights(ccz_ctx* c, EyState& S, const double* W_host) {
@@ -653,13 +609,13 @@ void ey_set_weights(ccz_ctx* c, EyState& S, const double* W_host) {
   st0.steps = 0;
   st0.stopped = 0;
   st0.pad = 0;
-  h2d(c, S.st, &st0, sizeof(st0));
+  h2d(c, S.drv.dev, &st0, sizeof(st0));
   S.enqueued = 0;
 }
 
 // upload `rows` x bs host indices into slot `slot` (waits for the slot's previous chunk); returns the device pointer
 const int* upload_idx(ccz_ctx* c, EyState& S, int slot, const int64_t* idx_host, int64_t rows, int64_t n_rows_data) {
-  if (S.ev_used[slot]) CCZ_HIP(hipEventSynchronize(S.ev[slot]));
+  S.drv.wait(slot);
   int* pin = S.idx_pin[slot];
   for (int64_t e = 0; e < rows * S.bs; ++e) {
     const int64_t v = idx_host[e];
@@ -692,9 +648,9 @@ int ccz_ey_destroy(ccz_handle h, void* state) {
 
 int ccz_ey_set_weights(ccz_handle h, void* state, const double* W_host) {
   CCZ_GUARD(h, {
-    ccz::EyState& S = *ccz::as_state(state);
+    ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
     ccz::sync(h);   // the pinned slots / status may still be in use by an earlier fit on this state
-    S.ev_used[0] = S.ev_used[1] = false;
+    S.drv.reset();
     ccz::ey_set_weights(h, S, W_host);
   })
 }
@@ -702,13 +658,13 @@ int ccz_ey_set_weights(ccz_handle h, void* state, const double* W_host) {
 int ccz_ey_project(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_rows,
                    const int64_t* idx_host, double* Z_host) {
   CCZ_GUARD(h, {
-    ccz::EyState& S = *ccz::as_state(state);
+    ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
     if (!Z_host) ccz::fail(CCZ_EINVAL, "null argument");
     if (!idx_host && n_rows != S.bs) ccz::fail(CCZ_EINVAL, "ey: without indices n_rows must equal the batch rows");
     const ccz::EyViews vw = ccz::make_views(S, views, means_dev);
     ccz::sync(h);
     const int* idx = idx_host ? ccz::upload_idx(h, S, 0, idx_host, 1, n_rows) : nullptr;
-    S.ev_used[0] = false;
+    S.drv.used[0] = false;
     if (S.dtype == CCZ_F32) ccz::launch_project<float>(h, S, vw, S.Wf, idx, S.bs, S.Z, nullptr);
     else ccz::launch_project<double>(h, S, vw, S.W[int(S.enqueued & 1)], idx, S.bs, S.Z, nullptr);
     ccz::d2h(h, Z_host, S.Z, size_t(S.M) * S.bs * S.k * 8);
@@ -718,34 +674,25 @@ int ccz_ey_project(ccz_handle h, void* state, const ccz_view* views, const void*
 int ccz_ey_steps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_rows,
                  const int64_t* idx_host, int64_t n_steps, int64_t* steps_known, int* stopped_known) {
   CCZ_GUARD(h, {
-    ccz::EyState& S = *ccz::as_state(state);
+    ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
     if (n_steps < 0 || n_steps > S.chunk) ccz::fail(CCZ_EINVAL, "ey: n_steps must be 0..%lld", (long long)S.chunk);
     if (!idx_host && n_rows != S.bs) ccz::fail(CCZ_EINVAL, "ey: a full-batch step needs n_rows == batch rows");
     const ccz::EyViews vw = ccz::make_views(S, views, means_dev);
-    const int slot = S.slot;
-    // the slot's previous chunk is complete once its event is: its status copy is then valid on the host
-    if (S.ev_used[slot]) {
-      CCZ_HIP(hipEventSynchronize(S.ev[slot]));
-      if (steps_known) *steps_known = S.st_pin[slot]->steps;
-      if (stopped_known) *stopped_known = S.st_pin[slot]->stopped;
-    } else {
-      if (steps_known) *steps_known = -1;
-      if (stopped_known) *stopped_known = 0;
-    }
+    const int slot = S.drv.slot;
+    const ccz::EyStatus* seen = S.drv.wait(slot);
+    if (steps_known) *steps_known = seen ? seen->steps : -1;
+    if (stopped_known) *stopped_known = seen ? seen->stopped : 0;
     const int* idx = idx_host ? ccz::upload_idx(h, S, slot, idx_host, n_steps, n_rows) : nullptr;
     for (int64_t t = 0; t < n_steps; ++t) ccz::enqueue_step(h, S, vw, idx ? idx + t * S.bs : nullptr);
-    CCZ_HIP(hipMemcpyAsync(S.st_pin[slot], S.st, sizeof(ccz::EyStatus), hipMemcpyDeviceToHost, ccz::stream(h)));
-    CCZ_HIP(hipEventRecord(S.ev[slot], ccz::stream(h)));
-    S.ev_used[slot] = true;
-    S.slot ^= 1;
+    S.drv.publish(h);
   })
 }
 
 int ccz_ey_status(ccz_handle h, void* state, int64_t* steps_done, int* stopped, double* last_objective) {
   CCZ_GUARD(h, {
-    ccz::EyState& S = *ccz::as_state(state);
+    ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
     ccz::EyStatus st;
-    ccz::d2h(h, &st, S.st, sizeof(st));
+    ccz::d2h(h, &st, S.drv.dev, sizeof(st));
     if (steps_done) *steps_done = st.steps;
     if (stopped) *stopped = st.stopped;
     if (last_objective) *last_objective = st.last_obj;
@@ -754,10 +701,10 @@ int ccz_ey_status(ccz_handle h, void* state, int64_t* steps_done, int* stopped, 
 
 int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host) {
   CCZ_GUARD(h, {
-    ccz::EyState& S = *ccz::as_state(state);
+    ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
     if (!W_host) ccz::fail(CCZ_EINVAL, "null argument");
     ccz::EyStatus st;
-    ccz::d2h(h, &st, S.st, sizeof(st));
+    ccz::d2h(h, &st, S.drv.dev, sizeof(st));
     ccz::d2h(h, W_host, S.W[int(st.steps & 1)], size_t(S.ptot * S.k) * 8);
   })
 }

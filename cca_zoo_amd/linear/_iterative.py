@@ -22,7 +22,8 @@ import numpy as np
 from sklearn.utils._param_validation import Interval
 
 from cca_zoo_amd._base import BaseModel
-from cca_zoo_amd._utils._validation import is_device_tensor, perview_parameter, validate_views
+from cca_zoo_amd._utils._resident import MEANS_COLMEANS, ResidentViews
+from cca_zoo_amd._utils._validation import perview_parameter
 
 #: sweeps per ``ccz_als_sweeps`` call: one host wait (for the chunk two calls back) per chunk
 CHUNK_SWEEPS = 8
@@ -89,7 +90,7 @@ class _BaseIterative(BaseModel):
         return [0.0] * len(p)
 
     def fit(self, views, y=None):
-        from cca_zoo_amd import _backend, _dist
+        from cca_zoo_amd import _dist
 
         if _dist.is_sharded():
             raise NotImplementedError(
@@ -97,15 +98,10 @@ class _BaseIterative(BaseModel):
                 "fit it outside row_sharded()"
             )
         self._validate_params()
-        validated = validate_views(views, check_finite=False)
-        dev = [is_device_tensor(v) for v in validated]
-        if any(dev) and not all(dev):
-            raise ValueError("views must be all host arrays or all CUDA tensors")
-        validated = [v if d or v.dtype in (np.float32, np.float64) else v.astype(np.float64)
-                     for v, d in zip(validated, dev)]
-        m = len(validated)
-        n = int(validated[0].shape[0])
-        p = [int(v.shape[1]) for v in validated]
+        # the means of device rows in NumPy's own order of summation (ccz_als_colmeans): torch's tree-ordered float32 mean
+        # differs from v.mean(axis=0) in the last bits, and with it the whole trajectory
+        res = ResidentViews(views, self.center, MEANS_COLMEANS)
+        m, n, p = len(res.p), res.n, res.p
         k = int(self.latent_dimensions)
         if k > MAX_DIMS:
             raise ValueError(f"latent_dimensions={k}: the device path supports at most {MAX_DIMS}")
@@ -115,86 +111,38 @@ class _BaseIterative(BaseModel):
             raise ValueError("at least 1 sample is required")
         self.n_views_, self.n_features_in_, self.n_samples_ = m, p, n
         par = self._rule_parameters(p)
-        f32 = all((v.element_size() == 4) if d else (v.dtype == np.float32) for v, d in zip(validated, dev))
-        code = _backend.F32 if f32 else _backend.F64
-        h = _backend.handle_for(validated)
-
-        # dtype, contiguity and the means (the reference's _setup_fit: v.mean(axis=0) in the input dtype), in HBM
-        if all(dev):
-            import torch
-
-            tdt = torch.float32 if f32 else torch.float64
-            xs = [v.to(tdt) for v in validated]
-            xs = [x if (x.stride(1) == 1 and x.stride(0) >= x.shape[1]) else x.contiguous() for x in xs]
-            # the means are formed on the device in NumPy's own order of summation (ccz_als_colmeans, below): torch's
-            # tree-ordered float32 mean differs from v.mean(axis=0) in the last bits, and with it the whole trajectory
-            mus = [torch.empty(pi, dtype=tdt, device=x.device) for x, pi in zip(xs, p)] if self.center else None
-            ptrs = [(int(x.data_ptr()), int(x.stride(0))) for x in xs]
-            mptrs = [int(mu.data_ptr()) for mu in mus] if mus is not None else None
-            means_host = [np.zeros(pi) for pi in p]
-            keep = [xs, mus]
-        else:
-            ndt = np.float32 if f32 else np.float64
-            xs = [np.ascontiguousarray(v, dtype=ndt) for v in validated]
-            if not all(np.all(np.isfinite(x)) for x in xs):
-                raise ValueError("Input contains NaN or infinity.")
-            means_host = [x.mean(axis=0) for x in xs] if self.center else [np.zeros(pi) for pi in p]
-            bufs = [h.to_device(x) for x in xs]
-            mbufs = [h.to_device(np.ascontiguousarray(mu, dtype=ndt)) for mu in means_host] if self.center else None
-            ptrs = [(int(b.ptr), pi) for b, pi in zip(bufs, p)]
-            mptrs = [int(b.ptr) for b in mbufs] if mbufs is not None else None
-            keep = [bufs, mbufs]
-        varr = (_backend.View * m)()
-        for i, ((ptr, ld), pi) in enumerate(zip(ptrs, p)):
-            varr[i].data, varr[i].cols, varr[i].ld = ptr, pi, ld
-        marr = (C.c_void_p * m)(*mptrs) if mptrs is not None else None
-
         total = k * int(self.max_iter)
         chunk = max(1, min(CHUNK_SWEEPS, total))
         state = C.c_void_p()
-        sp = None
-        if all(dev):
-            import torch
-
-            sp = int(torch.cuda.current_stream(validated[0].device).cuda_stream)
-            h.acquire(sp)
-        try:
-            if sp is not None and mptrs is not None:
-                for i in range(m):
-                    h.check(h.lib.ccz_als_colmeans(h.raw, code, C.byref(varr[i]), n, C.c_void_p(mptrs[i])))
-            h.check(h.lib.ccz_als_create(h.raw, code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
+        with res:
+            h = res.handle
+            h.check(h.lib.ccz_als_create(h.raw, res.code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
                                          (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter),
                                          chunk, C.byref(state)))
-            w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
-            h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
-            done = 0
-            known, stopped = C.c_int64(-1), C.c_int(0)
-            while done < total and not stopped.value:
-                s = min(chunk, total - done)
-                h.check(h.lib.ccz_als_sweeps(h.raw, state, varr, marr, s, C.byref(known), C.byref(stopped)))
-                done += s
-            dims, stop = C.c_int(0), C.c_int(0)
-            iters = (C.c_int64 * k)()
-            deltas = (C.c_double * k)()
-            h.check(h.lib.ccz_als_status(h.raw, state, C.byref(dims), C.byref(stop), iters, deltas))
-            if not stop.value or dims.value != k:
-                raise RuntimeError(f"ALS fit ended after {dims.value} of {k} dimensions")   # cannot happen: k * max_iter sweeps
-            wflat = np.empty(sum(p) * k)
-            h.check(h.lib.ccz_als_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
-        finally:
-            if state:
+            try:
+                w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
+                h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
+                done = 0
+                known, stopped = C.c_int64(-1), C.c_int(0)
+                while done < total and not stopped.value:
+                    s = min(chunk, total - done)
+                    h.check(h.lib.ccz_als_sweeps(h.raw, state, res.varr, res.marr, s, C.byref(known), C.byref(stopped)))
+                    done += s
+                dims, stop = C.c_int(0), C.c_int(0)
+                iters = (C.c_int64 * k)()
+                deltas = (C.c_double * k)()
+                h.check(h.lib.ccz_als_status(h.raw, state, C.byref(dims), C.byref(stop), iters, deltas))
+                if not stop.value or dims.value != k:
+                    raise RuntimeError(f"ALS fit ended after {dims.value} of {k} dimensions")   # cannot happen: k * max_iter sweeps
+                wflat = np.empty(sum(p) * k)
+                h.check(h.lib.ccz_als_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
+            finally:
                 h.lib.ccz_als_destroy(h.raw, state)
-            if sp is not None:
-                h.release(sp)
-        if all(dev) and self.center:
-            means_host = [mu.cpu().numpy() for mu in keep[1]]
-        del keep
         self.n_iter_ = [int(x) for x in iters]
         self.last_delta_ = [float(x) for x in deltas]
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
-        self._store(weights, means_host, "f32" if f32 else "f64", weights_like_input=False)
+        self._store(weights, res.means_host(), "f32" if res.f32 else "f64", weights_like_input=False)
         return self
-
 
 class PLS_ALS(_BaseIterative):
     r"""Alternating power iteration for PLS (multiset NIPALS), every sweep on the device.

@@ -14,7 +14,7 @@ from typing import Any, ClassVar
 import numpy as np
 
 from cca_zoo_amd._base import BaseModel
-from cca_zoo_amd._utils._validation import is_device_tensor, validate_views
+from cca_zoo_amd._utils._resident import MEANS_TORCH, ResidentViews
 
 #: steps per ``ccz_ey_steps`` call: one host wait (for the chunk two calls back) and one index upload per chunk
 CHUNK_STEPS = 64
@@ -78,7 +78,7 @@ class BaseGradientModel(BaseModel):
         return float(self.c)
 
     def fit(self, views, y=None):
-        from cca_zoo_amd import _backend, _dist
+        from cca_zoo_amd import _dist
 
         if _dist.is_sharded():
             raise NotImplementedError(
@@ -86,15 +86,9 @@ class BaseGradientModel(BaseModel):
                 "fit it outside row_sharded()"
             )
         self._validate_params()
-        validated = validate_views(views, check_finite=False)
-        validated = [v if is_device_tensor(v) or v.dtype in (np.float32, np.float64) else v.astype(np.float64)
-                     for v in validated]
-        dev = [is_device_tensor(v) for v in validated]
-        if any(dev) and not all(dev):
-            raise ValueError("views must be all host arrays or all CUDA tensors")
-        m = len(validated)
-        n = int(validated[0].shape[0])
-        p = [int(v.shape[1]) for v in validated]
+        # the reference's _setup_fit: v.mean(axis=0) in the input dtype (torch's mean for device rows)
+        res = ResidentViews(views, self.center, MEANS_TORCH)
+        m, n, p = len(res.p), res.n, res.p
         k = int(self.latent_dimensions)
         if k > min(p):
             raise ValueError(f"latent_dimensions={k} exceeds the smallest view width ({min(p)})")
@@ -103,84 +97,44 @@ class BaseGradientModel(BaseModel):
         if n < 1:
             raise ValueError("at least 1 sample is required")
         self.n_views_, self.n_features_in_, self.n_samples_ = m, p, n
-        f32 = all((v.element_size() == 4) if d else (v.dtype == np.float32) for v, d in zip(validated, dev))
-        code = _backend.F32 if f32 else _backend.F64
         bs = n if self.batch_size is None else min(int(self.batch_size), n)
         full = bs == n
-        h = _backend.handle_for(validated)
-
-        # stage 1, on the caller's stream (device tensors) / the host: dtype, contiguity, means (the reference's
-        # _setup_fit: v.mean(axis=0) in the input dtype), then the rows and the means in HBM
-        if all(dev):
-            import torch
-
-            tdt = torch.float32 if f32 else torch.float64
-            xs = [v.to(tdt) for v in validated]
-            xs = [x if (x.stride(1) == 1 and x.stride(0) >= x.shape[1]) else x.contiguous() for x in xs]
-            mus = [x.mean(dim=0) for x in xs] if self.center else None
-            ptrs = [(int(x.data_ptr()), int(x.stride(0))) for x in xs]
-            mptrs = [int(mu.data_ptr()) for mu in mus] if mus is not None else None
-            means_host = [mu.detach().cpu().numpy() for mu in mus] if mus is not None else [np.zeros(pi) for pi in p]
-            keep = [xs, mus]
-        else:
-            ndt = np.float32 if f32 else np.float64
-            xs = [np.ascontiguousarray(v, dtype=ndt) for v in validated]
-            if not all(np.all(np.isfinite(x)) for x in xs):
-                raise ValueError("Input contains NaN or infinity.")
-            means_host = [x.mean(axis=0) for x in xs] if self.center else [np.zeros(pi) for pi in p]
-            bufs = [h.to_device(x) for x in xs]
-            mbufs = [h.to_device(np.ascontiguousarray(mu, dtype=ndt)) for mu in means_host] if self.center else None
-            ptrs = [(int(b.ptr), pi) for b, pi in zip(bufs, p)]
-            mptrs = [int(b.ptr) for b in mbufs] if mbufs is not None else None
-            keep = [bufs, mbufs]
-        varr = (_backend.View * m)()
-        for i, ((ptr, ld), pi) in enumerate(zip(ptrs, p)):
-            varr[i].data, varr[i].cols, varr[i].ld = ptr, pi, ld
-        marr = (C.c_void_p * m)(*mptrs) if mptrs is not None else None
-
-        sp = None
-        if all(dev):
-            import torch
-
-            sp = int(torch.cuda.current_stream(validated[0].device).cuda_stream)
-            h.acquire(sp)
         chunk = max(1, min(CHUNK_STEPS, int(self.max_iter)))
         state = C.c_void_p()
-        h.check(h.lib.ccz_ey_create(h.raw, code, m, (C.c_int64 * m)(*p), k, bs, chunk, self._ridge(),
-                                    float(self.learning_rate), float(self.momentum), float(self.tol), C.byref(state)))
-        try:
-            rng = np.random.default_rng(self.random_state)
+        with res:
+            h, varr, marr = res.handle, res.varr, res.marr
+            h.check(h.lib.ccz_ey_create(h.raw, res.code, m, (C.c_int64 * m)(*p), k, bs, chunk, self._ridge(),
+                                        float(self.learning_rate), float(self.momentum), float(self.tol), C.byref(state)))
+            try:
+                rng = np.random.default_rng(self.random_state)
 
-            def project(idx, w0s):
-                h.check(h.lib.ccz_ey_set_weights(h.raw, state, _dp(_wblocks(w0s))))
-                z = np.empty((m, bs, k))
-                ia = np.ascontiguousarray(idx, dtype=np.int64)
-                h.check(h.lib.ccz_ey_project(h.raw, state, varr, marr, n, ia.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             z.ctypes.data_as(C.POINTER(C.c_double))))
-                return [z[i] for i in range(m)]
+                def project(idx, w0s):
+                    h.check(h.lib.ccz_ey_set_weights(h.raw, state, _dp(_wblocks(w0s))))
+                    z = np.empty((m, bs, k))
+                    ia = np.ascontiguousarray(idx, dtype=np.int64)
+                    h.check(h.lib.ccz_ey_project(h.raw, state, varr, marr, n, ia.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 z.ctypes.data_as(C.POINTER(C.c_double))))
+                    return [z[i] for i in range(m)]
 
-            W0 = initial_weights(self._init_kind, p, k, n, bs, rng, project)
-            h.check(h.lib.ccz_ey_set_weights(h.raw, state, _dp(_wblocks(W0))))
-            done = 0
-            known, stopped = C.c_int64(-1), C.c_int(0)
-            while done < self.max_iter and not stopped.value:
-                s = min(chunk, int(self.max_iter) - done)
-                idx = None if full else draw_batches(rng, n, bs, s)
-                ip = None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int64))
-                h.check(h.lib.ccz_ey_steps(h.raw, state, varr, marr, n, ip, s, C.byref(known), C.byref(stopped)))
-                done += s
-            steps, stop, obj = C.c_int64(0), C.c_int(0), C.c_double(0.0)
-            h.check(h.lib.ccz_ey_status(h.raw, state, C.byref(steps), C.byref(stop), C.byref(obj)))
-            wflat = np.empty(sum(p) * k)
-            h.check(h.lib.ccz_ey_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
-        finally:
-            h.lib.ccz_ey_destroy(h.raw, state)
-            if sp is not None:
-                h.release(sp)
-        del keep
+                W0 = initial_weights(self._init_kind, p, k, n, bs, rng, project)
+                h.check(h.lib.ccz_ey_set_weights(h.raw, state, _dp(_wblocks(W0))))
+                done = 0
+                known, stopped = C.c_int64(-1), C.c_int(0)
+                while done < self.max_iter and not stopped.value:
+                    s = min(chunk, int(self.max_iter) - done)
+                    idx = None if full else draw_batches(rng, n, bs, s)
+                    ip = None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int64))
+                    h.check(h.lib.ccz_ey_steps(h.raw, state, varr, marr, n, ip, s, C.byref(known), C.byref(stopped)))
+                    done += s
+                steps, stop, obj = C.c_int64(0), C.c_int(0), C.c_double(0.0)
+                h.check(h.lib.ccz_ey_status(h.raw, state, C.byref(steps), C.byref(stop), C.byref(obj)))
+                wflat = np.empty(sum(p) * k)
+                h.check(h.lib.ccz_ey_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
+            finally:
+                h.lib.ccz_ey_destroy(h.raw, state)
         self.n_iter_ = int(steps.value)
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
-        self._store(weights, means_host, "f32" if f32 else "f64", weights_like_input=False)
+        self._store(weights, res.means_host(), "f32" if res.f32 else "f64", weights_like_input=False)
         return self
 
 

@@ -14,6 +14,7 @@ from sklearn.utils.validation import check_is_fitted
 
 from cca_zoo_amd._backend import DeviceBuffer as _DeviceBuffer
 from cca_zoo_amd._base import BaseModel
+from cca_zoo_amd._utils._resident import acquire, as_dtype, as_float, is_f32, release
 from cca_zoo_amd._utils._validation import is_device_tensor, perview_parameter, validate_views
 
 #: kernel names of sklearn's ``pairwise_kernels`` that the device kernels implement -> include/ccz.h CCZ_KERNEL_*
@@ -47,13 +48,6 @@ def kernel_specs(kernel, gamma, degree, coef0, kernel_params, n_views, n_feature
             g = 1.0 / n_features[i]
         specs.append((kind, float(g) if kind in _USES_GAMMA else 0.0, float(degree_[i]), float(coef0_[i])))
     return specs
-
-
-def _f(v):
-    """Floating views: float32 / float64 stay, anything else becomes float64 (as ``v - mean`` does in the reference)."""
-    if is_device_tensor(v):
-        return v
-    return v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
 
 
 class _DevView:
@@ -118,7 +112,7 @@ class KernelModel(BaseModel):
                 "fit it outside row_sharded()"
             )
         self._validate_params()
-        validated = [_f(v) for v in validate_views(views, check_finite=False)]
+        validated = [as_float(v) for v in validate_views(views, check_finite=False)]
         m = len(validated)
         n = int(validated[0].shape[0])
         n_features = [int(v.shape[1]) for v in validated]
@@ -153,14 +147,14 @@ class KernelModel(BaseModel):
         # every conversion (contiguous copies, host -> device) is enqueued BEFORE the handle's stream takes over, and
         # every tensor it reads stays referenced until the caller's stream has been made to wait for it again
         dviews = [_DevView(h, v) for v in self.train_views_]
-        sp = _acquire(h, validated)
+        sp = acquire(h, validated)
         try:
             Ks = [h.alloc(n * n * 8) for _ in range(m)]
             for i, A in enumerate(dviews):
                 pairwise_kernel(h, A, A, specs[i], Ks[i].ptr, n)
             W, vals, kk = self._solve(h, [K.ptr for K in Ks], n, k)
         finally:
-            _release(h, sp)
+            release(h, sp)
         self.weights_ = [w.copy() for w in W]
         self.eigenvalues_ = vals
         del Ks, dviews
@@ -178,7 +172,7 @@ class KernelModel(BaseModel):
         from cca_zoo_amd import _backend
 
         check_is_fitted(self)
-        validated = [_f(v) for v in validate_views(views, check_finite=False)]
+        validated = [as_float(v) for v in validate_views(views, check_finite=False)]
         if len(validated) != self.n_views_:
             raise ValueError(f"expected {self.n_views_} views, got {len(validated)}")
         h = _backend.handle_for(validated)
@@ -198,8 +192,8 @@ class KernelModel(BaseModel):
                     tr = tr.to(v.device)
             elif is_device_tensor(tr):
                 tr = tr.detach().cpu().numpy()
-            if not (_is_f32(tr) and _is_f32(v)):
-                tr, v = _as_dtype(tr, _backend.F64), _as_dtype(v, _backend.F64)
+            if not (is_f32(tr) and is_f32(v)):
+                tr, v = as_dtype(tr, _backend.F64), as_dtype(v, _backend.F64)
             A, B = _DevView(h, tr), _DevView(h, v)
             k = int(self.weights_[i].shape[1])
             if is_device_tensor(v):
@@ -212,7 +206,7 @@ class KernelModel(BaseModel):
                 zp = z.ptr
             prepared.append((A, B, k, z, zp))
         # stage 2, on the handle's stream; the caller's stream waits for it before anything above is released
-        sp = _acquire(h, validated)
+        sp = acquire(h, validated)
         try:
             keep = []
             for i, (A, B, k, z, zp) in enumerate(prepared):
@@ -220,7 +214,7 @@ class KernelModel(BaseModel):
                 keep.append(wd)
                 kernel_project(h, A, B, self._specs[i], wd.ptr, k, zp, k)
         finally:
-            _release(h, sp)
+            release(h, sp)
         out = []
         for A, B, k, z, zp in prepared:
             if isinstance(z, _DeviceBuffer):
@@ -240,7 +234,7 @@ class KernelModel(BaseModel):
         from cca_zoo_amd._moments import compute_moments
 
         check_is_fitted(self)
-        validated = [_f(v) for v in validate_views(views, check_finite=False)]
+        validated = [as_float(v) for v in validate_views(views, check_finite=False)]
         zs = self.transform(validated)
         out = []
         for v, z in zip(validated, zs):
@@ -262,33 +256,3 @@ class KernelModel(BaseModel):
             out.append(h.to_host(od, (D, k))[:d].copy())
             del keep
         return out
-
-
-def _is_f32(v):
-    return v.element_size() == 4 if is_device_tensor(v) else v.dtype == np.float32
-
-
-def _as_dtype(v, code):
-    from cca_zoo_amd import _backend
-
-    if is_device_tensor(v):
-        import torch
-
-        return v.to(torch.float32 if code == _backend.F32 else torch.float64)
-    return np.asarray(v, dtype=np.float32 if code == _backend.F32 else np.float64)
-
-
-def _acquire(h, views):
-    """Device tensors: the handle's stream waits for the caller's current stream (no host wait)."""
-    if views and is_device_tensor(views[0]):
-        import torch
-
-        sp = int(torch.cuda.current_stream(views[0].device).cuda_stream)
-        h.acquire(sp)
-        return sp
-    return None
-
-
-def _release(h, sp):
-    if sp is not None:
-        h.release(sp)

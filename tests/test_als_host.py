@@ -241,14 +241,14 @@ def test_span_parameters_follow_the_reference():
 
 
 def test_mixed_host_and_device_views_rejected(monkeypatch):
-    from cca_zoo_amd.linear import _iterative
+    from cca_zoo_amd._utils import _resident
 
     class FakeTensor:
         shape = (20, 4)
 
-    real = _iterative.is_device_tensor
-    monkeypatch.setattr(_iterative, "is_device_tensor", lambda v: isinstance(v, FakeTensor) or real(v))
-    monkeypatch.setattr(_iterative, "validate_views", lambda views, **kw: list(views))
+    real = _resident.is_device_tensor
+    monkeypatch.setattr(_resident, "is_device_tensor", lambda v: isinstance(v, FakeTensor) or real(v))
+    monkeypatch.setattr(_resident, "validate_views", lambda views, **kw: list(views))
     with pytest.raises(ValueError, match="all host arrays or all CUDA tensors"):
         _classes()["PLS_ALS"]().fit([np.zeros((20, 3)), FakeTensor()])
 

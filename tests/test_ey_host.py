@@ -153,6 +153,20 @@ def test_parameter_validation_and_new_errors(monkeypatch):
             cls().fit([X, Y])
 
 
+def test_mixed_host_and_device_views_rejected(monkeypatch):
+    from cca_zoo_amd._utils import _resident
+    from cca_zoo_amd.linear import CCA_EY
+
+    class FakeTensor:
+        shape = (20, 4)
+
+    real = _resident.is_device_tensor
+    monkeypatch.setattr(_resident, "is_device_tensor", lambda v: isinstance(v, FakeTensor) or real(v))
+    monkeypatch.setattr(_resident, "validate_views", lambda views, **kw: list(views))
+    with pytest.raises(ValueError, match="all host arrays or all CUDA tensors"):
+        CCA_EY().fit([np.zeros((20, 3)), FakeTensor()])
+
+
 # ---- index producer -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES)
 def test_index_producer_matches_golden_draws(case):
