@@ -67,27 +67,22 @@ using STR = const char*;
   /* ---- fp64 GEMM (gemm64_big.hip, gemm64_skinny.hip) ---- */                                                                               \
   X(GEMM_BIG_MIN_TILES, I64, 32, ONCE, "128 x 128 tiles from which a product takes the big kernel -- gemm64_big.hip gemm_f64_big_eligible: A/B") \
   X(GEMM_BIG_MIN_K, I64, 64, ONCE, "smallest K of the big kernel -- gemm64_big.hip gemm_f64_big_eligible: A/B")                              \
-  X(GEMM64_PIPE, I64, 1, ONCE, "0: the round-2 kernels instead of the pipelined ones -- gemm64_big.hip gemm_f64_big: A/B")                   \
   X(GEMM_HALF_TILE, I64, 1, ONCE, "0: no half-height tiles on grids smaller than the chip -- gemm64_big.hip gemm_f64_big: A/B")              \
   X(GEMM_SKINNY_OFF, STR, nullptr, ONCE, "text starting with 1: the skinny kernel is never eligible -- gemm64_skinny.hip gemm_f64_skinny_eligible: A/B") \
   /* ---- Cholesky and triangular solves (cholinv.hip, ops_hip.hip) ---- */                                                                   \
   X(CHOLINV_MFMA, INT, 2, ONCE, "64 x 64 block: 0 shift-register form, 1 MFMA with 4-column panels, 2 with 16-column panels (else: 2) -- cholinv.hip cholinv_form: A/B") \
   X(CHOLINV_CHAIN, INT, 1, ONCE, "0: the launch-per-link form instead of the persistent chain kernel -- cholinv.hip chain_launch: A/B")      \
   X(CHAIN_WGS, INT, 128, ONCE, "workgroups of the chain launch (below 2: 2; Impl::chain_cap overrides it) -- cholinv.hip chain_launch: A/B")  \
-  X(CHAIN_WGS_LA, INT, 64, ONCE, "the same on the look-ahead stream, next to the update GEMMs -- ops_hip.hip potrf_lower_batched_new: A/B")  \
+  X(CHAIN_WGS_LA, INT, 64, ONCE, "the same on the look-ahead stream, next to the update GEMMs -- ops_hip.hip potrf_lower_batched_sb: A/B")   \
   X(CHAIN_SLEEP, INT, 1, ONCE, "sleep of the chain kernel's polling loops (below 1: 1) -- cholinv.hip chain_launch: A/B")                    \
   X(CHAIN_DEBUG, INT, 0, ONCE, "non-zero: shader-clock stamps of matrix 0's chain workgroup per launch (synchronises) -- cholinv.hip chain_launch: trace") \
   X(POTRF_SB, I64, 512, LOAD, "256 | 512 | 1024 (else: 512) columns per super-block; every user of the kept inverses sees one value -- ops_hip.hip SB: A/B") \
   X(POTRF_LOOKAHEAD, INT, 1, ONCE, "0: the next super-block is factored on the handle's stream, not on a second one -- ops_hip.hip potrf_lookahead: A/B") \
   X(POTRF_RIDER, INT, 1, ONCE, "0: the first whitening solve does not ride along the factorization -- ops_hip.hip potrf_lower_batched_aux_rider: A/B") \
   X(BACKPROJ_SPLIT, INT, 4, ONCE, "split-K factor of the batched few-row solves -- ops_hip.hip trsm_right_lower_aux_multi: A/B")             \
-  X(SOLVER_LEGACY, INT, 0, ONCE, "non-zero: the round-1 blocked Cholesky / rank-64 triangular solves -- ops_hip.hip solver_legacy: A/B")     \
-  X(SOLVER_RECURSIVE, INT, -1, ONCE, "of the legacy solvers: 1 recursive, 0 and above 1 iterative, negative by size -- ops_hip.hip solver_mode: A/B") \
   /* ---- eigensolvers (solve.cpp, ops_hip.hip, evd_block.hip) ---- */                                                                        \
-  X(EVD_LEGACY, INT, 0, ONCE, "non-zero: the launch-per-round one-sided Jacobi of rounds 1-3 above d = 160 -- solve.cpp legacy_evd, ops_hip.hip jacobi_rows: A/B") \
   X(EVD_REFRESH_MIN, INT, 1536, ONCE, "size from which the block Jacobi restarts from clean data near convergence -- evd_block.hip syev_block: knob") \
   X(BJ_GROUP_MIN_TILES, I64, 2048, ONCE, "row tiles from which a workgroup takes four 64-column chunks -- evd_block.hip bj_row_group: A/B")  \
-  X(BJ_FUSED, INT, 0, ONCE, "1 (exactly): pair kernels and tile updates on two streams (measured: no gain) -- evd_block.hip bj_fused: A/B")  \
   X(BJ_GRAM_SPLIT, INT, 0, ONCE, "column splits of the pair Gram products (below 1: 1); UNSET: sized to fill the chip -- evd_block.hip jacobi_rows_block: A/B") \
   X(BJ_DEBUG, FLAG, false, ONCE, "clock stamps of the pair kernel's three waves, printed in sweep 2 -- evd_block.hip syev_block: trace")     \
   X(SYEV_TWOSIDED, INT, 2, ONCE, "small EVD: 2 packed H + replayed V' (d <= 160), 1 fused LDS kernel (d <= 96), else one-sided rows -- ops_hip.hip syev_mode: A/B") \

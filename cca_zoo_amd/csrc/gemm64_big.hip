@@ -9,8 +9,8 @@
 //     owns one row, reads 64 contiguous bytes of it and scatters 8 ds_write_b64 (consecutive lanes ->
 //     consecutive addresses).
 // Rows / columns past M / N are clamped on load and masked on store; K must be a multiple of 16.
-// The recursive Cholesky / triangular solves in ops_hip.hip put ~all solver flops through this kernel
-// with K >= 128 (the 64 x 64-tile generic kernel keeps the small and ragged products).
+// The super-blocked Cholesky / triangular solves in ops_hip.hip put ~all solver flops through this kernel
+// with K = 512 (the 64 x 64-tile generic kernel keeps the small and ragged products).
 #include <algorithm>
 #include <cstdlib>
 
@@ -26,151 +26,6 @@ constexpr int DK = 16;    // k-block
 
 constexpr int DS = DT + 2;   // LDS row stride (doubles): 16-byte aligned rows, transposing writes at most 2-way conflicted
 
-// stage a 16 (k) x 128 (m) block of an operand into `dst` ([16][DS] doubles)
-//   KMAJOR: element (k, m) at P[k * ld + m]: a wave copies one full 1-KiB row per load instruction
-//   else  : element (k, m) at P[m * ld + k]: 8 lanes cover the 16 k (128 contiguous bytes) of a row, a wave
-//           covers 8 rows per load instruction (full cache lines), and the 2 doubles are scattered to [k][m]
-template <bool KMAJOR>
-struct Stager {
-  v2f64 r[4];
-  __device__ __forceinline__ void load(const double* __restrict__ P, int64_t ld, int64_t m0, int64_t mlim, int64_t k0,
-                                       int tid) {
-    if (KMAJOR) {
-      const int64_t m = m0 + 2 * (tid & 63);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double* p = P + (k0 + (tid >> 6) + 4 * i) * ld;
-        if (m + 1 < mlim) {
-          r[i] = *reinterpret_cast<const v2f64*>(p + m);
-        } else {
-          r[i][0] = m < mlim ? p[m] : 0.0;
-          r[i][1] = 0.0;
-        }
-      }
-    } else {
-      const int kq = tid & 7;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t m = std::min<int64_t>(m0 + (tid >> 3) + 32 * i, mlim - 1);
-        r[i] = *reinterpret_cast<const v2f64*>(P + m * ld + k0 + 2 * kq);
-      }
-    }
-  }
-  __device__ __forceinline__ void store(double* dst, int tid) const {
-    if (KMAJOR) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<v2f64*>(dst + ((tid >> 6) + 4 * i) * DS + 2 * (tid & 63)) = r[i];
-    } else {
-      const int kq = tid & 7;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = (tid >> 3) + 32 * i;
-        dst[(2 * kq) * DS + m] = r[i][0];
-        dst[(2 * kq + 1) * DS + m] = r[i][1];
-      }
-    }
-  }
-};
-
-template <bool TA, bool TB>
-__global__ __launch_bounds__(256, 2) void k_gemm_f64_big(int64_t M, int64_t N, int64_t K, double alpha,
-                                                         const double* __restrict__ A, int64_t lda,
-                                                         const double* __restrict__ B, int64_t ldb, double beta,
-                                                         double* __restrict__ C, int64_t ldc, int lower_only,
-                                                         int64_t k_per_split) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* lds = reinterpret_cast<double*>(smem);  // [2 buffers][A | B][16][DS]
-  const int64_t m0 = int64_t(blockIdx.y) * DT, n0 = int64_t(blockIdx.x) * DT;
-  if (lower_only && n0 > m0 + (DT - 1)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-
-  v4f64 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-
-  // A is k-major in memory iff TA (stored K x M); B is k-major iff !TB (stored K x N)
-  Stager<TA> sa;
-  Stager<!TB> sb;
-  // split-K: slice z accumulates its K range into C with fp64 atomics (the launcher pre-scaled C by beta)
-  const bool split = gridDim.z > 1;
-  const int64_t kz0 = int64_t(blockIdx.z) * k_per_split;
-  const int64_t nkb = (min(K, kz0 + k_per_split) - kz0) / DK;
-  if (nkb <= 0) return;
-  sa.load(A, lda, m0, M, kz0, tid);
-  sb.load(B, ldb, n0, N, kz0, tid);
-  sa.store(lds, tid);
-  sb.store(lds + DK * DS, tid);
-  __syncthreads();
-  for (int64_t kb = 0; kb < nkb; ++kb) {
-    const int cur = int(kb & 1);
-    if (kb + 1 < nkb) {
-      sa.load(A, lda, m0, M, kz0 + (kb + 1) * DK, tid);
-      sb.load(B, ldb, n0, N, kz0 + (kb + 1) * DK, tid);
-    }
-    const double* as = lds + cur * (2 * DK * DS);
-    const double* bs = as + DK * DS;
-#pragma unroll
-    for (int kk = 0; kk < DK / 4; ++kk) {
-      const int krow = 4 * kk + (lane >> 4);
-      const double* ap = as + krow * DS + wr * 64 + 4 * (lane & 15);
-      const double* bp = bs + krow * DS + wc * 64 + 4 * (lane & 15);
-      const v2f64 a01 = *reinterpret_cast<const v2f64*>(ap), a23 = *reinterpret_cast<const v2f64*>(ap + 2);
-      const v2f64 b01 = *reinterpret_cast<const v2f64*>(bp), b23 = *reinterpret_cast<const v2f64*>(bp + 2);
-      const double a4[4] = {a01[0], a01[1], a23[0], a23[1]};
-      const double b4[4] = {b01[0], b01[1], b23[0], b23[1]};
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[ti], b4[tj], acc[ti][tj], 0, 0, 0);
-    }
-    if (kb + 1 < nkb) {
-      double* nx = lds + (cur ^ 1) * (2 * DK * DS);
-      sa.store(nx, tid);
-      sb.store(nx + DK * DS, tid);
-    }
-    __syncthreads();
-  }
-
-  // f64 16x16 C/D layout: col (B side) = lane & 15, row (A side) = (lane >> 4) + 4 * reg
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t m = m0 + wr * 64 + 4 * ((lane >> 4) + 4 * r) + ti;
-      if (m >= M) continue;
-      const int64_t nb = n0 + wc * 64 + 4 * (lane & 15);
-      double* cp = C + m * ldc + nb;
-      if (split) {
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-          if (nb + tj < N) unsafeAtomicAdd(cp + tj, alpha * acc[ti][tj][r]);
-      } else if (nb + 3 < N) {
-        v4f64 v = {acc[ti][0][r], acc[ti][1][r], acc[ti][2][r], acc[ti][3][r]};
-        v *= alpha;
-        if (beta != 0.0) {
-          const v2f64 c01 = *reinterpret_cast<const v2f64*>(cp), c23 = *reinterpret_cast<const v2f64*>(cp + 2);
-          v[0] += beta * c01[0]; v[1] += beta * c01[1]; v[2] += beta * c23[0]; v[3] += beta * c23[1];
-        }
-        *reinterpret_cast<v2f64*>(cp) = v2f64{v[0], v[1]};
-        *reinterpret_cast<v2f64*>(cp + 2) = v2f64{v[2], v[3]};
-      } else {
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-          if (nb + tj < N) {
-            double v = alpha * acc[ti][tj][r];
-            if (beta != 0.0) v += beta * cp[tj];
-            cp[tj] = v;
-          }
-      }
-    }
-}
-
 // ---------------------------------------------------------------------------
 // 64 x 128 tile variant for grids that the 128 x 128 tile cannot fill.  The super-block products of the triangular
 // solves and Cholesky panels are M x 512 x 512: at M = 4096 that is 128 tiles on 256 CUs, and a tile's 128 x 128 x 512
@@ -179,9 +34,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f64_big(int64_t M, int64_t N, i
 // each: 4 x 2 MFMA tiles, all waves read the same A fragment rows).
 // ---------------------------------------------------------------------------
 constexpr int HM = 64;         // tile rows
-constexpr int HSA = HM + 2;    // LDS row stride of the A image
 
-template <bool KMAJOR, int W>   // 16 (k) x W (m) block, W = 64 or 128; same two layouts as Stager
+// stage a 16 (k) x W (m) block of an operand, W = 64 or 128, into `dst` ([16][stride] doubles)
+//   KMAJOR: element (k, m) at P[k * ld + m]: a wave copies whole rows per load instruction
+//   else  : element (k, m) at P[m * ld + k]: 8 lanes cover the 16 k (128 contiguous bytes) of a row, a wave
+//           covers 8 rows per load instruction (full cache lines), and the 2 doubles are scattered to [k][m]
+template <bool KMAJOR, int W>
 struct StagerW {
   static constexpr int NI = W / 32;          // 16-byte loads per thread
   static constexpr int TPR = W / 2;          // k-major: threads per k-row
@@ -225,91 +83,11 @@ struct StagerW {
   }
 };
 
-template <bool TA, bool TB>
-__global__ __launch_bounds__(256, 2) void k_gemm_f64_half(int64_t M, int64_t N, int64_t K, double alpha,
-                                                          const double* __restrict__ A, int64_t lda,
-                                                          const double* __restrict__ B, int64_t ldb, double beta,
-                                                          double* __restrict__ C, int64_t ldc) {
-  extern __shared__ __attribute__((aligned(16))) char smem_h[];
-  double* lds = reinterpret_cast<double*>(smem_h);   // [2 buffers][A: 16 x HSA | B: 16 x DS]
-  constexpr int BUF = DK * (HSA + DS);
-  const int64_t m0 = int64_t(blockIdx.y) * HM, n0 = int64_t(blockIdx.x) * DT;
-  const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6;     // wave wc: columns [32 wc, 32 wc + 32)
-  v4f64 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-  StagerW<TA, HM> sa;
-  StagerW<!TB, DT> sb;
-  const int64_t nkb = K / DK;
-  sa.load(A, lda, m0, M, 0, tid);
-  sb.load(B, ldb, n0, N, 0, tid);
-  sa.store(lds, HSA, tid);
-  sb.store(lds + DK * HSA, DS, tid);
-  __syncthreads();
-  for (int64_t kb = 0; kb < nkb; ++kb) {
-    const int cur = int(kb & 1);
-    if (kb + 1 < nkb) {
-      sa.load(A, lda, m0, M, (kb + 1) * DK, tid);
-      sb.load(B, ldb, n0, N, (kb + 1) * DK, tid);
-    }
-    const double* as = lds + cur * BUF;
-    const double* bs = as + DK * HSA;
-#pragma unroll
-    for (int kk = 0; kk < DK / 4; ++kk) {
-      const int krow = 4 * kk + (lane >> 4);
-      const double* ap = as + krow * HSA + 4 * (lane & 15);
-      const double* bp = bs + krow * DS + wc * 32 + 2 * (lane & 15);
-      const v2f64 a01 = *reinterpret_cast<const v2f64*>(ap), a23 = *reinterpret_cast<const v2f64*>(ap + 2);
-      const v2f64 b01 = *reinterpret_cast<const v2f64*>(bp);
-      const double a4[4] = {a01[0], a01[1], a23[0], a23[1]};
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        acc[ti][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[ti], b01[0], acc[ti][0], 0, 0, 0);
-        acc[ti][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[ti], b01[1], acc[ti][1], 0, 0, 0);
-      }
-    }
-    if (kb + 1 < nkb) {
-      double* nx = lds + (cur ^ 1) * BUF;
-      sa.store(nx, HSA, tid);
-      sb.store(nx + DK * HSA, DS, tid);
-    }
-    __syncthreads();
-  }
-  // C/D layout of the 16 x 16 tile: col (B side) = lane & 15, row (A side) = (lane >> 4) + 4 * reg; tile ti owns the rows
-  // == ti mod 4, tile tj the columns == tj mod 2 of the wave's 32
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t m = m0 + 4 * ((lane >> 4) + 4 * r) + ti;
-      if (m >= M) continue;
-      const int64_t nb = n0 + wc * 32 + 2 * (lane & 15);
-      double* cp = C + m * ldc + nb;
-      if (nb + 1 < N) {
-        v2f64 v = {alpha * acc[ti][0][r], alpha * acc[ti][1][r]};
-        if (beta != 0.0) {
-          const v2f64 c01 = *reinterpret_cast<const v2f64*>(cp);
-          v[0] += beta * c01[0];
-          v[1] += beta * c01[1];
-        }
-        *reinterpret_cast<v2f64*>(cp) = v;
-      } else if (nb < N) {
-        double v = alpha * acc[ti][0][r];
-        if (beta != 0.0) v += beta * cp[0];
-        cp[0] = v;
-      }
-    }
-}
-
 // ---------------------------------------------------------------------------
-// Round 6: both tiles on ONE software-pipelined loop (k_gemm_f64_pipe<TA, TB, TM>, TM = 128 or 64).  The kernels above keep a
-// k-block's MFMA stream apart from its staging: loads at the top, 64 (32) MFMAs, `s_waitcnt vmcnt(0)`, transposing ds_writes,
-// `s_waitcnt lgkmcnt(0)`, barrier, and the next block starts with the latency of its first fragment reads -- 400 - 500 idle
-// cycles per 4096 (2048) MFMA cycles with one workgroup per CU, and two workgroups per CU fall into step.  Measured with
+// Both tiles run ONE software-pipelined loop (k_gemm_f64_pipe<TA, TB, TM>, TM = 128 or 64).  The round-2 kernels (one per tile,
+// in the history) kept a k-block's MFMA stream apart from its staging: loads at the top, 64 (32) MFMAs, `s_waitcnt vmcnt(0)`, transposing ds_writes,
+// `s_waitcnt lgkmcnt(0)`, barrier, and the next block started with the latency of its first fragment reads -- 400 - 500 idle
+// cycles per 4096 (2048) MFMA cycles with one workgroup per CU, and two workgroups per CU fell into step.  Measured with
 // tools/gemm64_probe.py (profiles/r06_gemm64_probe.log): steady state 77 % (one workgroup per CU) / 84 % (two) of the fp64 matrix
 // peak against rocBLAS' 92 / 98 %.  Here the staging rides INSIDE the MFMA stream (an fp64 MFMA holds the pipe for 64 cycles: every
 // one of them hides a few other instructions):
@@ -481,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f64_pipe(int64_t M, int64_t N, 
 // Round 3 tried the wave-private LDS-DMA FIFO of K1 on the A B' shape of the Cholesky updates and forward triangular
 // solves (lane l of a 16-row MFMA tile loads X[16 t + (l & 15)][k0 + 2 (l >> 4) .. + 1] as one 16-byte
 // buffer_load ... lds; no barriers, no transposing scatter, 8 DMA + 8 ds_read_b128 per 32 MFMAs).  Correct, and SLOWER than
-// the staged kernels below: rCCA solve 14.4 vs 13.6 ms, GCCA (D = 16384) 201 vs 178 ms.  With the projection kernel's
+// the staged kernel above: rCCA solve 14.4 vs 13.6 ms, GCCA (D = 16384) 201 vs 178 ms.  With the projection kernel's
 // result (gemm_big.hip) the lesson is that the FIFO pays when one DMA instruction moves 1 KiB of CONTIGUOUS memory (K1:
 // a k-step of X'X is two full row segments); gathering 16 - 64-byte pieces from 16 - 32 different rows per instruction runs
 // the texture path at a fraction of that rate, and a cooperative, coalesced stage + LDS transpose wins.  (Measured on the
@@ -511,70 +289,17 @@ __global__ void k_scale2d_f64(int64_t total, int64_t cols, double* __restrict__ 
 
 void gemm_f64_big(ccz_ctx* c, bool tA, bool tB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
                   int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, bool lower_only) {
-  const size_t lds_bytes = size_t(2) * 2 * DK * DS * 8;   // 65 KiB
   hipStream_t st = stream(c);
   const int64_t tm = (M + DT - 1) / DT, tn = (N + DT - 1) / DT;
   const int ncu = std::max(1, impl(c)->props.multiProcessorCount);
   int splits = 1;
   // (split-K with an fp64-atomic epilogue only where the tiles leave at least half of the chip idle: at one workgroup per CU the
   // pipelined kernel runs at 0.89 of the peak, and a 256-tile product measured 541 us split four ways against 272 us for rocBLAS)
-  const bool pipe_on = env::once(env::GEMM64_PIPE) != 0;
-  if (!lower_only && tm * tn * (pipe_on ? 2 : 1) < 2 * int64_t(ncu) && K >= 2048) {
+  if (!lower_only && tm * tn * 2 < 2 * int64_t(ncu) && K >= 2048) {
     splits = int(std::min<int64_t>({int64_t(16), (4 * ncu) / (tm * tn), K / 512}));
     if (splits < 2) splits = 1;
   }
   const bool use_half = env::once(env::GEMM_HALF_TILE) && splits == 1 && !lower_only && tm * tn < int64_t(ncu) && M > HM;
-  if (pipe_on) {
-    int64_t kps = K;
-    if (splits > 1) {
-      kps = ((K + splits - 1) / splits + DK - 1) / DK * DK;
-      splits = int((K + kps - 1) / kps);
-      const int64_t total = M * N;
-      hipLaunchKernelGGL(k_scale2d_f64, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st,
-                         total, N, C, ldc, beta);
-    }
-    const int lo = lower_only ? 1 : 0;
-#define CCZ_LAUNCH_PIPE(TA_, TB_, TM_)                                                                                  \
-  do {                                                                                                                  \
-    const size_t lds_p = size_t(2) * DK * ((TM_) + 2 + DS) * 8;                                                         \
-    const dim3 gridp((unsigned)tn, (unsigned)((M + (TM_) - 1) / (TM_)), (unsigned)splits);                              \
-    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_f64_pipe<TA_, TB_, TM_>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_p)));                               \
-    hipLaunchKernelGGL((k_gemm_f64_pipe<TA_, TB_, TM_>), gridp, dim3(256), lds_p, st, M, N, K, alpha, A, lda, B, ldb,   \
-                       beta, C, ldc, lo, kps);                                                                          \
-  } while (0)
-#define CCZ_LAUNCH_PIPE_T(TM_)                              \
-  do {                                                      \
-    if (!tA && !tB) CCZ_LAUNCH_PIPE(false, false, TM_);     \
-    else if (tA && !tB) CCZ_LAUNCH_PIPE(true, false, TM_);  \
-    else if (!tA && tB) CCZ_LAUNCH_PIPE(false, true, TM_);  \
-    else CCZ_LAUNCH_PIPE(true, true, TM_);                  \
-  } while (0)
-    if (use_half) CCZ_LAUNCH_PIPE_T(64);
-    else CCZ_LAUNCH_PIPE_T(128);
-#undef CCZ_LAUNCH_PIPE_T
-#undef CCZ_LAUNCH_PIPE
-    CCZ_LAUNCH_CHECK();
-    return;
-  }
-  if (use_half) {
-    const size_t lds_h = size_t(2) * DK * (HSA + DS) * 8;    // 49 KiB
-    dim3 gridh((unsigned)tn, (unsigned)((M + HM - 1) / HM), 1);
-#define CCZ_LAUNCH_HALF(TA_, TB_)                                                                                     \
-  do {                                                                                                                \
-    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_f64_half<TA_, TB_>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_h)));                             \
-    hipLaunchKernelGGL((k_gemm_f64_half<TA_, TB_>), gridh, dim3(256), lds_h, st, M, N, K, alpha, A, lda, B, ldb, beta, \
-                       C, ldc);                                                                                       \
-  } while (0)
-    if (!tA && !tB) CCZ_LAUNCH_HALF(false, false);
-    else if (tA && !tB) CCZ_LAUNCH_HALF(true, false);
-    else if (!tA && tB) CCZ_LAUNCH_HALF(false, true);
-    else CCZ_LAUNCH_HALF(true, true);
-#undef CCZ_LAUNCH_HALF
-    CCZ_LAUNCH_CHECK();
-    return;
-  }
   int64_t kps = K;
   if (splits > 1) {
     kps = ((K + splits - 1) / splits + DK - 1) / DK * DK;
@@ -583,20 +308,27 @@ void gemm_f64_big(ccz_ctx* c, bool tA, bool tB, int64_t M, int64_t N, int64_t K,
     hipLaunchKernelGGL(k_scale2d_f64, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st,
                        total, N, C, ldc, beta);
   }
-  dim3 grid((unsigned)tn, (unsigned)tm, (unsigned)splits);
   const int lo = lower_only ? 1 : 0;
-#define CCZ_LAUNCH_BIG(TA_, TB_)                                                                                  \
-  do {                                                                                                            \
-    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_f64_big<TA_, TB_>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));                     \
-    hipLaunchKernelGGL((k_gemm_f64_big<TA_, TB_>), grid, dim3(256), lds_bytes, st, M, N, K, alpha, A, lda, B, ldb, \
-                       beta, C, ldc, lo, kps);                                                                    \
+#define CCZ_LAUNCH_PIPE(TA_, TB_, TM_)                                                                                \
+  do {                                                                                                                \
+    const size_t lds_p = size_t(2) * DK * ((TM_) + 2 + DS) * 8;                                                       \
+    const dim3 gridp((unsigned)tn, (unsigned)((M + (TM_) - 1) / (TM_)), (unsigned)splits);                            \
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_f64_pipe<TA_, TB_, TM_>),                       \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_p)));                             \
+    hipLaunchKernelGGL((k_gemm_f64_pipe<TA_, TB_, TM_>), gridp, dim3(256), lds_p, st, M, N, K, alpha, A, lda, B, ldb, \
+                       beta, C, ldc, lo, kps);                                                                        \
   } while (0)
-  if (!tA && !tB) CCZ_LAUNCH_BIG(false, false);
-  else if (tA && !tB) CCZ_LAUNCH_BIG(true, false);
-  else if (!tA && tB) CCZ_LAUNCH_BIG(false, true);
-  else CCZ_LAUNCH_BIG(true, true);
-#undef CCZ_LAUNCH_BIG
+#define CCZ_LAUNCH_PIPE_T(TM_)                              \
+  do {                                                      \
+    if (!tA && !tB) CCZ_LAUNCH_PIPE(false, false, TM_);     \
+    else if (tA && !tB) CCZ_LAUNCH_PIPE(true, false, TM_);  \
+    else if (!tA && tB) CCZ_LAUNCH_PIPE(false, true, TM_);  \
+    else CCZ_LAUNCH_PIPE(true, true, TM_);                  \
+  } while (0)
+  if (use_half) CCZ_LAUNCH_PIPE_T(64);
+  else CCZ_LAUNCH_PIPE_T(128);
+#undef CCZ_LAUNCH_PIPE_T
+#undef CCZ_LAUNCH_PIPE
   CCZ_LAUNCH_CHECK();
 }
 

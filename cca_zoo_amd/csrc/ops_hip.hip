@@ -944,36 +944,13 @@ __global__ __launch_bounds__(64) void k_wave_chol_inv(double* __restrict__ A, in
   if (DO_CHOL && bad != 0x7fffffff && threadIdx.x == 0) atomicMin(info, int(j0 + bad + 1));
 }
 
-constexpr int MAXB = 8;
-struct CholBatch {
-  double* A[MAXB];
-  double* invT[MAXB];
-  int64_t lda[MAXB];
-  int64_t d[MAXB];
-};
-
-// one panel step of up to MAXB independent factorisations: block b factors the diagonal block at
-// column j0 of matrix b (if it has one) and forms its L^-T
-__global__ __launch_bounds__(64) void k_wave_chol_inv_batched(CholBatch bt, int64_t j0, int* __restrict__ info) {
-  extern __shared__ __attribute__((aligned(16))) char wave_smem[];
-  const int b = blockIdx.x;
-  if (j0 >= bt.d[b]) return;
-  const int nb = int(min(int64_t(NB), bt.d[b] - j0));
-  const int64_t lda = bt.lda[b];
-  const bool last = j0 + nb >= bt.d[b];          // last panel: no solve against it follows
-  const int bad = wave_block(bt.A[b] + j0 * lda + j0, lda, nb, true, last ? nullptr : bt.invT[b],
-                             reinterpret_cast<double*>(wave_smem));
-  if (bad != 0x7fffffff && threadIdx.x == 0) atomicMin(info + b, int(j0 + bad + 1));
-}
-
-// the wave kernels use 65 KiB of dynamic LDS: opt in once per device (never inside a graph capture)
+// the wave kernel uses 65 KiB of dynamic LDS: opt in once per device (never inside a graph capture)
 void wave_kernels_init() {
   static thread_local int done_for_device = -1;
   int dev = -1;
   CCZ_HIP(hipGetDevice(&dev));
   if (done_for_device == dev) return;
   CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wave_chol_inv<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(WAVE_BLOCK_LDS)));
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wave_chol_inv_batched), hipFuncAttributeMaxDynamicSharedMemorySize, int(WAVE_BLOCK_LDS)));
   done_for_device = dev;
 }
 
@@ -985,123 +962,12 @@ static void diag_inverses(ccz_ctx* c, const double* L, int64_t ldl, int64_t d, d
   CCZ_LAUNCH_CHECK();
 }
 
-// ---------------------------------------------------------------------------
-// Recursive blocked Cholesky / triangular solves.  The recursion halves the block until it reaches
-// the 64-column base case (the wave kernel above, which also leaves L_jj^-T in `invT`); every update
-// above the base case is a GEMM whose inner dimension is half the current block, so nearly all flops
-// run at K >= 128 on the 128x128-tile kernel instead of K = 64 rank updates (memory bound).
-// `invT` holds one 64 x 64 block per 64 columns of the matrix.
-// ---------------------------------------------------------------------------
-static int64_t split_point(int64_t n) {   // multiple of NB closest to n / 2 (at least NB)
-  const int64_t blocks = (n + NB - 1) / NB;
-  return std::max<int64_t>(1, blocks / 2) * NB;
-}
-
-// X (r x n) <- X L^-T (trans) or X L^-1 (!trans); L = lower n x n block whose diagonal 64-blocks have their
-// L^-T in invT[0 .. ceil(n/64))
-static void trsm_rec(ccz_ctx* c, bool trans, int64_t r, int64_t n, const double* L, int64_t ldl, const double* invT,
-                     double* X, int64_t ldx, double* tmp) {
-  if (n <= NB) {
-    gemm_ex(c, false, !trans, r, n, n, 1.0, X, ldx, invT, NB, 0.0, tmp, NB, X, ldx, false);
-    return;
-  }
-  const int64_t h = split_point(n), t = n - h;
-  const double* L21 = L + h * ldl;
-  const double* L22 = L + h * ldl + h;
-  const double* inv2 = invT + (h / NB) * NB * NB;
-  if (trans) {   // [X1 X2] [L11' L21'; 0 L22'] = [B1 B2]
-    trsm_rec(c, true, r, h, L, ldl, invT, X, ldx, tmp);
-    gemm(c, false, true, r, t, h, -1.0, X, ldx, L21, ldl, 1.0, X + h, ldx);          // B2 -= X1 L21'
-    trsm_rec(c, true, r, t, L22, ldl, inv2, X + h, ldx, tmp);
-  } else {       // [X1 X2] [L11 0; L21 L22] = [B1 B2]
-    trsm_rec(c, false, r, t, L22, ldl, inv2, X + h, ldx, tmp);
-    gemm(c, false, false, r, h, t, -1.0, X + h, ldx, L21, ldl, 1.0, X, ldx);          // B1 -= X2 L21
-    trsm_rec(c, false, r, h, L, ldl, invT, X, ldx, tmp);
-  }
-}
-
-struct PotrfJob {
-  double* A;
-  int64_t lda, d;
-  double* invT;   // ceil(d / 64) blocks
-  double* tmp;    // d x 64 scratch for the base-case dual-destination products
-};
-
-// factor the diagonal range [j0, j0 + n) of every job (all jobs share the recursion shape of the largest)
-static void potrf_rec(ccz_ctx* c, std::vector<PotrfJob>& jobs, int64_t j0, int64_t n, int* d_info) {
-  if (n <= NB) {
-    CholBatch bt;
-    const int nb = int(jobs.size());
-    for (int i = 0; i < MAXB; ++i) {
-      const PotrfJob& jb = jobs[std::min(i, nb - 1)];
-      bt.A[i] = jb.A;
-      bt.lda[i] = jb.lda;
-      bt.d[i] = i < nb ? jb.d : 0;
-      bt.invT[i] = jb.invT + (j0 / NB) * NB * NB;
-    }
-    hipLaunchKernelGGL(k_wave_chol_inv_batched, dim3(nb), dim3(64), WAVE_BLOCK_LDS, stream(c), bt, j0, d_info);
-    CCZ_LAUNCH_CHECK();
-    return;
-  }
-  const int64_t h = split_point(n), t = n - h;
-  potrf_rec(c, jobs, j0, h, d_info);
-  for (PotrfJob& jb : jobs) {
-    const int64_t hi = std::min(j0 + n, jb.d);
-    if (hi <= j0 + h) continue;
-    const int64_t tt = hi - (j0 + h);
-    double* A11 = jb.A + j0 * jb.lda + j0;
-    double* A21 = jb.A + (j0 + h) * jb.lda + j0;
-    double* A22 = jb.A + (j0 + h) * jb.lda + (j0 + h);
-    trsm_rec(c, true, tt, h, A11, jb.lda, jb.invT + (j0 / NB) * NB * NB, A21, jb.lda, jb.tmp);      // L21 = A21 L11^-T
-    gemm_ex(c, false, true, tt, tt, h, -1.0, A21, jb.lda, A21, jb.lda, 1.0, A22, jb.lda, nullptr, 0, true);  // A22 -= L21 L21'
-  }
-  (void)t;
-  potrf_rec(c, jobs, j0 + h, n - h, d_info);
-}
-
-static void potrf_lower_batched_rec(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info) {
-  Impl* im = impl(c);
-  for (int b0 = 0; b0 < count; b0 += MAXB) {
-    const int nbt = std::min(MAXB, count - b0);
-    int big[MAXB];
-    for (int i = 0; i < MAXB; ++i) big[i] = 0x7fffffff;
-    CCZ_HIP(hipMemcpyAsync(im->d_flag + 8, big, sizeof(big), hipMemcpyHostToDevice, stream(c)));
-    CCZ_HIP(hipStreamSynchronize(stream(c)));
-    std::vector<DBuf> bufs;
-    std::vector<PotrfJob> jobs;
-    int64_t dmax = 0;
-    for (int i = 0; i < nbt; ++i) {
-      const int64_t di = d[b0 + i];
-      const int64_t nblk = (di + NB - 1) / NB;
-      bufs.emplace_back(c, nblk * NB * NB);
-      double* inv = bufs.back().get();
-      bufs.emplace_back(c, std::max<int64_t>(di, 1) * NB);
-      jobs.push_back({A[b0 + i], lda[b0 + i], di, inv, bufs.back().get()});
-      dmax = std::max(dmax, di);
-    }
-    // jobs narrower than the widest simply run out of columns (the kernel / loops skip them)
-    potrf_rec(c, jobs, 0, (dmax + NB - 1) / NB * NB, im->d_flag + 8);
-    int got[MAXB];
-    d2h(c, got, im->d_flag + 8, sizeof(got));
-    for (int i = 0; i < nbt; ++i) info[b0 + i] = got[i] == 0x7fffffff ? 0 : got[i];
-  }
-}
-
 int potrf_lower(ccz_ctx* c, double* A, int64_t d, int64_t lda) {
   int info = 0;
   double* Ap[1] = {A};
   potrf_lower_batched(c, 1, Ap, &d, &lda, &info);
   return info;
 }
-
-static void trsm_right_lower_rec(ccz_ctx* c, bool trans, int64_t r, int64_t d, const double* L, int64_t ldl, double* X,
-                                 int64_t ldx) {
-  const int64_t nblk = (d + NB - 1) / NB;
-  DBuf invT(c, nblk * NB * NB), tmp(c, r * NB);
-  diag_inverses(c, L, ldl, d, invT);
-  trsm_rec(c, trans, r, d, L, ldl, invT, X, ldx, tmp);
-}
-
 
 // ---------------------------------------------------------------------------
 // hipGraph replay of fixed-shape launch sequences.  `fn` must only enqueue work on the handle's stream
@@ -1162,63 +1028,7 @@ static void graph_run(ccz_ctx* c, uint64_t key, F&& fn) {
 uint64_t graph_key_mix(uint64_t h, uint64_t v) { return key_mix(h, v); }
 void graph_run_fn(ccz_ctx* c, uint64_t key, const std::function<void()>& fn) { graph_run(c, key, fn); }
 
-// ---- iterative (one 64-column panel at a time) variants: fewer, smaller launches ----
-static void potrf_lower_batched_iter(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info) {
-  Impl* im = impl(c);
-  for (int b0 = 0; b0 < count; b0 += MAXB) {
-    const int nbt = std::min(MAXB, count - b0);
-    int big[MAXB];
-    for (int i = 0; i < MAXB; ++i) big[i] = 0x7fffffff;
-    CCZ_HIP(hipMemcpyAsync(im->d_flag + 8, big, sizeof(big), hipMemcpyHostToDevice, stream(c)));
-    CCZ_HIP(hipStreamSynchronize(stream(c)));
-    CholBatch bt;
-    std::vector<DBuf> invT, tmp;
-    int64_t dmax = 0;
-    for (int i = 0; i < MAXB; ++i) {
-      const int b = b0 + std::min(i, nbt - 1);     // pad the descriptor with the last matrix (never launched)
-      bt.A[i] = A[b];
-      bt.lda[i] = lda[b];
-      bt.d[i] = i < nbt ? d[b] : 0;
-      bt.invT[i] = nullptr;
-    }
-    for (int i = 0; i < nbt; ++i) {
-      invT.emplace_back(c, NB * NB);
-      tmp.emplace_back(c, std::max<int64_t>(d[b0 + i] - NB, 1) * NB);
-      bt.invT[i] = invT.back().get();
-      dmax = std::max(dmax, d[b0 + i]);
-    }
-    uint64_t key = key_mix(0x504f545246ull, uint64_t(nbt));
-    for (int i = 0; i < nbt; ++i) {
-      key = key_ptr(key, A[b0 + i]);
-      key = key_mix(key_mix(key, uint64_t(d[b0 + i])), uint64_t(lda[b0 + i]));
-      key = key_ptr(key_ptr(key, invT[i].get()), tmp[i].get());
-    }
-    graph_run(c, key, [&] {
-      for (int64_t j = 0; j < dmax; j += NB) {
-        hipLaunchKernelGGL(k_wave_chol_inv_batched, dim3(nbt), dim3(64), WAVE_BLOCK_LDS, stream(c), bt, j, im->d_flag + 8);
-        CCZ_LAUNCH_CHECK();
-        for (int i = 0; i < nbt; ++i) {
-          const int64_t di = d[b0 + i], ld = lda[b0 + i];
-          if (j >= di) continue;
-          const int nb = int(std::min<int64_t>(NB, di - j));
-          const int64_t rem = di - j - nb;
-          if (rem <= 0) continue;
-          double* Ab = A[b0 + i];
-          double* A21 = Ab + (j + nb) * ld + j;
-          // L21 = A21 L11^-T to the scratch panel and (second destination) back in place: a workgroup reads
-          // only its own 64 rows of A21 (all of K) before it writes them
-          gemm_ex(c, false, false, rem, nb, nb, 1.0, A21, ld, invT[i], NB, 0.0, tmp[i], NB, A21, ld, false);
-          gemm_ex(c, false, true, rem, rem, nb, -1.0, tmp[i], NB, tmp[i], NB, 1.0, Ab + (j + nb) * ld + (j + nb), ld, nullptr, 0, true);
-        }
-      }
-    });
-    int got[MAXB];
-    d2h(c, got, im->d_flag + 8, sizeof(got));
-    for (int i = 0; i < nbt; ++i) info[b0 + i] = got[i] == 0x7fffffff ? 0 : got[i];
-  }
-}
-
-
+// d < 1024: one 64-column block at a time against the explicit L_jj^-T of the diagonal blocks
 static void trsm_right_lower_iter(ccz_ctx* c, bool trans, int64_t r, int64_t d, const double* L, int64_t ldl, double* X,
                       int64_t ldx) {
   if (r <= 0 || d <= 0) return;
@@ -1507,9 +1317,10 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
   }
 }
 
-static bool potrf_lower_batched_new(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info,
-                                    double* const* aux = nullptr, const TrsmRider* rider = nullptr) {
-  // matrices up to 1024 columns go through the step kernels directly; wider ones super-blocked; both batched by 8
+// Dispatch of every factorization: matrices up to 1024 columns go through the step kernels directly; wider ones super-blocked;
+// both batched by 8.  Returns whether the rider rode along.
+static bool potrf_dispatch(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info,
+                           double* const* aux, const TrsmRider* rider) {
   std::vector<double*> As, Ab, Kb;
   std::vector<int64_t> ds, lds_, db, ldb_;
   std::vector<int> idx, idb;
@@ -1586,25 +1397,15 @@ static void trsm_right_lower_sb(ccz_ctx* c, bool trans, int64_t r, int64_t d, co
   }
 }
 
-// Dispatch: the recursive forms put the flops into large-K GEMMs but issue ~40% more (tiny) launches;
-// they pay off once the matrices are big enough for the GEMMs to dominate the launch latency.
-static int solver_mode() { return env::once(env::SOLVER_RECURSIVE); }
-static int solver_legacy() { return env::once(env::SOLVER_LEGACY); }
-
 void potrf_lower_batched(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info) {
-  int64_t dmax = 0;
-  for (int i = 0; i < count; ++i) dmax = std::max(dmax, d[i]);
-  if (!solver_legacy()) { potrf_lower_batched_new(c, count, A, d, lda, info); return; }
-  const int mode = solver_mode();
-  if (mode == 1 || (mode < 0 && dmax >= 6144)) potrf_lower_batched_rec(c, count, A, d, lda, info);
-  else potrf_lower_batched_iter(c, count, A, d, lda, info);
+  potrf_dispatch(c, count, A, d, lda, info, nullptr, nullptr);
 }
 
 // Factor and inverse of ONE small SPD matrix (ops.h): the chain kernel produces L^-1 next to L (cholinv_batched with X), so the
 // Cholesky-QR passes of the subspace iteration need no triangular solve -- X <- X L^-T is one product with the explicit inverse.
 int potrf_lower_inv(ccz_ctx* c, double* A, int64_t d, int64_t lda, double* Linv, int64_t ldi) {
   if (d < 1) fail(CCZ_EINVAL, "potrf_lower_inv: d >= 1 required");
-  if (solver_legacy() || d > 4096) {
+  if (d > 4096) {
     // (no chain kernel: factor, then L^-1 = I L^-1 by the triangular solve)
     const int info = potrf_lower(c, A, d, lda);
     if (info != 0) return info;
@@ -1628,35 +1429,32 @@ int potrf_lower_inv(ccz_ctx* c, double* A, int64_t d, int64_t lda, double* Linv,
 }
 
 int64_t trsm_aux_size(ccz_ctx*, int64_t d) {
-  if (solver_legacy() || d <= 1024) return 0;
+  if (d <= 1024) return 0;
   return (d + SB - 1) / SB * SB * SB;
 }
 
 void potrf_lower_batched_aux(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info,
                              double* const* aux) {
-  if (solver_legacy() || !aux) { potrf_lower_batched(c, count, A, d, lda, info); return; }
-  potrf_lower_batched_new(c, count, A, d, lda, info, aux);
+  potrf_dispatch(c, count, A, d, lda, info, aux, nullptr);
 }
 
 bool potrf_lower_batched_aux_rider(ccz_ctx* c, int count, double* const* A, const int64_t* d, const int64_t* lda, int* info,
                                    double* const* aux, const TrsmRider* rider) {
-  if (solver_legacy() || !aux || !env::once(env::POTRF_RIDER) || !rider) { potrf_lower_batched_aux(c, count, A, d, lda, info, aux); return false; }
-  return potrf_lower_batched_new(c, count, A, d, lda, info, aux, rider);
+  if (!aux || !env::once(env::POTRF_RIDER)) rider = nullptr;
+  return potrf_dispatch(c, count, A, d, lda, info, aux, rider);
 }
 
 void trsm_right_lower_aux(ccz_ctx* c, bool trans, int64_t r, int64_t d, const double* L, int64_t ldl, double* X,
                           int64_t ldx, const double* aux) {
   if (r <= 0 || d <= 0) return;
-  if (aux && !solver_legacy() && d > 1024) { trsm_right_lower_sb(c, trans, r, d, L, ldl, X, ldx, aux); return; }
+  if (aux && d > 1024) { trsm_right_lower_sb(c, trans, r, d, L, ldl, X, ldx, aux); return; }
   trsm_right_lower(c, trans, r, d, L, ldl, X, ldx);
 }
 
 void trsm_right_lower(ccz_ctx* c, bool trans, int64_t r, int64_t d, const double* L, int64_t ldl, double* X,
                       int64_t ldx) {
   if (r <= 0 || d <= 0) return;
-  if (!solver_legacy() && d >= 1024) { trsm_right_lower_sb(c, trans, r, d, L, ldl, X, ldx); return; }
-  const int mode = solver_mode();
-  if (mode == 1 || (mode < 0 && d >= 2048 && r >= 6144)) trsm_right_lower_rec(c, trans, r, d, L, ldl, X, ldx);
+  if (d >= 1024) trsm_right_lower_sb(c, trans, r, d, L, ldl, X, ldx);
   else trsm_right_lower_iter(c, trans, r, d, L, ldl, X, ldx);
 }
 
@@ -1667,7 +1465,7 @@ void trsm_right_lower(ccz_ctx* c, bool trans, int64_t r, int64_t d, const double
 //   stage 2:  X_b[:, rest] -= Y_b[:, J] L_b[., .]^(T)            (the not yet solved columns)
 void trsm_right_lower_aux_multi(ccz_ctx* c, int count, bool trans, const int64_t* r, const int64_t* d, const double* const* L,
                                 const int64_t* ldl, double* const* X, const int64_t* ldx, const double* const* aux) {
-  bool batched = !solver_legacy() && count >= 1 && count <= 8;
+  bool batched = count >= 1 && count <= 8;
   for (int b = 0; b < count && batched; ++b) batched = aux && aux[b] && d[b] > 1024 && r[b] >= 1 && r[b] <= 256;
   if (!batched) {
     for (int b = 0; b < count; ++b) trsm_right_lower_aux(c, trans, r[b], d[b], L[b], ldl[b], X[b], ldx[b], aux ? aux[b] : nullptr);
@@ -1714,57 +1512,8 @@ void trsm_right_lower_aux_multi(ccz_ctx* c, int count, bool trans, const int64_t
 }
 
 // ===========================================================================
-// one-sided Jacobi on rows: one workgroup per row pair, one launch per tournament round
+// one-sided Jacobi on rows
 // ===========================================================================
-template <int BS>
-__global__ __launch_bounds__(BS) void k_jacobi_round(int64_t p, int64_t pe, int64_t q, double* __restrict__ W,
-                                                     int64_t ldw, double* __restrict__ Q, int64_t qc, int64_t ldq,
-                                                     int64_t round, double tol, double floor2,
-                                                     int* __restrict__ counter) {
-  __shared__ double red[3][BS / 64 > 0 ? BS / 64 : 1];
-  const int64_t k = blockIdx.x, m1 = pe - 1;
-  int64_t a, b;
-  if (k == 0) { a = m1; b = round; } else { a = (round + k) % m1; b = (round - k + m1) % m1; }
-  if (a >= p || b >= p) return;
-  double* wa = W + a * ldw;
-  double* wb = W + b * ldw;
-  double al = 0.0, be = 0.0, ga = 0.0;
-  for (int64_t t = threadIdx.x; t < q; t += BS) {
-    const double x = wa[t], y = wb[t];
-    al += x * x; be += y * y; ga += x * y;
-  }
-  al = wave_sum(al); be = wave_sum(be); ga = wave_sum(ga);
-  if (BS > 64) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = al; red[1][wave] = be; red[2][wave] = ga; }
-    __syncthreads();
-    al = be = ga = 0.0;
-    for (int i = 0; i < BS / 64; ++i) { al += red[0][i]; be += red[1][i]; ga += red[2][i]; }
-  }
-  const double prod = al * be;
-  // rows whose norm has sunk below 1e-14 of the largest row are numerically zero: rotating rounding
-  // noise against real rows never meets the relative criterion (rank-deficient inputs)
-  if (!(prod > 0.0) || !(fmin(al, be) > floor2) || !(fabs(ga) > tol * sqrt(prod))) return;
-  if (threadIdx.x == 0) atomicAdd(counter, 1);
-  const double zeta = (be - al) / (2.0 * ga);
-  const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-  for (int64_t t = threadIdx.x; t < q; t += BS) {
-    const double x = wa[t], y = wb[t];
-    wa[t] = cs * x - sn * y;
-    wb[t] = sn * x + cs * y;
-  }
-  if (Q) {
-    double* qa = Q + a * ldq;
-    double* qb = Q + b * ldq;
-    for (int64_t t = threadIdx.x; t < qc; t += BS) {
-      const double x = qa[t], y = qb[t];
-      qa[t] = cs * x - sn * y;
-      qb[t] = sn * x + cs * y;
-    }
-  }
-}
-
 // Small problems (the Rayleigh-Ritz blocks of the subspace iteration, p ~ 80): the whole W and Q
 // live in LDS and ONE workgroup runs every round of every sweep.  A row pair is handled by a
 // 16-lane DPP row (64 pairs per pass of the 1024-thread workgroup); the three inner products
@@ -1843,23 +1592,18 @@ int jacobi_rows(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double
                 int max_sweeps) {
   if (p < 2) return 1;
   Impl* im = impl(c);
-  const int64_t pe = (p + 1) & ~int64_t(1);
-  const double tol = 2.220446049250313e-16 * std::sqrt(double(q)) * 4.0;
-  // rows whose squared norm is below 1e-28 of the largest never rotate (one row_dots + one blocking read-back): only the
-  // one-workgroup kernel and the legacy loop take it as an argument -- the block form finds its own on the device
-  auto rest_floor = [&]() {
+  const size_t lds_need = (size_t(p) * (q | 1) + (Q ? size_t(p) * (qc | 1) : 0)) * 8;
+  if (lds_need <= size_t(144) * 1024) {
+    const double tol = 2.220446049250313e-16 * std::sqrt(double(q)) * 4.0;
+    // rows whose squared norm is below 1e-28 of the largest never rotate (one row_dots + one blocking read-back): only the
+    // one-workgroup kernel takes it as an argument -- the block form finds its own on the device
     DBuf nn(c, p);
     row_dots(c, p, q, W, ldw, W, ldw, nn);
     std::vector<double> nh(p);
     d2h(c, nh.data(), nn, size_t(p) * 8);
     double mx = 0.0;
     for (double v : nh) mx = std::max(mx, v);
-    return mx * 1e-28;
-  };
-  double floor2 = 0.0;
-  const size_t lds_need = (size_t(p) * (q | 1) + (Q ? size_t(p) * (qc | 1) : 0)) * 8;
-  if (lds_need <= size_t(144) * 1024) {
-    floor2 = rest_floor();
+    const double floor2 = mx * 1e-28;
     CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_jacobi_lds), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_need + 16)));
     hipLaunchKernelGGL(k_jacobi_lds, dim3(1), dim3(1024), lds_need + 16, stream(c), int(p), int(q), W, ldw, Q, int(Q ? qc : 0), ldq,
                        tol, floor2, max_sweeps, im->d_flag + 1);
@@ -1869,42 +1613,19 @@ int jacobi_rows(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double
     if (sw < 0) fail(CCZ_ENOCONV, "Jacobi did not converge in %d sweeps (p=%lld, q=%lld)", max_sweeps, (long long)p, (long long)q);
     return sw;
   }
-  if (env::once(env::EVD_LEGACY) == 0) {
-    // evd_block.hip: 32-row blocks, Gram blocks + rotations as MFMA tiles.  It wants a multiple of 64 rows and even
-    // leading dimensions (16-byte row pieces): pad with zero rows (they never rotate) when the caller's shape differs.
-    const int64_t pp = (p + 63) / 64 * 64;
-    if (pp == p && (ldw & 1) == 0 && (!Q || (ldq & 1) == 0)) return jacobi_rows_block(c, p, q, W, ldw, Q, qc, ldq, max_sweeps);
-    const int64_t lw = (q + 1) & ~int64_t(1), lq = (qc + 1) & ~int64_t(1);
-    DBuf Wp(c, pp * lw), Qp(c, Q ? pp * lq : 0);
-    fill2d(c, pp, lw, Wp, lw, 0.0);
-    copy2d(c, p, q, W, ldw, Wp, lw);
-    if (Q) { fill2d(c, pp, lq, Qp, lq, 0.0); copy2d(c, p, qc, Q, ldq, Qp, lq); }
-    const int sw = jacobi_rows_block(c, pp, q, Wp, lw, Q ? Qp.get() : nullptr, qc, lq, max_sweeps);
-    copy2d(c, p, q, Wp, lw, W, ldw);
-    if (Q) copy2d(c, p, qc, Qp, lq, Q, ldq);
-    return sw;
-  }
-  const bool small = std::max(q, Q ? qc : 0) <= 256;
-  dim3 grid((unsigned)(pe / 2));
-  floor2 = rest_floor();
-  for (int sweep = 1; sweep <= max_sweeps; ++sweep) {
-    CCZ_HIP(hipMemsetAsync(im->d_flag + 1, 0, sizeof(int), stream(c)));
-    // one sweep = pe - 1 dependent tiny launches: replayed as a hipGraph after the first sweep
-    uint64_t key = key_mix(key_mix(0x4a41434full, uint64_t(p)), uint64_t(q));
-    key = key_mix(key_mix(key_ptr(key_ptr(key, W), Q), uint64_t(ldw)), uint64_t(ldq));
-    key = key_mix(key_mix(key, uint64_t(qc)), uint64_t(floor2 * 1e300));
-    graph_run(c, key, [&] {
-      for (int64_t round = 0; round < pe - 1; ++round) {
-        if (small) hipLaunchKernelGGL(k_jacobi_round<64>, grid, dim3(64), 0, stream(c), p, pe, q, W, ldw, Q, qc, ldq, round, tol, floor2, im->d_flag + 1);
-        else hipLaunchKernelGGL(k_jacobi_round<256>, grid, dim3(256), 0, stream(c), p, pe, q, W, ldw, Q, qc, ldq, round, tol, floor2, im->d_flag + 1);
-      }
-      CCZ_LAUNCH_CHECK();
-    });
-    int rot = 0;
-    d2h(c, &rot, im->d_flag + 1, sizeof(int));
-    if (rot == 0) return sweep;
-  }
-  fail(CCZ_ENOCONV, "Jacobi did not converge in %d sweeps (p=%lld, q=%lld)", max_sweeps, (long long)p, (long long)q);
+  // evd_block.hip: 32-row blocks, Gram blocks + rotations as MFMA tiles.  It wants a multiple of 64 rows and even
+  // leading dimensions (16-byte row pieces): pad with zero rows (they never rotate) when the caller's shape differs.
+  const int64_t pp = (p + 63) / 64 * 64;
+  if (pp == p && (ldw & 1) == 0 && (!Q || (ldq & 1) == 0)) return jacobi_rows_block(c, p, q, W, ldw, Q, qc, ldq, max_sweeps);
+  const int64_t lw = (q + 1) & ~int64_t(1), lq = (qc + 1) & ~int64_t(1);
+  DBuf Wp(c, pp * lw), Qp(c, Q ? pp * lq : 0);
+  fill2d(c, pp, lw, Wp, lw, 0.0);
+  copy2d(c, p, q, W, ldw, Wp, lw);
+  if (Q) { fill2d(c, pp, lq, Qp, lq, 0.0); copy2d(c, p, qc, Q, ldq, Qp, lq); }
+  const int sw = jacobi_rows_block(c, pp, q, Wp, lw, Q ? Qp.get() : nullptr, qc, lq, max_sweeps);
+  copy2d(c, p, q, Wp, lw, W, ldw);
+  if (Q) copy2d(c, p, qc, Qp, lq, Q, ldq);
+  return sw;
 }
 
 // ===========================================================================

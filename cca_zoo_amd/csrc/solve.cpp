@@ -62,9 +62,6 @@ std::vector<int64_t> offsets(const int64_t* dims, int m) {
 //     accuracy): a psd caller that separates "zero" from "small" must do so with an absolute floor well above that --
 //     make_whiteners' rank floor is kRankTol d lam_0 = 64 eps d lam_0 = 1.4e-14 d lam_0, a factor ~24 over the noise, and
 //     tests/test_gpu_seams_r5.py::test_rank_detection_between_the_kernels holds the detected rank at d = 320 / 256 / 700.
-// The legacy route below (CCZ_EVD_LEGACY=1): rows of (A + shift I) orthogonalised, shift = ||A||_inf so that +lam / -lam
-// pairs (MCCA with two views has them exactly) cannot mix; psd skips the shift.
-static bool legacy_evd() { return env::once(env::EVD_LEGACY) != 0; }
 static int syev_full_impl(ccz_ctx* c, double* A, int64_t d, bool psd, std::vector<double>& w,
                           double* Vrows, int64_t ldv, double small_tol = 2.220446049250313e-16) {
   if (!psd && d >= 2 && d <= syev_small_max(c)) {
@@ -83,7 +80,7 @@ static int syev_full_impl(ccz_ctx* c, double* A, int64_t d, bool psd, std::vecto
   }
   // PSD matrices small enough for the one-workgroup ONE-sided kernel keep it (relative accuracy of tiny eigenvalues)
   const bool lds_one_sided = psd && size_t(2) * d * (d | 1) * 8 <= size_t(144) * 1024;
-  if (d >= 2 && !legacy_evd() && !lds_one_sided) {
+  if (d >= 2 && !lds_one_sided) {
     // everything wider: two-sided block Jacobi (no shift, no definiteness assumed; A is only read)
     DBuf wd(c, d), V(c, d * d);
     const int sweeps = syev_block(c, A, d, d, wd, V, d, kMaxSweeps);
@@ -97,6 +94,7 @@ static int syev_full_impl(ccz_ctx* c, double* A, int64_t d, bool psd, std::vecto
     if (Vrows) gather_rows(c, d, d, V, d, perm.data(), nullptr, Vrows, ldv);
     return sweeps;
   }
+  // What is left: the one-sided rows of a small psd matrix, and d = 1 (not psd: rows of A + shift I, shift = ||A||_inf)
   double shift = 0.0;
   if (!psd) {
     shift = norm_inf(c, d, d, A, d);

@@ -85,8 +85,10 @@ def test_gemm_strided_views(H):
     assert np.all(got[:, :4] == 0) and np.all(got[:, 13:] == 0)
 
 
-@pytest.mark.parametrize("d", [1, 7, 64, 65, 200, 513])
+@pytest.mark.parametrize("d", [1, 7, 64, 65, 200, 513, 1023, 1024, 1025, 1600])
 def test_potrf_and_trsm(H, d):
+    # 1023: the blocked triangular solve's last size; 1024: the step-kernel factorization's last size and the super-blocked
+    # solve's first; 1025: the super-blocked factorization's first; 1600: a ragged fourth super-block
     rng = np.random.default_rng(d)
     X = rng.standard_normal((d + 10, d))
     S = X.T @ X / d + 0.1 * np.eye(d)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The solver's fp64 GEMM (ccz_gemm_f64: k_gemm_f64_big / k_gemm_f64_half) shape by shape against the 78.6 TF fp64 matrix
+"""The solver's fp64 GEMM (ccz_gemm_f64: k_gemm_f64_pipe, 128- and 64-row tiles) shape by shape against the 78.6 TF fp64 matrix
 peak and against torch.matmul (rocBLAS) on the same operands -- a measurement TOOL for DESIGN section 7 item 1.
 
   python tools/gemm64_probe.py            the shapes of the rCCA / GCCA solves (A B' with K = 512) + a K sweep
