@@ -134,6 +134,7 @@ SIGNATURES = {
     "ccz_als_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _int, _pdbl, _dbl, _i64, _i64, C.POINTER(_vp)]),
     "ccz_als_destroy": (_int, [_vp, _vp]),
     "ccz_als_set_init": (_int, [_vp, _vp, _pdbl]),
+    "ccz_als_admm_setup": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _dbl]),
     "ccz_als_sweeps": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pint]),
     "ccz_als_status": (_int, [_vp, _vp, _pint, _pint, _pi64, _pdbl]),
     "ccz_als_colmeans": (_int, [_vp, _int, C.POINTER(View), _i64, _vp]),

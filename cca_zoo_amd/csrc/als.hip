@@ -25,6 +25,23 @@
 // All reductions run in a fixed order (per-thread strided sums, wave butterflies, waves and workgroups in index order):
 // two fits of the same inputs give the same bits.
 //
+// SCCA_ADMM (cca_zoo/linear/_iterative.py:388-514) runs on the same buffers with its own ordering (Jacobi in the scores: the
+// targets of ALL views come from the vectors the iteration started with) and its own rule.  One iteration:
+//   M x  k_als_score          first iteration of a dimension only, as above
+//   per view i:
+//     k_als_admm_kq/_h or _xtq/_afold, k_als_admm_gnorm, k_als_admm_lfinal
+//                             first iteration of a dimension only (return at once otherwise): L_i = |X_d' X_d|_F / n + mu from
+//                             the Gram of the centred view, formed once on its smaller side (ccz_als_admm_setup), and Q_i
+//     k_als_admm_prologue     one workgroup: r = s_i - t_i, t_i as above, r~ = r - Q_i Q_i' r
+//     k_als_xt                per-chunk partial sums of (X_i - mu_i)' r~  =  X_d' X_d w_i - X_d' t_i
+//     k_als_admm_fold         w' = w_i - (that + mu eta_i) / L_i into raw; partial sums of squares of soft(w' + eta_i, tau_i / mu)
+//     k_als_admm_apply        z_i = that vector, over its norm when the norm exceeds 1; eta_i += w' - z_i; w_i <- z_i;
+//                             per-workgroup partial |z_i - w_i|^2
+//   M x  k_als_score          s_i = (X_i - mu_i) w_i of the new vectors: the next iteration's targets, the Q columns of k_als_finish
+//   k_als_finish, k_als_advance as above
+// z_i and w_i coincide between iterations (the reference starts from z = w and ends every iteration with w = z), so w_i - z_i
+// in its gradient is exactly zero and z has no buffer of its own; eta_i counts as zero at a dimension's first iteration.
+//
 // Precision: x - mu is rounded in the views' precision (the reference's own `v - v.mean(0)`), then widened; every product
 // and sum is fp64 (the reference's fp64 initial w promotes every product, cca_zoo/linear/_iterative.py:88-89).
 #include <algorithm>
@@ -50,7 +67,13 @@ constexpr int ALS_NC = 31;           // candidate levels per k_als_levels pass
 constexpr int ALS_PMD_PASSES = 10;   // 50 halvings, 5 per pass
 constexpr int ALS_SPAN_PASSES = 13;  // bits 62..0 of a non-negative double: 12 passes of 5 bits, one of 3
 
-enum { RULE_NORMALISE = 0, RULE_SOFT_FIXED = 1, RULE_SOFT_L1 = 2, RULE_TOP_S = 3 };
+constexpr int ALS_ADMM_MAXSIDE = 16384;   // SCCA_ADMM: largest min(n, p_i), the side of a view's stored Gram
+constexpr int ALS_LG = 256;          // k_als_admm_gnorm: workgroups (one partial sum each)
+constexpr int ALS_GT = 64;           // k_als_gram: tile edge
+constexpr int ALS_GKC = 32;          // k_als_gram: contraction indices per LDS stage
+constexpr int ALS_GLD = ALS_GKC + 1; // LDS row stride (doubles)
+
+enum { RULE_NORMALISE = 0, RULE_SOFT_FIXED = 1, RULE_SOFT_L1 = 2, RULE_TOP_S = 3, RULE_ADMM = 4 };
 
 struct AlsStatus {
   double last_delta[ALS_MAXK];     // delta of the last sweep of each dimension
@@ -74,6 +97,15 @@ struct AlsViews {
   int rule[ALS_MAXV];              // the rule of this view (top s with s >= p is plain normalisation)
 };
 
+// SCCA_ADMM: what ccz_als_admm_setup leaves for view i (side = min(n, p_i); the n side when n <= p_i)
+struct AdmmView {
+  double* G;        // side x side: (X - mu) (X - mu)' or (X - mu)' (X - mu)
+  double* U;        // k x side: n side H = K Q - Q (Q' K Q) / 2 (deflated Gram = K - Q H' - H Q'); p side A = (X - mu)' Q (G - A A')
+  double* KQ;       // n side only, k x n: K Q
+  int64_t side;
+  int nside;
+};
+
 // the device buffers of one fit
 struct AlsBuf {
   double* w;        // ptot: current vectors
@@ -90,6 +122,10 @@ struct AlsBuf {
   double* nstat;    // ALS_MAXG: k_als_norm partial sums of squares
   double* thr;      // M x 2: final level of view i's last update, 1.0 when thresholding applied
   double* dpart;    // M x ALS_MAXG: partial |w - w_old|^2
+  double* eta;      // SCCA_ADMM, ptot: scaled dual variables
+  double* tt2;      // SCCA_ADMM, n: the view's own corrected score while the prologue forms s_i - t_i
+  double* lip;      // SCCA_ADMM, M: L_i of the current dimension
+  double* gpart;    // SCCA_ADMM, ALS_LG: partial sums of squares of a deflated Gram
   int n, M, k, csmax, nchunk, rc;
   int64_t ptot, pmax;
 };
@@ -210,12 +246,10 @@ __device__ void als_corrected_score(const AlsBuf& B, const AlsViews& vw, int j, 
   __syncthreads();
 }
 
-// t~ of view i into B.tt (cca_zoo/linear/_iterative.py:138-158 on the deflated views)
-__global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
-  if (fit_stopped(st)) return;
-  __shared__ double sh[ALS_PT / 64];
-  __shared__ double coef[ALS_MAXK];
-  const int n = B.n, d = st->dim;
+// B.tt = t of view i: the sum of the other views' corrected scores, over its norm when that exceeds 1e-12
+// (cca_zoo/linear/_iterative.py:138-158 on the deflated views)
+__device__ void als_target(const AlsBuf& B, const AlsViews& vw, int i, int d, double* coef, double* sh) {
+  const int n = B.n;
   bool first = true;
   for (int j = 0; j < B.M; ++j) {
     if (j == i) continue;
@@ -230,7 +264,12 @@ __global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, 
   for (int r = threadIdx.x; r < n; r += ALS_PT) acc += B.tt[r] * B.tt[r];
   const double nrm = sqrt(als_block_sum<ALS_PT / 64>(acc, sh));
   if (nrm > 1e-12)
-    for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] /= nrm;     // every thread rereads only its own rows below
+    for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] /= nrm;     // every thread rereads only its own rows afterwards
+}
+
+// B.tt -= Q_i (Q_i' B.tt); every thread has written only its own rows of B.tt
+__device__ void als_correct_target(const AlsBuf& B, int i, int d, double* coef, double* sh) {
+  const int n = B.n;
   const double* Q = B.Q + int64_t(i) * B.k * n;
   for (int a = 0; a < d; ++a) {
     double q = 0.0;
@@ -244,6 +283,29 @@ __global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, 
     for (int a = 0; a < d; ++a) corr += Q[int64_t(a) * n + r] * coef[a];
     B.tt[r] -= corr;
   }
+}
+
+// t~ of view i into B.tt
+__global__ void __launch_bounds__(ALS_PT) k_als_prologue(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  const int d = st->dim;
+  als_target(B, vw, i, d, coef, sh);
+  als_correct_target(B, i, d, coef, sh);
+}
+
+// SCCA_ADMM: r~ = (s_i - t_i) - Q_i Q_i' (s_i - t_i) into B.tt, so that (X_i - mu_i)' r~ = X_d' X_d w_i - X_d' t_i
+// (cca_zoo/linear/_iterative.py:475-480); the scores are those the iteration started with for every view
+__global__ void __launch_bounds__(ALS_PT) k_als_admm_prologue(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  const int n = B.n, d = st->dim;
+  als_target(B, vw, i, d, coef, sh);
+  als_corrected_score(B, vw, i, d, B.tt2, false, coef, sh);
+  for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] = B.tt2[r] - B.tt[r];
+  als_correct_target(B, i, d, coef, sh);
 }
 
 // once per sweep: delta, the stop test, the end of a dimension (cca_zoo/linear/_iterative.py:109-117, :91-93, _linalg.py:108-116)
@@ -559,6 +621,238 @@ __global__ void __launch_bounds__(256) k_als_apply(const double* __restrict__ ra
   if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
 }
 
+// ---- SCCA_ADMM: the rule ------------------------------------------------------------------------------------------------
+// w' = w - (X_d'X_d w - X_d' t + mu (w - z + eta)) / L with w - z = 0 (see the head of the file) into raw; per-workgroup
+// partial sums of squares of soft(w' + eta, thr), thr = tau / mu (cca_zoo/linear/_iterative.py:480-483)
+__global__ void __launch_bounds__(256) k_als_admm_fold(const double* __restrict__ xpart, int nchunk, int64_t p,
+                                                      const double* __restrict__ w, const double* __restrict__ eta,
+                                                      const double* __restrict__ lip, double mu, double thr,
+                                                      double* __restrict__ raw, double* __restrict__ fstat, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  __shared__ double sh[4];
+  const bool first = st->sweep == 0;     // eta = 0 at the start of a dimension
+  const double L = *lip;
+  double ss = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    double v = 0.0;
+    for (int c = 0; c < nchunk; ++c) v += xpart[int64_t(c) * p + f];
+    const double e = first ? 0.0 : eta[f];
+    const double wp = w[f] - (v + mu * e) / L;
+    raw[f] = wp;
+    const double u = als_soft(wp + e, thr);
+    ss += u * u;
+  }
+  ss = als_block_sum<4>(ss, sh);
+  if (threadIdx.x == 0) fstat[3 * blockIdx.x + 2] = ss;
+}
+
+// z = soft(w' + eta, thr), over its norm when the norm exceeds 1; eta += w' - z; w <- z; per-workgroup partial |z - w|^2
+// (cca_zoo/linear/_iterative.py:483-493)
+__global__ void __launch_bounds__(256) k_als_admm_apply(const double* __restrict__ raw, int64_t p, double thr,
+                                                       const double* __restrict__ fstat, int ng, double* __restrict__ w,
+                                                       double* __restrict__ eta, double* __restrict__ dpart, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  __shared__ double sh[4];
+  const bool first = st->sweep == 0;
+  const double nrm = sqrt(als_block_sum<4>(int(threadIdx.x) < ng ? fstat[3 * threadIdx.x + 2] : 0.0, sh));
+  double dd = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    const double e = first ? 0.0 : eta[f], wp = raw[f];
+    double z = als_soft(wp + e, thr);
+    if (nrm > 1.0) z /= nrm;
+    eta[f] = e + wp - z;
+    const double diff = z - w[f];
+    dd += diff * diff;
+    w[f] = z;
+  }
+  dd = als_block_sum<4>(dd, sh);
+  if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
+}
+
+// ---- SCCA_ADMM: L_i = |X_d' X_d|_F / n + mu without the deflated view ---------------------------------------------------
+// |X_d' X_d|_F = |X_d X_d'|_F, and with Xc = X - mu, P = I - Q Q':  X_d X_d' = P K P (K = Xc Xc'),  X_d' X_d = G - A A'
+// (G = Xc' Xc, A = Xc' Q).  The Gram of the smaller side is formed once (k_als_gram); at the first iteration of a dimension
+// the kernels below bring K Q / A up to date with the newest column of Q and sum the squares of the deflated entries.  They
+// return at once on every other iteration.
+__device__ __forceinline__ bool admm_not_first(const AlsStatus* st) { return fit_stopped(st) || st->sweep != 0; }
+
+// n side: column d - 1 of K Q, one wave per row of K
+__global__ void __launch_bounds__(256) k_als_admm_kq(const double* __restrict__ K, int n, const double* __restrict__ Q,
+                                                    double* __restrict__ KQ, const AlsStatus* st) {
+  if (admm_not_first(st) || st->dim == 0) return;
+  const int a = st->dim - 1, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const double* q = Q + int64_t(a) * n;
+  double s = 0.0;
+  for (int c = threadIdx.x & 63; c < n; c += 64) s += K[int64_t(r) * n + c] * q[c];
+  s = als_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) KQ[int64_t(a) * n + r] = s;
+}
+
+// n side: H = K Q - Q (Q' K Q) / 2 over the d columns in use, one workgroup
+__global__ void __launch_bounds__(ALS_PT) k_als_admm_h(int n, const double* __restrict__ Q, const double* __restrict__ KQ,
+                                                      double* __restrict__ H, const AlsStatus* st) {
+  if (admm_not_first(st) || st->dim == 0) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double Cm[ALS_MAXK * ALS_MAXK];
+  const int d = st->dim;
+  for (int a = 0; a < d; ++a)
+    for (int b = 0; b < d; ++b) {
+      double acc = 0.0;
+      for (int r = threadIdx.x; r < n; r += ALS_PT) acc += Q[int64_t(a) * n + r] * KQ[int64_t(b) * n + r];
+      const double c = als_block_sum<ALS_PT / 64>(acc, sh);
+      if (threadIdx.x == 0) Cm[a * ALS_MAXK + b] = c;
+    }
+  __syncthreads();
+  for (int r = threadIdx.x; r < n; r += ALS_PT)
+    for (int a = 0; a < d; ++a) {
+      double qc = 0.0;
+      for (int b = 0; b < d; ++b) qc += Q[int64_t(b) * n + r] * Cm[b * ALS_MAXK + a];
+      H[int64_t(a) * n + r] = KQ[int64_t(a) * n + r] - 0.5 * qc;
+    }
+}
+
+// p side: per-chunk partial sums of column d - 1 of A = (X - mu)' Q, one thread per column of X
+template <typename T>
+__global__ void __launch_bounds__(256) k_als_admm_xtq(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
+                                                     int rc, const double* __restrict__ Q, double* __restrict__ xpart,
+                                                     const AlsStatus* st) {
+  if (admm_not_first(st) || st->dim == 0) return;
+  const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (f >= p) return;
+  const double* q = Q + int64_t(st->dim - 1) * n;
+  const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
+  const T m = mu ? mu[f] : T(0);
+  double acc = 0.0;
+  for (int r = r0; r < r1; ++r) acc += double(T(X[int64_t(r) * ld + f] - m)) * q[r];
+  xpart[int64_t(blockIdx.y) * p + f] = acc;
+}
+
+// p side: column d - 1 of A = the chunk partials summed in chunk order
+__global__ void __launch_bounds__(256) k_als_admm_afold(const double* __restrict__ xpart, int nchunk, int64_t p,
+                                                       double* __restrict__ A, const AlsStatus* st) {
+  if (admm_not_first(st) || st->dim == 0) return;
+  const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (f >= p) return;
+  double v = 0.0;
+  for (int c = 0; c < nchunk; ++c) v += xpart[int64_t(c) * p + f];
+  A[int64_t(st->dim - 1) * p + f] = v;
+}
+
+// per-workgroup partial sums of squares of the deflated Gram, entry by entry (expanding the norm instead would cancel):
+// n side G[r][c] - sum_a (Q[a][r] H[a][c] + H[a][r] Q[a][c]), p side G[r][c] - sum_a A[a][r] A[a][c].  Workgroup b takes
+// rows b, b + gridDim.x, ...; U = H or A, Qn = Q of the n side
+__global__ void __launch_bounds__(256) k_als_admm_gnorm(const double* __restrict__ G, int64_t side, const double* __restrict__ U,
+                                                       const double* __restrict__ Qn, int nside, double* __restrict__ gpart,
+                                                       const AlsStatus* st) {
+  if (admm_not_first(st)) return;
+  __shared__ double sh[4];
+  __shared__ double ur[ALS_MAXK], qr[ALS_MAXK];
+  const int d = st->dim;
+  double acc = 0.0;
+  for (int64_t r = blockIdx.x; r < side; r += gridDim.x) {
+    __syncthreads();
+    if (int(threadIdx.x) < d) {
+      ur[threadIdx.x] = U[int64_t(threadIdx.x) * side + r];
+      qr[threadIdx.x] = nside ? Qn[int64_t(threadIdx.x) * side + r] : 0.0;
+    }
+    __syncthreads();
+    for (int64_t c = threadIdx.x; c < side; c += 256) {
+      double corr = 0.0;
+      if (nside)
+        for (int a = 0; a < d; ++a) corr += qr[a] * U[int64_t(a) * side + c] + ur[a] * Qn[int64_t(a) * side + c];
+      else
+        for (int a = 0; a < d; ++a) corr += ur[a] * U[int64_t(a) * side + c];
+      const double v = G[r * side + c] - corr;
+      acc += v * v;
+    }
+  }
+  acc = als_block_sum<4>(acc, sh);
+  if (threadIdx.x == 0) gpart[blockIdx.x] = acc;
+}
+
+// L_i = sqrt(the partials summed in workgroup order) / n + mu (cca_zoo/linear/_iterative.py:481)
+__global__ void __launch_bounds__(256) k_als_admm_lfinal(const double* __restrict__ gpart, int ng, int n, double mu,
+                                                        double* __restrict__ lip, const AlsStatus* st) {
+  if (admm_not_first(st)) return;
+  __shared__ double sh[4];
+  const double s = als_block_sum<4>(int(threadIdx.x) < ng ? gpart[threadIdx.x] : 0.0, sh);
+  if (threadIdx.x == 0) *lip = sqrt(s) / double(n) + mu;
+}
+
+// The Gram of the centred view on one side, fp64 on v_mfma_f64_16x16x4f64 (lane maps as in kernel_matrix.hip: A operand
+// m = lane & 15, k = lane >> 4; B operand k = lane >> 4, n = lane & 15; C/D col = lane & 15, row = (lane >> 4) + 4 reg).
+// NSIDE: G[i][j] = sum_f x(i, f) x(j, f) over the p features (i, j rows); else G[i][j] = sum_r x(r, i) x(r, j) over the n
+// rows (i, j features); x = fl(X - mu) in the views' precision, as k_als_score rounds it.  256 threads, a 64 x 64 tile per
+// workgroup, each wave a 32 x 32 quarter; only tiles on and above the diagonal run, mirror_upper copies them down.
+template <typename T, bool NSIDE>
+__device__ __forceinline__ void gram_stage(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t side, int64_t klen,
+                                           int64_t i0, int64_t k0, double* lds) {
+#pragma unroll
+  for (int e = 0; e < ALS_GT * ALS_GKC / 256; ++e) {
+    const int idx = threadIdx.x + 256 * e;
+    // consecutive threads read consecutive addresses: features along a row
+    const int row = NSIDE ? idx / ALS_GKC : idx % ALS_GT, kk = NSIDE ? idx % ALS_GKC : idx / ALS_GT;
+    const int64_t i = i0 + row, kg = k0 + kk;
+    double v = 0.0;
+    if (i < side && kg < klen) {
+      const int64_t r = NSIDE ? i : kg, f = NSIDE ? kg : i;
+      const T x = X[r * ld + f];
+      v = double(mu ? T(x - mu[f]) : x);
+    }
+    lds[row * ALS_GLD + kk] = v;
+  }
+}
+
+template <typename T, bool NSIDE>
+__global__ void __launch_bounds__(256) k_als_gram(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t side,
+                                                 int64_t klen, double* __restrict__ G) {
+  if (blockIdx.x < blockIdx.y) return;   // strictly below the diagonal: mirrored afterwards
+  typedef double v4f64 __attribute__((ext_vector_type(4)));
+  __shared__ double As[ALS_GT * ALS_GLD];
+  __shared__ double Bs[ALS_GT * ALS_GLD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;
+  const int64_t i0 = int64_t(blockIdx.y) * ALS_GT, j0 = int64_t(blockIdx.x) * ALS_GT;
+  v4f64 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = v4f64{0.0, 0.0, 0.0, 0.0};
+  for (int64_t k0 = 0; k0 < klen; k0 += ALS_GKC) {
+    gram_stage<T, NSIDE>(X, mu, ld, side, klen, i0, k0, As);
+    gram_stage<T, NSIDE>(X, mu, ld, side, klen, j0, k0, Bs);
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < ALS_GKC; kk += 4) {
+      double a[2], b[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        a[t] = As[(32 * wr + 16 * t + lr) * ALS_GLD + kk + lk];
+        b[t] = Bs[(32 * wc + 16 * t + lr) * ALS_GLD + kk + lk];
+      }
+#pragma unroll
+      for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+        for (int tb = 0; tb < 2; ++tb) acc[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ta], b[tb], acc[ta][tb], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int tb = 0; tb < 2; ++tb) {
+    const int64_t j = j0 + 32 * wc + 16 * tb + lr;
+    if (j >= side) continue;
+#pragma unroll
+    for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t i = i0 + 32 * wr + 16 * ta + lk + 4 * r;
+        if (i < side) G[i * side + j] = acc[ta][tb][r];
+      }
+  }
+}
+
 // ---- column means as the reference forms them ----------------------------------------------------------------------------
 // NumPy's v.mean(axis=0) of a row-major array adds the rows in order in the array's own precision and divides by n
 // (cca_zoo/_base.py:97-99); one thread per column does exactly that, so the means of device rows equal the reference's bit for bit.
@@ -582,6 +876,9 @@ struct AlsState {
   AlsBuf B;
   ChunkDriver<AlsStatus> drv;
   bool has_init = false;
+  double mu = 0.0;                 // SCCA_ADMM: the penalty, and what ccz_als_admm_setup left per view
+  bool admm_ready = false;
+  AdmmView admm[ALS_MAXV] = {};
   int last_cs[ALS_MAXV] = {};
   std::vector<void*> allocs;
 };
@@ -664,7 +961,69 @@ void xt_any(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   else launch_xt<double>(c, S, vw, i);
 }
 
+// SCCA_ADMM: L_i at the first iteration of a dimension (the four kernels return at once otherwise)
+void launch_admm_lipschitz(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const AlsBuf& B = S.B;
+  const AdmmView& a = S.admm[i];
+  const double* Q = B.Q + int64_t(i) * B.k * S.n;
+  if (S.k > 1 && a.nside) {
+    hipLaunchKernelGGL(k_als_admm_kq, dim3(unsigned((S.n + 3) / 4)), dim3(256), 0, stream(c), a.G, int(S.n), Q, a.KQ, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_als_admm_h, dim3(1), dim3(ALS_PT), 0, stream(c), int(S.n), Q, a.KQ, a.U, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  } else if (S.k > 1) {
+    const dim3 grid(unsigned((vw.p[i] + 255) / 256), unsigned(B.nchunk));
+    if (S.dtype == CCZ_F32)
+      hipLaunchKernelGGL((k_als_admm_xtq<float>), grid, dim3(256), 0, stream(c), static_cast<const float*>(vw.X[i]),
+                         static_cast<const float*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
+    else
+      hipLaunchKernelGGL((k_als_admm_xtq<double>), grid, dim3(256), 0, stream(c), static_cast<const double*>(vw.X[i]),
+                         static_cast<const double*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_als_admm_afold, dim3(grid.x), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], a.U, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+  const int lg = int(std::min<int64_t>(ALS_LG, a.side));
+  hipLaunchKernelGGL(k_als_admm_gnorm, dim3(lg), dim3(256), 0, stream(c), a.G, a.side, a.U, Q, a.nside, B.gpart, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_als_admm_lfinal, dim3(1), dim3(256), 0, stream(c), B.gpart, lg, int(S.n), S.mu, B.lip + i, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+}
+
+void finish_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
+  hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, S.tol, S.max_iter, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+  const int ga = int(std::max<int64_t>(1, std::min<int64_t>(256, (S.B.ptot + 2047) / 2048)));
+  hipLaunchKernelGGL(k_als_advance, dim3(ga), dim3(256), 0, stream(c), S.B, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+}
+
+// one SCCA_ADMM iteration: every view's update reads the scores the iteration started with (Jacobi), so the new vectors are
+// scored only after the last update
+void enqueue_admm_iteration(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
+  const AlsBuf& B = S.B;
+  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 1);
+  for (int i = 0; i < S.M; ++i) {
+    launch_admm_lipschitz(c, S, vw, i);
+    hipLaunchKernelGGL(k_als_admm_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), B, vw, i, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    xt_any(c, S, vw, i);
+    const int ng = vw.ng[i];
+    const double thr = vw.par[i] / S.mu;
+    double* fstat = B.fstat + size_t(i) * ALS_MAXG * 3;
+    hipLaunchKernelGGL(k_als_admm_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], B.w + vw.off[i], B.eta + vw.off[i],
+                       B.lip + i, S.mu, thr, B.raw + vw.off[i], fstat, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_als_admm_apply, dim3(ng), dim3(256), 0, stream(c), B.raw + vw.off[i], vw.p[i], thr, fstat, ng, B.w + vw.off[i],
+                       B.eta + vw.off[i], B.dpart + size_t(i) * ALS_MAXG, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 0);
+  finish_sweep(c, S, vw);
+}
+
 void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
+  if (S.rule == RULE_ADMM) return enqueue_admm_iteration(c, S, vw);
   for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 1);
   for (int i = 0; i < S.M; ++i) {
     launch_prologue(c, S, vw, i);
@@ -672,11 +1031,7 @@ void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
     launch_rule(c, S, vw, i);
     score_any(c, S, vw, i, 0);
   }
-  hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(ALS_PT), 0, stream(c), S.B, vw, S.tol, S.max_iter, S.drv.dev);
-  CCZ_LAUNCH_CHECK();
-  const int ga = int(std::max<int64_t>(1, std::min<int64_t>(256, (S.B.ptot + 2047) / 2048)));
-  hipLaunchKernelGGL(k_als_advance, dim3(ga), dim3(256), 0, stream(c), S.B, S.drv.dev);
-  CCZ_LAUNCH_CHECK();
+  finish_sweep(c, S, vw);
 }
 
 void als_free(ccz_ctx* c, AlsState* S) {
@@ -693,7 +1048,7 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
   if (k < 1 || k > ALS_MAXK) fail(CCZ_EUNSUP, "als: 1 to %d latent dimensions are supported, got %lld", ALS_MAXK, (long long)k);
   if (!p || n < 1 || n > (int64_t(1) << 30) || max_iter < 1 || max_iter > (int64_t(1) << 30) || chunk < 1 || !(tol >= 0.0))
     fail(CCZ_EINVAL, "als: bad argument");
-  if (rule < RULE_NORMALISE || rule > RULE_TOP_S) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
+  if (rule < RULE_NORMALISE || rule > RULE_ADMM) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
   if (rule != RULE_NORMALISE && !par) fail(CCZ_EINVAL, "als: the rule needs one parameter per view");
   AlsState* S = new AlsState();
   S->dtype = dtype; S->M = M; S->rule = rule; S->max_iter = int(max_iter);
@@ -703,6 +1058,11 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
   B.n = int(n); B.M = M; B.k = int(k);
   for (int i = 0; i < M; ++i) {
     if (p[i] < 1) { delete S; fail(CCZ_EINVAL, "als: view %d has no columns", i); }
+    if (rule == RULE_ADMM && std::min(n, p[i]) > ALS_ADMM_MAXSIDE) {
+      delete S;
+      fail(CCZ_EUNSUP, "als: ADMM keeps a min(n, p) x min(n, p) Gram per view; view %d has min(n, p) = %lld > %d", i,
+           (long long)std::min(n, p[i]), ALS_ADMM_MAXSIDE);
+    }
     const double q = par ? par[i] : 0.0;
     if (rule == RULE_TOP_S && !(q >= 1.0)) { delete S; fail(CCZ_EINVAL, "als: top-s needs s >= 1 (view %d)", i); }
     if (rule != RULE_NORMALISE && !(q == q)) { delete S; fail(CCZ_EINVAL, "als: the parameter of view %d is NaN", i); }
@@ -735,12 +1095,53 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
     B.nstat = get(ALS_MAXG);
     B.thr = get(size_t(M) * 2);
     B.dpart = get(size_t(M) * ALS_MAXG);
+    if (rule == RULE_ADMM) {
+      B.eta = get(size_t(B.ptot));
+      B.tt2 = get(size_t(n));
+      B.lip = get(size_t(M));
+      B.gpart = get(ALS_LG);
+      for (int i = 0; i < M; ++i) {
+        AdmmView& a = S->admm[i];
+        a.nside = n <= p[i] ? 1 : 0;
+        a.side = std::min(n, p[i]);
+        a.G = get(size_t(a.side) * a.side);
+        a.U = get(size_t(k) * a.side);
+        a.KQ = a.nside ? get(size_t(k) * n) : nullptr;
+      }
+    }
     S->drv.create(c);
   } catch (...) {
     als_free(c, S);
     throw;
   }
   return S;
+}
+
+// SCCA_ADMM: the penalty and the Gram of every centred view on its smaller side
+template <typename T>
+void launch_gram(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const AdmmView& a = S.admm[i];
+  const unsigned nb = unsigned((a.side + ALS_GT - 1) / ALS_GT);
+  const T* X = static_cast<const T*>(vw.X[i]);
+  const T* mu = static_cast<const T*>(vw.mu[i]);
+  if (a.nside)
+    hipLaunchKernelGGL((k_als_gram<T, true>), dim3(nb, nb), dim3(256), 0, stream(c), X, mu, vw.ld[i], a.side, vw.p[i], a.G);
+  else
+    hipLaunchKernelGGL((k_als_gram<T, false>), dim3(nb, nb), dim3(256), 0, stream(c), X, mu, vw.ld[i], a.side, S.n, a.G);
+  CCZ_LAUNCH_CHECK();
+  mirror_upper(c, a.side, a.G, a.side);
+}
+
+void als_admm_setup(ccz_ctx* c, AlsState& S, const ccz_view* views, const void* const* means, double mu) {
+  if (S.rule != RULE_ADMM) fail(CCZ_EINVAL, "als: the fit state was not created with CCZ_ALS_ADMM");
+  if (!(mu > 0.0) || !std::isfinite(mu)) fail(CCZ_EINVAL, "als: mu must be positive and finite");
+  const AlsViews vw = make_views(S, views, means);
+  for (int i = 0; i < S.M; ++i) {
+    if (S.dtype == CCZ_F32) launch_gram<float>(c, S, vw, i);
+    else launch_gram<double>(c, S, vw, i);
+  }
+  S.mu = mu;
+  S.admm_ready = true;
 }
 
 void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
@@ -786,11 +1187,19 @@ int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host) {
   })
 }
 
+int ccz_als_admm_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, double mu) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
+    ccz::als_admm_setup(h, S, views, means_dev, mu);
+  })
+}
+
 int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_sweeps,
                    int64_t* sweeps_known, int* stopped_known) {
   CCZ_GUARD(h, {
     ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     if (!S.has_init) ccz::fail(CCZ_EINVAL, "als: ccz_als_set_init has not been called");
+    if (S.rule == ccz::RULE_ADMM && !S.admm_ready) ccz::fail(CCZ_EINVAL, "als: ccz_als_admm_setup has not been called");
     if (n_sweeps < 0 || n_sweeps > S.chunk) ccz::fail(CCZ_EINVAL, "als: n_sweeps must be 0..%lld", (long long)S.chunk);
     const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
     for (int i = 0; i < S.M; ++i) S.last_cs[i] = vw.cs[i];
@@ -840,11 +1249,18 @@ int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host
     for (int i = 0; i < view; ++i) off += S.p[i];
     const int64_t n = S.n, p = S.p[view];
     switch (what) {
+      case CCZ_ALS_PEEK_Z:      // z_i and w_i coincide between iterations
       case CCZ_ALS_PEEK_W: ccz::d2h(h, out_host, B.w + off, size_t(p) * 8); break;
       case CCZ_ALS_PEEK_RAW: ccz::d2h(h, out_host, B.raw + off, size_t(p) * 8); break;
       case CCZ_ALS_PEEK_TARGET: ccz::d2h(h, out_host, B.tt, size_t(n) * 8); break;
       case CCZ_ALS_PEEK_Q: ccz::d2h(h, out_host, B.Q + int64_t(view) * S.k * n, size_t(S.k) * n * 8); break;
       case CCZ_ALS_PEEK_LEVEL: ccz::d2h(h, out_host, B.thr + 2 * view, 16); break;
+      case CCZ_ALS_PEEK_ETA:
+      case CCZ_ALS_PEEK_LIPSCHITZ:
+        if (S.rule != ccz::RULE_ADMM) ccz::fail(CCZ_EINVAL, "als: buffer %d exists for CCZ_ALS_ADMM only", what);
+        if (what == CCZ_ALS_PEEK_ETA) ccz::d2h(h, out_host, B.eta + off, size_t(p) * 8);
+        else ccz::d2h(h, out_host, B.lip + view, 8);
+        break;
       case CCZ_ALS_PEEK_SCORE: {
         // the column-split partial sums, added in split order as the device adds them; the split count is that of the
         // last ccz_als_sweeps call

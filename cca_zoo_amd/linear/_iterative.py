@@ -1,8 +1,9 @@
-"""ALS models with deflation, run on the device: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span.
+"""ALS models with deflation, run on the device: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span, SCCA_ADMM.
 
 Reference: ``cca_zoo/linear/_iterative.py:38-158`` (the loop and the target score), ``:166-223`` (PLS_ALS),
 ``:231-380`` (SCCA_PMD and its bisection), ``:631-722`` (SCCA_Span), ``:839-930`` (ParkhomenkoCCA) and
-``cca_zoo/_utils/_linalg.py:76-116`` (soft threshold, deflation).  The four models share one sweep: for every view,
+``cca_zoo/_utils/_linalg.py:76-116`` (soft threshold, deflation); ``:388-514`` (SCCA_ADMM, whose iteration is described
+at the class).  The first four models share one sweep: for every view,
 ``t = normalise(sum_{j != i} X_j w_j)``, ``raw = X_i' t``, then the model's rule turns ``raw`` into ``w_i``.  Every sweep
 runs in libccz (``csrc/als.hip``); the host draws the initial vectors of all dimensions up front (they do not depend on
 results), uploads them and enqueues sweeps in chunks behind a device stop word.
@@ -30,7 +31,9 @@ CHUNK_SWEEPS = 8
 #: limits of the device path (``csrc/als.hip``)
 MAX_DIMS, MAX_VIEWS = 32, 8
 #: rule codes of ``ccz_als_create`` (``include/ccz.h``)
-RULE_NORMALISE, RULE_SOFT_FIXED, RULE_SOFT_L1, RULE_TOP_S = 0, 1, 2, 3
+RULE_NORMALISE, RULE_SOFT_FIXED, RULE_SOFT_L1, RULE_TOP_S, RULE_ADMM = 0, 1, 2, 3, 4
+#: SCCA_ADMM: the largest ``min(n, p_i)`` (the side of the Gram ``csrc/als.hip`` keeps per view)
+ADMM_MAX_SIDE = 16384
 
 
 def initial_vectors(random_state, p, k):
@@ -89,6 +92,12 @@ class _BaseIterative(BaseModel):
         """One number per view for the rule (``ccz_als_create``'s ``rule_param``)."""
         return [0.0] * len(p)
 
+    def _check_shapes(self, n, p) -> None:
+        """Limits of the model beyond those of the family (raises ``ValueError``)."""
+
+    def _setup_state(self, h, state, res) -> None:
+        """Model-specific calls between ``ccz_als_create`` and the first sweep."""
+
     def fit(self, views, y=None):
         from cca_zoo_amd import _dist
 
@@ -109,6 +118,7 @@ class _BaseIterative(BaseModel):
             raise ValueError(f"{m} views: the device path supports at most {MAX_VIEWS} views")
         if n < 1:
             raise ValueError("at least 1 sample is required")
+        self._check_shapes(n, p)
         self.n_views_, self.n_features_in_, self.n_samples_ = m, p, n
         par = self._rule_parameters(p)
         total = k * int(self.max_iter)
@@ -120,6 +130,7 @@ class _BaseIterative(BaseModel):
                                          (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter),
                                          chunk, C.byref(state)))
             try:
+                self._setup_state(h, state, res)
                 w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
                 h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
                 done = 0
@@ -282,3 +293,73 @@ class SCCA_Span(_BaseIterative):
             raise ValueError("span must not be negative")
         # span = 0 keeps every entry, as the reference's ``np.sort(np.abs(raw))[-0]`` (the smallest magnitude) does
         return [float(int(s)) if int(s) > 0 else float(pi) for s, pi in zip(span, p)]
+
+
+class SCCA_ADMM(_BaseIterative):
+    r"""Sparse CCA by ADMM (Suo et al. 2017), every iteration on the device.
+
+    Per iteration the targets $\bar s_{\neg i}$ of all views come from the vectors the iteration started with; then,
+    for each view,
+
+    $$
+    w' = w_i - \bigl(X_i^\top (X_i w_i - \bar s_{\neg i}) + \mu\,\eta_i\bigr) / L_i,\quad
+    z_i = \Pi_{\|\cdot\|_2 \le 1}\, S_{\tau_i/\mu}(w' + \eta_i),\quad \eta_i \leftarrow \eta_i + w' - z_i,\quad w_i = z_i
+    $$
+
+    with $L_i = \|X_i^\top X_i\|_F / n + \mu$ on the deflated view (reference:
+    ``cca_zoo/linear/_iterative.py:388-514``).  ``X_i' X_i`` is never formed: its product with ``w_i`` is two streaming
+    passes over the rows, and its Frobenius norm equals that of ``X_i X_i'``, so the device keeps the float64 Gram of the
+    centred view on its smaller side, ``min(n, p_i)`` squared, and deflates it with the scores of the finished
+    dimensions.
+
+    Differences from the reference, on purpose (besides those of the family):
+
+    - ``min(n, p_i) <= 16384`` for every view (the ceiling the kernel models use for an n x n matrix); wider and taller
+      views raise ``ValueError``.
+    - ``mu`` must be positive (the reference divides by it).
+    - float32 views: the reference multiplies ``X_i' X_i`` in float32 at the first dimension; here every product after
+      centring is float64 (README "Differences").
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        tau: L1 weight(s), per view. Default is 0.1.
+        mu: ADMM penalty, > 0. Default is 1.0.
+        max_iter: Maximum iterations per dimension. Default is 500.
+        tol: Convergence tolerance on the largest weight change of an iteration. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **_BaseIterative._parameter_constraints,
+        "tau": [Real, list],
+        "mu": [Interval(Real, 0, None, closed="neither")],
+    }
+    _rule = RULE_ADMM
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        tau: float | list[float] = 0.1,
+        mu: float = 1.0,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.tau = tau
+        self.mu = mu
+
+    def _rule_parameters(self, p):
+        return [float(t) for t in perview_parameter("tau", self.tau, 0.1, len(p))]
+
+    def _check_shapes(self, n, p):
+        for i, pi in enumerate(p):
+            if min(n, pi) > ADMM_MAX_SIDE:
+                raise ValueError(f"view {i} has min(n, p) = {min(n, pi)}: SCCA_ADMM keeps a min(n, p) x min(n, p) Gram per "
+                                 f"view and supports at most {ADMM_MAX_SIDE}")
+
+    def _setup_state(self, h, state, res):
+        h.check(h.lib.ccz_als_admm_setup(h.raw, state, res.varr, res.marr, float(self.mu)))

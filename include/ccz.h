@@ -463,7 +463,7 @@ CCZ_API int ccz_ey_status(ccz_handle h, void* state, int64_t* steps_done, int* s
 /* Copy the current weights (W blocks, float64) to the host.  Synchronises. */
 CCZ_API int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host);
 
-/* ---- ALS models with deflation: PLS_ALS / SCCA_PMD / ParkhomenkoCCA / SCCA_Span (csrc/als.hip) -------------------------
+/* ---- ALS models with deflation: PLS_ALS / SCCA_PMD / ParkhomenkoCCA / SCCA_Span / SCCA_ADMM (csrc/als.hip) -------------
  * Whole Gauss-Seidel sweeps on the device, no host wait inside a chunk of sweeps.  For every view i of a sweep:
  * t = normalise(sum_{j != i} X_j w_j), raw = X_i' t, w_i = rule(raw); after the sweep delta = max_i |w_i - w_i_old|_2 and
  * the dimension ends when delta < tol or after max_iter sweeps.  The views are never copied or written: the deflated view
@@ -478,6 +478,12 @@ CCZ_API int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host);
 #define CCZ_ALS_SOFT_FIXED 1
 #define CCZ_ALS_SOFT_L1 2
 #define CCZ_ALS_TOP_S 3
+/* SCCA_ADMM (cca_zoo/linear/_iterative.py:388-514), rule_param[i] = tau_i.  Its iteration is Jacobi in the scores: every
+ * view's target comes from the vectors the iteration started with.  Per view: w' = w_i - (X_d'(X_d w_i - t_i) + mu eta_i) /
+ * L_i, z_i = soft(w' + eta_i, tau_i / mu) over its norm when that exceeds 1, eta_i += w' - z_i, w_i = z_i, with
+ * L_i = |X_d' X_d|_F / n + mu taken at the first iteration of each dimension from the Gram of the centred view on its
+ * smaller side.  min(n_rows, p[i]) <= 16384 for every view; ccz_als_admm_setup must precede the first ccz_als_sweeps. */
+#define CCZ_ALS_ADMM 4
 
 /* Create a fit state: n_views (1..8) views of widths p[i] and n_rows rows, k (1..32) latent dimensions, the rule and its
  * per-view parameter (NULL for CCZ_ALS_NORMALISE), tol and max_iter per dimension as in the reference
@@ -491,6 +497,11 @@ CCZ_API int ccz_als_destroy(ccz_handle h, void* state);
 /* Upload the initial vectors of all dimensions (host, float64, k x sum p: dimension d's vectors of all views back to
  * back) and reset the fit (cca_zoo/linear/_iterative.py:80-89: the draws do not depend on results). */
 CCZ_API int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host);
+
+/* CCZ_ALS_ADMM only: set the penalty mu (> 0) and form, for every view, the float64 Gram of fl(X_i - mu_i) on its smaller
+ * side ((X - mu)(X - mu)' when n_rows <= p[i], else (X - mu)'(X - mu)) in the state.  views / means_dev as for
+ * ccz_als_sweeps, and the same rows must be passed there.  Asynchronous on the handle's stream. */
+CCZ_API int ccz_als_admm_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, double mu);
 
 /* Enqueue n_sweeps (<= chunk_sweeps) sweeps (cca_zoo/linear/_iterative.py:86-117).  Returns without waiting for the
  * device; the only host wait is for the chunk that used the same status slot two calls earlier, whose state is returned
@@ -521,6 +532,12 @@ CCZ_API int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int6
 #define CCZ_ALS_PEEK_TARGET 3
 #define CCZ_ALS_PEEK_Q 4
 #define CCZ_ALS_PEEK_LEVEL 5
+/* CCZ_ALS_ADMM: RAW holds w' of the view's last update and TARGET the n-vector (s_i - t_i) - Q_i Q_i' (s_i - t_i) of the
+ * last view updated; Z is z_i (p_i; it coincides with w_i between iterations), ETA the scaled dual eta_i (p_i), LIPSCHITZ
+ * L_i of the current dimension (1 number). */
+#define CCZ_ALS_PEEK_Z 6
+#define CCZ_ALS_PEEK_ETA 7
+#define CCZ_ALS_PEEK_LIPSCHITZ 8
 CCZ_API int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host);
 
 /* Copy the finished columns (W blocks as in ccz_ey_get_weights: view i's p_i x k row-major float64 weights, views back

@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Measure the ALS sweep on one GPU and print one JSON object (``--out`` also writes it).
 
-    python tools/als_probe.py [--out profiles/als_probe.json] [--only device|cpu] [--model PLS_ALS|SCCA_PMD] [--sweeps 20]
+    python tools/als_probe.py [--out profiles/als_probe.json] [--only device|cpu] [--model PLS_ALS|SCCA_PMD|SCCA_ADMM]
+                              [--sweeps 20]
 
-device: PLS_ALS and SCCA_PMD sweeps through the C ABI on n = 4096, 2 x 262144 float32 features drawn on the device
+device: PLS_ALS, SCCA_PMD and SCCA_ADMM sweeps through the C ABI on n = 4096, 2 x 262144 float32 features drawn on the device
         (ccz_randn_fill), k = 1, tol = 0, a fixed number of sweeps: ms per sweep between two stream synchronisations
         (the first, untimed call holds the scores of the initial vectors and the code-object loads), achieved bytes per
         second against the model 2 * sum_i n p_i 4 bytes per sweep, and PMD's extra time per sweep over PLS_ALS (the
-        price of its 12 extra passes over raw per view).  The per-kernel split comes from one
+        price of its 12 extra passes over raw per view).  SCCA_ADMM (tau = 0.1 / sqrt(p), mu = 1) also reports its one-off
+        setup, the two 4096 x 4096 float64 Grams of ccz_als_admm_setup, between two synchronisations (best of three), and
+        the time of a dimension's first iteration (which adds the Frobenius norm of the Gram) over a later one.  The
+        per-kernel split comes from one
         ``rocprofv3 --kernel-trace --stats`` run of ``--only device --model SCCA_PMD`` and one of ``--model PLS_ALS``,
         summarised by tools/rocpd_stats.py (profiles/als_kernel_stats.md); ``--kernel-stats MODEL=TABLE.md`` reads such a
         table back and adds the split of the sweep's kernel time (rule kernels, one-workgroup kernels) to the JSON.
@@ -36,7 +40,7 @@ def device(out, sweeps, models=("PLS_ALS", "SCCA_PMD")):
     import torch
 
     from cca_zoo_amd import _backend
-    from cca_zoo_amd.linear._iterative import RULE_NORMALISE, RULE_SOFT_L1, initial_vectors
+    from cca_zoo_amd.linear._iterative import RULE_ADMM, RULE_NORMALISE, RULE_SOFT_L1, initial_vectors
 
     h = _backend.default_handle()
     views = []
@@ -56,19 +60,30 @@ def device(out, sweeps, models=("PLS_ALS", "SCCA_PMD")):
     model_bytes = 2 * 2 * N * P * 4
     res = {}
     for name, rule, par in (("PLS_ALS", RULE_NORMALISE, [0.0, 0.0]),
-                            ("SCCA_PMD", RULE_SOFT_L1, [0.02 * np.sqrt(P)] * 2)):
+                            ("SCCA_PMD", RULE_SOFT_L1, [0.02 * np.sqrt(P)] * 2),
+                            ("SCCA_ADMM", RULE_ADMM, [0.1 / np.sqrt(P)] * 2)):
         if name not in models:
             continue
         state = C.c_void_p()
         h.check(h.lib.ccz_als_create(h.raw, _backend.F32, 2, (C.c_int64 * 2)(P, P), N, 1, rule, (C.c_double * 2)(*par), 0.0,
                                      10 ** 6, sweeps, C.byref(state)))
         try:
-            times = []
+            times, setup, first = [], [], []
+            for rep in range(3 if rule == RULE_ADMM else 0):
+                h.sync()
+                t0 = time.perf_counter()
+                h.check(h.lib.ccz_als_admm_setup(h.raw, state, varr, marr, 1.0))
+                h.sync()
+                setup.append(time.perf_counter() - t0)
             for rep in range(4):
                 h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
                 a, b = C.c_int64(0), C.c_int(0)
+                h.sync()
+                t0 = time.perf_counter()
                 h.check(h.lib.ccz_als_sweeps(h.raw, state, varr, marr, 1, C.byref(a), C.byref(b)))
                 h.sync()
+                if rep:
+                    first.append(time.perf_counter() - t0)
                 t0 = time.perf_counter()
                 h.check(h.lib.ccz_als_sweeps(h.raw, state, varr, marr, sweeps, C.byref(a), C.byref(b)))
                 h.sync()
@@ -80,16 +95,22 @@ def device(out, sweeps, models=("PLS_ALS", "SCCA_PMD")):
             res[name] = {"ms_per_sweep": round(ms, 4), "tb_per_s": round(model_bytes / (ms * 1e-3) / 1e12, 3),
                          "timed_runs_ms": [round(t / sweeps * 1e3, 4) for t in times],
                          "support_view0": int(np.count_nonzero(wv))}
+            if rule == RULE_ADMM:
+                res[name]["setup_grams_ms"] = round(min(setup) * 1e3, 2)
+                res[name]["setup_runs_ms"] = [round(t * 1e3, 2) for t in setup]
+                res[name]["first_iteration_ms"] = round(min(first) * 1e3, 4)
         finally:
             h.check(h.lib.ccz_als_destroy(h.raw, state))
     out["device"] = {
         "shape": {"n": N, "p": [P, P], "k": 1, "dtype": "float32", "sweeps": sweeps, "tol": 0.0},
         "model_bytes_per_sweep": model_bytes, **res,
     }
-    if len(res) == 2:
+    if "PLS_ALS" in res and "SCCA_PMD" in res:
         extra = res["SCCA_PMD"]["ms_per_sweep"] - res["PLS_ALS"]["ms_per_sweep"]
         out["device"]["pmd_extra_ms_per_sweep_over_pls"] = round(extra, 4)
         out["device"]["pmd_extra_fraction_of_sweep"] = round(extra / res["SCCA_PMD"]["ms_per_sweep"], 4)
+    if "PLS_ALS" in res and "SCCA_ADMM" in res:
+        out["device"]["admm_extra_ms_per_iteration_over_pls"] = round(res["SCCA_ADMM"]["ms_per_sweep"] - res["PLS_ALS"]["ms_per_sweep"], 4)
 
 
 def cpu(out, sweeps=2):
@@ -115,8 +136,9 @@ def cpu(out, sweeps=2):
     }
 
 
-RULE_KERNELS = ("k_als_fold", "k_als_levels", "k_als_norm", "k_als_apply")
-ONE_WORKGROUP_KERNELS = ("k_als_prologue", "k_als_finish", "k_als_advance")
+RULE_KERNELS = ("k_als_fold", "k_als_levels", "k_als_norm", "k_als_apply", "k_als_admm_fold", "k_als_admm_apply")
+ONE_WORKGROUP_KERNELS = ("k_als_prologue", "k_als_admm_prologue", "k_als_finish", "k_als_advance", "k_als_admm_h",
+                         "k_als_admm_lfinal")
 
 
 def kernel_split(out, spec):
@@ -145,12 +167,12 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--only", choices=["device", "cpu", "none"])
     ap.add_argument("--kernel-stats", action="append", default=[], metavar="MODEL=TABLE.md")
-    ap.add_argument("--model", choices=["PLS_ALS", "SCCA_PMD"], help="device part: this model alone (for a profiler run)")
+    ap.add_argument("--model", choices=["PLS_ALS", "SCCA_PMD", "SCCA_ADMM"], help="device part: this model alone (for a profiler run)")
     ap.add_argument("--sweeps", type=int, default=20)
     a = ap.parse_args()
     out = {}
     if a.only in (None, "device"):
-        device(out, a.sweeps, (a.model,) if a.model else ("PLS_ALS", "SCCA_PMD"))
+        device(out, a.sweeps, (a.model,) if a.model else ("PLS_ALS", "SCCA_PMD", "SCCA_ADMM"))
     if a.only in (None, "cpu"):
         cpu(out)
     for spec in a.kernel_stats:
