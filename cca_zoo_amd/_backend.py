@@ -140,6 +140,15 @@ SIGNATURES = {
     "ccz_als_colmeans": (_int, [_vp, _int, C.POINTER(View), _i64, _vp]),
     "ccz_als_peek": (_int, [_vp, _vp, _int, _int, _pdbl]),
     "ccz_als_get_weights": (_int, [_vp, _vp, _pdbl]),
+    "ccz_gfa_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _dbl, _i64, _int, _i64, C.POINTER(_vp)]),
+    "ccz_gfa_destroy": (_int, [_vp, _vp]),
+    "ccz_gfa_set_init": (_int, [_vp, _vp, _pdbl]),
+    "ccz_gfa_setup": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp)]),
+    "ccz_gfa_iterations": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pint]),
+    "ccz_gfa_status": (_int, [_vp, _vp, _pi64, _pint, _pint, _pint, _pdbl, _pint, _pi64, _pint]),
+    "ccz_gfa_peek": (_int, [_vp, _vp, _int, _int, _pdbl]),
+    "ccz_gfa_get_result": (_int, [_vp, _vp, _pint, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
+    "ccz_gfa_sumsq": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
 }
 
 

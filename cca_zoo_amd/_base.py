@@ -100,6 +100,11 @@ class BaseModel(BaseEstimator, ABC):
                 out.append(z)
         return out
 
+    def _variates(self, views) -> list:
+        """The per-view variates that the correlations compare: ``transform``, unless a model's ``transform`` returns
+        something else (GFA's is the one shared latent variable)."""
+        return self.transform(views)
+
     def fit_transform(self, views, y=None) -> list:
         return self.fit(views, y).transform(views)
 
@@ -118,7 +123,7 @@ class BaseModel(BaseEstimator, ABC):
         from cca_zoo_amd import _backend
         from cca_zoo_amd._moments import compute_moments
 
-        zs = self.transform(views)
+        zs = self._variates(views)
         m, k = len(zs), int(zs[0].shape[1])
         h = _backend.handle_for(zs)
         mom, keep, n, _, _ = compute_moments(zs, h)

@@ -544,6 +544,74 @@ CCZ_API int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* 
  * to back; unfinished columns are zero) to the host (cca_zoo/linear/_iterative.py:91-92).  Synchronises. */
 CCZ_API int ccz_als_get_weights(ccz_handle h, void* state, double* W_host);
 
+/* ---- GFA: group factor analysis, Bayesian CCA with per-view ARD (csrc/gfa.hip) -----------------------------------------
+ * Whole coordinate-ascent iterations of mean-field variational Bayes on the device, no host wait inside a chunk of
+ * iterations.  One iteration, in the reference's order: per view cov_w, w = (X'z) cov_w tau, ww = w'w + p cov_w; cov_z =
+ * inv(I + sum tau ww); z = (sum tau X w) cov_z, zz = z'z + n cov_z; alpha, tau; columns whose mean z^2 is at most 1e-7 are
+ * dropped (drop_k, when some but not all are kept; the kept ones stay in order); the fit stops after 1000 consecutive
+ * iterations without a prune whose relative change of z stayed below tol, or after max_iter.  Views, means_dev, rounding
+ * (x - mu in the views' precision, everything after it float64) as for ccz_als_sweeps.  k x k results are packed to the
+ * ACTIVE k (k_active of ccz_gfa_status), row-major.
+ * cca_zoo/probabilistic/_gfa.py:184-204 (initialisation), :217-286 (iteration) */
+
+/* Create a fit state: n_views (1..8) views of widths p[i] and n_rows (>= 2) rows, k (1..32) latent dimensions at the start,
+ * up to chunk_iters iterations per ccz_gfa_iterations call. */
+CCZ_API int ccz_gfa_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t n_rows, int64_t k, double tol,
+                           int64_t max_iter, int drop_k, int64_t chunk_iters, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op. */
+CCZ_API int ccz_gfa_destroy(ccz_handle h, void* state);
+
+/* Upload the initial z (host, float64, n_rows x k row-major: default_rng(random_state).standard_normal((n, k)),
+ * cca_zoo/probabilistic/_gfa.py:184).  Must precede every ccz_gfa_setup. */
+CCZ_API int ccz_gfa_set_init(ccz_handle h, void* state, const double* z0_host);
+
+/* One pass per view: y_const = sum fl(x - mu)^2 and datavar = the sum of the ddof = 1 column variances of fl(x - mu)
+ * (re-centred by the float64 column mean, as np.var does), then the initial alpha, tau = 1e3, cov_z = cov_w = I, w = 0, ww,
+ * zz, and the status word.  Asynchronous on the handle's stream; the same rows must be passed to ccz_gfa_iterations. */
+CCZ_API int ccz_gfa_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev);
+
+/* Enqueue n_iters (<= chunk_iters) iterations.  Returns without waiting for the device; the only host wait is for the
+ * chunk that used the same status slot two calls earlier, whose state is returned in iters_known / stopped_known (-1 / 0
+ * when there is none yet).  Iterations after the stop are no-ops. */
+CCZ_API int ccz_gfa_iterations(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_iters,
+                               int64_t* iters_known, int* stopped_known);
+
+/* Iterations done, whether the fit has stopped, the active k, the stable counter, the last relative change of z, and the
+ * prunes so far: their number and, per prune (k entries suffice), the 1-based iteration and the active k after it.
+ * Synchronises. */
+CCZ_API int ccz_gfa_status(ccz_handle h, void* state, int64_t* iters, int* stopped, int* k_active, int* stable, double* rel_change,
+                           int* n_prunes, int64_t* prune_iters, int* prune_k);
+
+/* Copy one quantity to the host (float64, packed to the active k) -- what the kernel tests compare with NumPy term by term:
+ * z (n x k), view's w (p x k), XW = (X - mu) w (n x k), cov_z, view's cov_w, ww, zz (k x k), view's alpha, b_ard (k), tau,
+ * b_tau (n_views each), SETUP: view's y_const and datavar (2).  Synchronises. */
+#define CCZ_GFA_PEEK_Z 0
+#define CCZ_GFA_PEEK_W 1
+#define CCZ_GFA_PEEK_XW 2
+#define CCZ_GFA_PEEK_COV_Z 3
+#define CCZ_GFA_PEEK_COV_W 4
+#define CCZ_GFA_PEEK_WW 5
+#define CCZ_GFA_PEEK_ZZ 6
+#define CCZ_GFA_PEEK_ALPHA 7
+#define CCZ_GFA_PEEK_TAU 8
+#define CCZ_GFA_PEEK_B_TAU 9
+#define CCZ_GFA_PEEK_B_ARD 10
+#define CCZ_GFA_PEEK_SETUP 11
+CCZ_API int ccz_gfa_peek(ccz_handle h, void* state, int what, int view, double* out_host);
+
+/* Everything the posterior draws need (cca_zoo/probabilistic/_gfa.py:301-352), packed to the active k written to
+ * *k_active: z (n x k), cov_z (k x k), w of all views back to back (sum p x k), cov_w (n_views x k x k), alpha and b_ard
+ * (n_views x k), tau and b_tau (n_views).  Size the outputs for the k of ccz_gfa_status or of ccz_gfa_create; NULL outputs
+ * are skipped.  Synchronises. */
+CCZ_API int ccz_gfa_get_result(ccz_handle h, void* state, int* k_active, double* z_host, double* cov_z_host, double* w_host,
+                               double* cov_w_host, double* alpha_host, double* b_ard_host, double* tau_host, double* b_tau_host);
+
+/* *sumsq_host = sum over all entries of fl(x - mean)^2 of one view of DEVICE rows, in float64 (mean_dev: the view's dtype,
+ * NULL for none): the setup pass alone, for the marginal log-likelihood (cca_zoo/probabilistic/_utils.py:102-103 with a
+ * noise variance that is constant within a view).  Synchronises. */
+CCZ_API int ccz_gfa_sumsq(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev, double* sumsq_host);
+
 #ifdef __cplusplus
 }
 #endif
