@@ -1,8 +1,10 @@
-"""Views kept in HBM for the length of an iterative fit (:class:`ResidentViews`: the EY and the ALS models), and the
-coercion, dtype probes and stream bracket that the kernel models share with it."""
+"""Views kept in HBM for the length of an iterative fit (:class:`ResidentViews`: the EY, ALS / ADMM and GFA models), the
+host side of such a fit (its refusals, the fit state's bracket, the chunk loop), and the coercion, dtype probes and stream
+bracket that the kernel models share with it."""
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -49,6 +51,44 @@ def acquire(h, views):
 def release(h, sp):
     if sp is not None:
         h.release(sp)
+
+
+def refuse_row_sharded(why):
+    """Raise inside ``row_sharded()``; ``why`` names the model and what keeps it from sharding by rows."""
+    from cca_zoo_amd import _dist
+
+    if _dist.is_sharded():
+        raise NotImplementedError(f"{why}: fit it outside row_sharded()")
+
+
+def check_limits(k, m, max_dims, max_views):
+    if k > max_dims:
+        raise ValueError(f"latent_dimensions={k}: the device path supports at most {max_dims}")
+    if m > max_views:
+        raise ValueError(f"{m} views: the device path supports at most {max_views} views")
+
+
+@contextlib.contextmanager
+def fit_state(h, family, *args):
+    """The fit state of ``family`` ("ey", "als", "gfa") for the length of a ``with`` block: ``ccz_<family>_create(handle,
+    *args, &state)`` makes it (a refused create raises and leaves nothing behind), ``ccz_<family>_destroy`` frees it on
+    every path."""
+    state = C.c_void_p()
+    h.check(getattr(h.lib, f"ccz_{family}_create")(h.raw, *args, C.byref(state)))
+    try:
+        yield state
+    finally:
+        getattr(h.lib, f"ccz_{family}_destroy")(h.raw, state)
+
+
+def run_chunks(total, chunk, call):
+    """Enqueue ``total`` steps in chunks of at most ``chunk``.  ``call(step)`` enqueues one chunk and returns the stop flag
+    it was told (that of the chunk two calls back); no chunk follows a reported stop."""
+    done, stopped = 0, False
+    while done < total and not stopped:
+        step = min(chunk, total - done)
+        stopped = bool(call(step))
+        done += step
 
 
 class ResidentViews:

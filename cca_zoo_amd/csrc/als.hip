@@ -52,6 +52,7 @@
 #include "hip_common.h"
 #include "abi_guard.h"
 #include "fit_driver.h"
+#include "reduce.h"
 #include "row_load.h"
 
 namespace ccz {
@@ -130,40 +131,6 @@ struct AlsBuf {
   int64_t ptot, pmax;
 };
 
-// deterministic sums / maxima over a wave and over a workgroup of NW waves (every thread gets the result)
-__device__ __forceinline__ double als_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double als_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-template <int NW>
-__device__ __forceinline__ double als_block_sum(double v, double* sh) {
-  v = als_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += sh[w];
-  return t;
-}
-template <int NW>
-__device__ __forceinline__ double als_block_max(double v, double* sh) {
-  v = als_wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = sh[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) t = fmax(t, sh[w]);
-  return t;
-}
-
 __device__ __forceinline__ double als_soft(double x, double t) {
   const double a = fabs(x) - t;
   return a > 0.0 ? copysign(a, x) : 0.0;
@@ -180,10 +147,8 @@ __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, cons
   if (first_only && st->sweep != 0) return;
   __shared__ double sh[4];
   const int r0 = blockIdx.x * ALS_SROWS;
-  const int cs = gridDim.y;
-  // column range of this split, in units of 4 columns so that every split starts on a whole line
-  const int64_t units = (p + 3) / 4, per = (units + cs - 1) / cs;
-  const int64_t c0 = 4 * per * blockIdx.y, c1 = c0 + 4 * per < p ? c0 + 4 * per : p;
+  int64_t c0, c1;
+  split_range(p, gridDim.y, blockIdx.y, &c0, &c1);
   const bool vec = vec_ok(X, ld, mu);
   const bool wvec = reinterpret_cast<uintptr_t>(w) % 16 == 0;
   double acc[ALS_SROWS] = {0.0, 0.0, 0.0, 0.0};
@@ -211,7 +176,7 @@ __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, cons
   }
 #pragma unroll
   for (int t = 0; t < ALS_SROWS; ++t) {
-    const double s = als_block_sum<4>(acc[t], sh);
+    const double s = block_sum<4>(acc[t], sh);
     if (threadIdx.x == 0 && live[t]) spart[int64_t(blockIdx.y) * n + r0 + t] = s;
   }
 }
@@ -232,7 +197,7 @@ __device__ void als_corrected_score(const AlsBuf& B, const AlsViews& vw, int j, 
       for (int c = 0; c < cs; ++c) s += sp[int64_t(c) * n + r];
       acc += Q[int64_t(a) * n + r] * s;
     }
-    const double c = als_block_sum<ALS_PT / 64>(acc, sh);
+    const double c = block_sum<ALS_PT / 64>(acc, sh);
     if (threadIdx.x == 0) coef[a] = c;
   }
   __syncthreads();
@@ -262,7 +227,7 @@ __device__ void als_target(const AlsBuf& B, const AlsViews& vw, int i, int d, do
   }
   double acc = 0.0;
   for (int r = threadIdx.x; r < n; r += ALS_PT) acc += B.tt[r] * B.tt[r];
-  const double nrm = sqrt(als_block_sum<ALS_PT / 64>(acc, sh));
+  const double nrm = sqrt(block_sum<ALS_PT / 64>(acc, sh));
   if (nrm > 1e-12)
     for (int r = threadIdx.x; r < n; r += ALS_PT) B.tt[r] /= nrm;     // every thread rereads only its own rows afterwards
 }
@@ -274,7 +239,7 @@ __device__ void als_correct_target(const AlsBuf& B, int i, int d, double* coef, 
   for (int a = 0; a < d; ++a) {
     double q = 0.0;
     for (int r = threadIdx.x; r < n; r += ALS_PT) q += Q[int64_t(a) * n + r] * B.tt[r];
-    const double c = als_block_sum<ALS_PT / 64>(q, sh);
+    const double c = block_sum<ALS_PT / 64>(q, sh);
     if (threadIdx.x == 0) coef[a] = c;
   }
   __syncthreads();
@@ -320,7 +285,7 @@ __global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, do
   const int n = B.n, d = st->dim;
   double delta = 0.0;
   for (int i = 0; i < B.M; ++i) {
-    const double s = als_block_sum<ALS_PT / 64>(int(threadIdx.x) < vw.ng[i] ? B.dpart[i * ALS_MAXG + threadIdx.x] : 0.0, sh);
+    const double s = block_sum<ALS_PT / 64>(int(threadIdx.x) < vw.ng[i] ? B.dpart[i * ALS_MAXG + threadIdx.x] : 0.0, sh);
     const double di = sqrt(s);
     if (di > delta) delta = di;             // Python's max(): a NaN after the first entry never wins ...
     if (i == 0 && di != di) delta = di;     // ... and a NaN first entry always does
@@ -342,7 +307,7 @@ __global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, do
     als_corrected_score(B, vw, i, d, q, false, coef, sh);
     double acc = 0.0;
     for (int r = threadIdx.x; r < n; r += ALS_PT) acc += q[r] * q[r];
-    const double ns = als_block_sum<ALS_PT / 64>(acc, sh);
+    const double ns = block_sum<ALS_PT / 64>(acc, sh);
     const double nrm = sqrt(ns);
     for (int r = threadIdx.x; r < n; r += ALS_PT) q[r] = ns > 1e-12 ? q[r] / nrm : 0.0;
     __syncthreads();
@@ -408,9 +373,9 @@ __global__ void __launch_bounds__(256) k_als_fold(const double* __restrict__ xpa
     const double u = rule == RULE_SOFT_FIXED ? als_soft(v, par) : v;
     ss += u * u;
   }
-  l1 = als_block_sum<4>(l1, sh);
-  mx = als_block_max<4>(mx, sh);
-  ss = als_block_sum<4>(ss, sh);
+  l1 = block_sum<4>(l1, sh);
+  mx = block_max<4>(mx, sh);
+  ss = block_sum<4>(ss, sh);
   if (threadIdx.x == 0) {
     fstat[3 * blockIdx.x + 0] = l1;
     fstat[3 * blockIdx.x + 1] = mx;
@@ -422,9 +387,9 @@ __global__ void __launch_bounds__(256) k_als_fold(const double* __restrict__ xpa
 // partial per thread, wave butterflies, waves in index order); every thread gets the result
 __device__ __forceinline__ void als_fold_totals(const double* fstat, int ng, double* l1, double* mx, double* ss, double* sh) {
   const int t = threadIdx.x;
-  *l1 = als_block_sum<4>(t < ng ? fstat[3 * t + 0] : 0.0, sh);
-  *mx = als_block_max<4>(t < ng ? fstat[3 * t + 1] : 0.0, sh);
-  *ss = als_block_sum<4>(t < ng ? fstat[3 * t + 2] : 0.0, sh);
+  *l1 = block_sum<4>(t < ng ? fstat[3 * t + 0] : 0.0, sh);
+  *mx = block_max<4>(t < ng ? fstat[3 * t + 1] : 0.0, sh);
+  *ss = block_sum<4>(t < ng ? fstat[3 * t + 2] : 0.0, sh);
 }
 
 // the sums of the previous level pass's partials over the workgroups in index order: thread c < 31 owns candidate c
@@ -535,7 +500,7 @@ __global__ void __launch_bounds__(256) k_als_levels(const double* __restrict__ r
   }
 #pragma unroll
   for (int c = 0; c < ALS_NC; ++c) {
-    const double s = als_wave_sum(acc[c]);
+    const double s = wave_sum(acc[c]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s;
   }
   __syncthreads();
@@ -581,7 +546,7 @@ __global__ void __launch_bounds__(256) k_als_norm(const double* __restrict__ raw
     const double u = rule == RULE_SOFT_L1 ? als_soft(v, lv) : (fabs(v) >= lv ? v : 0.0);
     ss += u * u;
   }
-  ss = als_block_sum<4>(ss, sh);
+  ss = block_sum<4>(ss, sh);
   if (threadIdx.x == 0) nstat[blockIdx.x] = ss;
 }
 
@@ -600,7 +565,7 @@ __global__ void __launch_bounds__(256) k_als_apply(const double* __restrict__ ra
   double lv = 0.0;
   if (thresholded) {                     // uniform over the workgroup
     lv = thr[0];
-    ss = als_block_sum<4>(int(threadIdx.x) < ng ? nstat[threadIdx.x] : 0.0, sh);
+    ss = block_sum<4>(int(threadIdx.x) < ng ? nstat[threadIdx.x] : 0.0, sh);
   } else if (rule == RULE_SOFT_FIXED) {
     lv = par;
   }
@@ -617,7 +582,7 @@ __global__ void __launch_bounds__(256) k_als_apply(const double* __restrict__ ra
     dd += diff * diff;
     w[f] = u;
   }
-  dd = als_block_sum<4>(dd, sh);
+  dd = block_sum<4>(dd, sh);
   if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
 }
 
@@ -642,7 +607,7 @@ __global__ void __launch_bounds__(256) k_als_admm_fold(const double* __restrict_
     const double u = als_soft(wp + e, thr);
     ss += u * u;
   }
-  ss = als_block_sum<4>(ss, sh);
+  ss = block_sum<4>(ss, sh);
   if (threadIdx.x == 0) fstat[3 * blockIdx.x + 2] = ss;
 }
 
@@ -654,7 +619,7 @@ __global__ void __launch_bounds__(256) k_als_admm_apply(const double* __restrict
   if (fit_stopped(st)) return;
   __shared__ double sh[4];
   const bool first = st->sweep == 0;
-  const double nrm = sqrt(als_block_sum<4>(int(threadIdx.x) < ng ? fstat[3 * threadIdx.x + 2] : 0.0, sh));
+  const double nrm = sqrt(block_sum<4>(int(threadIdx.x) < ng ? fstat[3 * threadIdx.x + 2] : 0.0, sh));
   double dd = 0.0;
   for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
     const double e = first ? 0.0 : eta[f], wp = raw[f];
@@ -665,7 +630,7 @@ __global__ void __launch_bounds__(256) k_als_admm_apply(const double* __restrict
     dd += diff * diff;
     w[f] = z;
   }
-  dd = als_block_sum<4>(dd, sh);
+  dd = block_sum<4>(dd, sh);
   if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
 }
 
@@ -685,7 +650,7 @@ __global__ void __launch_bounds__(256) k_als_admm_kq(const double* __restrict__ 
   const double* q = Q + int64_t(a) * n;
   double s = 0.0;
   for (int c = threadIdx.x & 63; c < n; c += 64) s += K[int64_t(r) * n + c] * q[c];
-  s = als_wave_sum(s);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) KQ[int64_t(a) * n + r] = s;
 }
 
@@ -700,7 +665,7 @@ __global__ void __launch_bounds__(ALS_PT) k_als_admm_h(int n, const double* __re
     for (int b = 0; b < d; ++b) {
       double acc = 0.0;
       for (int r = threadIdx.x; r < n; r += ALS_PT) acc += Q[int64_t(a) * n + r] * KQ[int64_t(b) * n + r];
-      const double c = als_block_sum<ALS_PT / 64>(acc, sh);
+      const double c = block_sum<ALS_PT / 64>(acc, sh);
       if (threadIdx.x == 0) Cm[a * ALS_MAXK + b] = c;
     }
   __syncthreads();
@@ -767,7 +732,7 @@ __global__ void __launch_bounds__(256) k_als_admm_gnorm(const double* __restrict
       acc += v * v;
     }
   }
-  acc = als_block_sum<4>(acc, sh);
+  acc = block_sum<4>(acc, sh);
   if (threadIdx.x == 0) gpart[blockIdx.x] = acc;
 }
 
@@ -776,7 +741,7 @@ __global__ void __launch_bounds__(256) k_als_admm_lfinal(const double* __restric
                                                         double* __restrict__ lip, const AlsStatus* st) {
   if (admm_not_first(st)) return;
   __shared__ double sh[4];
-  const double s = als_block_sum<4>(int(threadIdx.x) < ng ? gpart[threadIdx.x] : 0.0, sh);
+  const double s = block_sum<4>(int(threadIdx.x) < ng ? gpart[threadIdx.x] : 0.0, sh);
   if (threadIdx.x == 0) *lip = sqrt(s) / double(n) + mu;
 }
 
@@ -867,38 +832,29 @@ __global__ void __launch_bounds__(256) k_als_colmeans(const T* __restrict__ X, i
 }
 
 // ---- host driver ----------------------------------------------------------------------------------------------------
-struct AlsState {
-  int dtype, M, rule, max_iter;
-  int64_t n, k, chunk;
+struct AlsState : FitState<AlsStatus> {
+  int rule, max_iter;
+  int64_t n, k;
   double tol;
-  std::vector<int64_t> p;
   std::vector<double> par;
   AlsBuf B;
-  ChunkDriver<AlsStatus> drv;
   bool has_init = false;
   double mu = 0.0;                 // SCCA_ADMM: the penalty, and what ccz_als_admm_setup left per view
   bool admm_ready = false;
   AdmmView admm[ALS_MAXV] = {};
   int last_cs[ALS_MAXV] = {};
-  std::vector<void*> allocs;
 };
 
 AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const* means) {
-  check_views("als", views, S.p);
   AlsViews vw;
   memset(&vw, 0, sizeof(vw));
+  fill_views("als", vw, views, means, S.p);
   int64_t off = 0;
   for (int i = 0; i < S.M; ++i) {
-    vw.X[i] = views[i].data;
-    vw.mu[i] = means ? means[i] : nullptr;
-    vw.ld[i] = views[i].ld;
     vw.p[i] = S.p[i];
     vw.off[i] = off;
     off += S.p[i];
-    // enough score workgroups to fill the device when there are few rows; every split at least 4096 columns wide
-    const int64_t rowgroups = (S.n + ALS_SROWS - 1) / ALS_SROWS;
-    int64_t cs = std::min<int64_t>((2048 + rowgroups - 1) / rowgroups, std::max<int64_t>(1, S.p[i] / 4096));
-    vw.cs[i] = int(std::max<int64_t>(1, std::min<int64_t>(cs, S.B.csmax)));
+    vw.cs[i] = column_splits(S.n, ALS_SROWS, S.p[i], S.B.csmax);
     vw.ng[i] = int(std::max<int64_t>(1, std::min<int64_t>(ALS_MAXG, (S.p[i] + 2047) / 2048)));
     vw.par[i] = S.par[i];
     vw.rule[i] = (S.rule == RULE_TOP_S && S.par[i] >= double(S.p[i])) ? int(RULE_NORMALISE) : S.rule;
@@ -906,19 +862,23 @@ AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const*
   return vw;
 }
 
-template <typename T>
 void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
   const dim3 grid(unsigned((S.n + ALS_SROWS - 1) / ALS_SROWS), unsigned(vw.cs[i]));
-  hipLaunchKernelGGL((k_als_score<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                     vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.drv.dev);
+  by_dtype(S.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_score<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
+                       vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.drv.dev);
+  });
   CCZ_LAUNCH_CHECK();
 }
 
-template <typename T>
 void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const dim3 grid(unsigned((vw.p[i] + ALS_STRIP - 1) / ALS_STRIP), unsigned(S.B.nchunk));
-  hipLaunchKernelGGL((k_als_xt<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                     vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.drv.dev);
+  by_dtype(S.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_xt<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
+                       vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.drv.dev);
+  });
   CCZ_LAUNCH_CHECK();
 }
 
@@ -951,16 +911,6 @@ void launch_prologue(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   CCZ_LAUNCH_CHECK();
 }
 
-void score_any(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
-  if (S.dtype == CCZ_F32) launch_score<float>(c, S, vw, i, first_only);
-  else launch_score<double>(c, S, vw, i, first_only);
-}
-
-void xt_any(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
-  if (S.dtype == CCZ_F32) launch_xt<float>(c, S, vw, i);
-  else launch_xt<double>(c, S, vw, i);
-}
-
 // SCCA_ADMM: L_i at the first iteration of a dimension (the four kernels return at once otherwise)
 void launch_admm_lipschitz(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const AlsBuf& B = S.B;
@@ -973,12 +923,11 @@ void launch_admm_lipschitz(ccz_ctx* c, const AlsState& S, const AlsViews& vw, in
     CCZ_LAUNCH_CHECK();
   } else if (S.k > 1) {
     const dim3 grid(unsigned((vw.p[i] + 255) / 256), unsigned(B.nchunk));
-    if (S.dtype == CCZ_F32)
-      hipLaunchKernelGGL((k_als_admm_xtq<float>), grid, dim3(256), 0, stream(c), static_cast<const float*>(vw.X[i]),
-                         static_cast<const float*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
-    else
-      hipLaunchKernelGGL((k_als_admm_xtq<double>), grid, dim3(256), 0, stream(c), static_cast<const double*>(vw.X[i]),
-                         static_cast<const double*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
+    by_dtype(S.dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_als_admm_xtq<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]),
+                         static_cast<const T*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
+    });
     CCZ_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_als_admm_afold, dim3(grid.x), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], a.U, S.drv.dev);
     CCZ_LAUNCH_CHECK();
@@ -1002,12 +951,12 @@ void finish_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
 // scored only after the last update
 void enqueue_admm_iteration(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
   const AlsBuf& B = S.B;
-  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 1);
+  for (int i = 0; i < S.M; ++i) launch_score(c, S, vw, i, 1);
   for (int i = 0; i < S.M; ++i) {
     launch_admm_lipschitz(c, S, vw, i);
     hipLaunchKernelGGL(k_als_admm_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), B, vw, i, S.drv.dev);
     CCZ_LAUNCH_CHECK();
-    xt_any(c, S, vw, i);
+    launch_xt(c, S, vw, i);
     const int ng = vw.ng[i];
     const double thr = vw.par[i] / S.mu;
     double* fstat = B.fstat + size_t(i) * ALS_MAXG * 3;
@@ -1018,103 +967,82 @@ void enqueue_admm_iteration(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
                        B.eta + vw.off[i], B.dpart + size_t(i) * ALS_MAXG, S.drv.dev);
     CCZ_LAUNCH_CHECK();
   }
-  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 0);
+  for (int i = 0; i < S.M; ++i) launch_score(c, S, vw, i, 0);
   finish_sweep(c, S, vw);
 }
 
 void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
   if (S.rule == RULE_ADMM) return enqueue_admm_iteration(c, S, vw);
-  for (int i = 0; i < S.M; ++i) score_any(c, S, vw, i, 1);
+  for (int i = 0; i < S.M; ++i) launch_score(c, S, vw, i, 1);
   for (int i = 0; i < S.M; ++i) {
     launch_prologue(c, S, vw, i);
-    xt_any(c, S, vw, i);
+    launch_xt(c, S, vw, i);
     launch_rule(c, S, vw, i);
-    score_any(c, S, vw, i, 0);
+    launch_score(c, S, vw, i, 0);
   }
   finish_sweep(c, S, vw);
 }
 
-void als_free(ccz_ctx* c, AlsState* S) {
-  sync(c);
-  for (void* a : S->allocs) dev_free(c, a);
-  S->drv.destroy(c);
-  delete S;
-}
-
 AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, int64_t k, int rule, const double* par, double tol,
                      int64_t max_iter, int64_t chunk) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "als: dtype must be CCZ_F32 or CCZ_F64");
-  if (M < 1 || M > ALS_MAXV) fail(CCZ_EUNSUP, "als: 1 to %d views are supported, got %d", ALS_MAXV, M);
+  check_dtype("als", dtype);
+  check_view_count("als", M, ALS_MAXV);
   if (k < 1 || k > ALS_MAXK) fail(CCZ_EUNSUP, "als: 1 to %d latent dimensions are supported, got %lld", ALS_MAXK, (long long)k);
   if (!p || n < 1 || n > (int64_t(1) << 30) || max_iter < 1 || max_iter > (int64_t(1) << 30) || chunk < 1 || !(tol >= 0.0))
     fail(CCZ_EINVAL, "als: bad argument");
   if (rule < RULE_NORMALISE || rule > RULE_ADMM) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
   if (rule != RULE_NORMALISE && !par) fail(CCZ_EINVAL, "als: the rule needs one parameter per view");
-  AlsState* S = new AlsState();
-  S->dtype = dtype; S->M = M; S->rule = rule; S->max_iter = int(max_iter);
-  S->n = n; S->k = k; S->chunk = chunk; S->tol = tol;
-  AlsBuf& B = S->B;
-  memset(&B, 0, sizeof(B));
-  B.n = int(n); B.M = M; B.k = int(k);
-  for (int i = 0; i < M; ++i) {
-    if (p[i] < 1) { delete S; fail(CCZ_EINVAL, "als: view %d has no columns", i); }
-    if (rule == RULE_ADMM && std::min(n, p[i]) > ALS_ADMM_MAXSIDE) {
-      delete S;
-      fail(CCZ_EUNSUP, "als: ADMM keeps a min(n, p) x min(n, p) Gram per view; view %d has min(n, p) = %lld > %d", i,
-           (long long)std::min(n, p[i]), ALS_ADMM_MAXSIDE);
+  check_no_empty_view("als", M, p);
+  return new_state<AlsState>(c, [&](AlsState& S) {
+    S.dtype = dtype; S.M = M; S.rule = rule; S.max_iter = int(max_iter);
+    S.n = n; S.k = k; S.chunk = chunk; S.tol = tol;
+    AlsBuf& B = S.B;
+    memset(&B, 0, sizeof(B));
+    B.n = int(n); B.M = M; B.k = int(k);
+    for (int i = 0; i < M; ++i) {
+      if (rule == RULE_ADMM && std::min(n, p[i]) > ALS_ADMM_MAXSIDE)
+        fail(CCZ_EUNSUP, "als: ADMM keeps a min(n, p) x min(n, p) Gram per view; view %d has min(n, p) = %lld > %d", i,
+             (long long)std::min(n, p[i]), ALS_ADMM_MAXSIDE);
+      const double q = par ? par[i] : 0.0;
+      if (rule == RULE_TOP_S && !(q >= 1.0)) fail(CCZ_EINVAL, "als: top-s needs s >= 1 (view %d)", i);
+      if (rule != RULE_NORMALISE && !(q == q)) fail(CCZ_EINVAL, "als: the parameter of view %d is NaN", i);
+      S.p.push_back(p[i]);
+      S.par.push_back(q);
+      B.ptot += p[i];
+      B.pmax = std::max(B.pmax, p[i]);
     }
-    const double q = par ? par[i] : 0.0;
-    if (rule == RULE_TOP_S && !(q >= 1.0)) { delete S; fail(CCZ_EINVAL, "als: top-s needs s >= 1 (view %d)", i); }
-    if (rule != RULE_NORMALISE && !(q == q)) { delete S; fail(CCZ_EINVAL, "als: the parameter of view %d is NaN", i); }
-    S->p.push_back(p[i]);
-    S->par.push_back(q);
-    B.ptot += p[i];
-    B.pmax = std::max(B.pmax, p[i]);
-  }
-  B.csmax = 16;
-  B.nchunk = int(std::min<int64_t>(64, (n + 63) / 64));
-  B.rc = int((n + B.nchunk - 1) / B.nchunk);
-  B.nchunk = int((n + B.rc - 1) / B.rc);
-  try {
-    auto get = [&](size_t doubles) {
-      void* a = dev_alloc(c, std::max<size_t>(doubles, 1) * 8);
-      S->allocs.push_back(a);
-      return static_cast<double*>(a);
-    };
-    B.w = get(size_t(B.ptot));
-    B.raw = get(size_t(B.ptot));
-    B.init = get(size_t(B.ptot) * k);
-    B.Wout = get(size_t(B.ptot) * k);
-    B.spart = get(size_t(M) * B.csmax * n);
-    B.Q = get(size_t(M) * k * n);
-    B.tt = get(size_t(n));
-    B.xpart = get(size_t(B.nchunk) * B.pmax);
-    B.fstat = get(size_t(M) * ALS_MAXG * 3);
-    B.lpart = get(size_t(2) * ALS_MAXG * ALS_NC);
-    B.lstate = get(size_t(2) * (ALS_SPAN_PASSES + 1));
-    B.nstat = get(ALS_MAXG);
-    B.thr = get(size_t(M) * 2);
-    B.dpart = get(size_t(M) * ALS_MAXG);
+    B.csmax = 16;
+    row_chunks(n, 64, &B.nchunk, &B.rc);
+    B.w = S.get(c, size_t(B.ptot));
+    B.raw = S.get(c, size_t(B.ptot));
+    B.init = S.get(c, size_t(B.ptot) * k);
+    B.Wout = S.get(c, size_t(B.ptot) * k);
+    B.spart = S.get(c, size_t(M) * B.csmax * n);
+    B.Q = S.get(c, size_t(M) * k * n);
+    B.tt = S.get(c, size_t(n));
+    B.xpart = S.get(c, size_t(B.nchunk) * B.pmax);
+    B.fstat = S.get(c, size_t(M) * ALS_MAXG * 3);
+    B.lpart = S.get(c, size_t(2) * ALS_MAXG * ALS_NC);
+    B.lstate = S.get(c, size_t(2) * (ALS_SPAN_PASSES + 1));
+    B.nstat = S.get(c, ALS_MAXG);
+    B.thr = S.get(c, size_t(M) * 2);
+    B.dpart = S.get(c, size_t(M) * ALS_MAXG);
     if (rule == RULE_ADMM) {
-      B.eta = get(size_t(B.ptot));
-      B.tt2 = get(size_t(n));
-      B.lip = get(size_t(M));
-      B.gpart = get(ALS_LG);
+      B.eta = S.get(c, size_t(B.ptot));
+      B.tt2 = S.get(c, size_t(n));
+      B.lip = S.get(c, size_t(M));
+      B.gpart = S.get(c, ALS_LG);
       for (int i = 0; i < M; ++i) {
-        AdmmView& a = S->admm[i];
+        AdmmView& a = S.admm[i];
         a.nside = n <= p[i] ? 1 : 0;
         a.side = std::min(n, p[i]);
-        a.G = get(size_t(a.side) * a.side);
-        a.U = get(size_t(k) * a.side);
-        a.KQ = a.nside ? get(size_t(k) * n) : nullptr;
+        a.G = S.get(c, size_t(a.side) * a.side);
+        a.U = S.get(c, size_t(k) * a.side);
+        a.KQ = a.nside ? S.get(c, size_t(k) * n) : nullptr;
       }
     }
-    S->drv.create(c);
-  } catch (...) {
-    als_free(c, S);
-    throw;
-  }
-  return S;
+    S.drv.create(c);
+  });
 }
 
 // SCCA_ADMM: the penalty and the Gram of every centred view on its smaller side
@@ -1136,10 +1064,7 @@ void als_admm_setup(ccz_ctx* c, AlsState& S, const ccz_view* views, const void* 
   if (S.rule != RULE_ADMM) fail(CCZ_EINVAL, "als: the fit state was not created with CCZ_ALS_ADMM");
   if (!(mu > 0.0) || !std::isfinite(mu)) fail(CCZ_EINVAL, "als: mu must be positive and finite");
   const AlsViews vw = make_views(S, views, means);
-  for (int i = 0; i < S.M; ++i) {
-    if (S.dtype == CCZ_F32) launch_gram<float>(c, S, vw, i);
-    else launch_gram<double>(c, S, vw, i);
-  }
+  for (int i = 0; i < S.M; ++i) by_dtype(S.dtype, [&](auto t) { launch_gram<decltype(t)>(c, S, vw, i); });
   S.mu = mu;
   S.admm_ready = true;
 }
@@ -1174,15 +1099,14 @@ int ccz_als_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64
 
 int ccz_als_destroy(ccz_handle h, void* state) {
   CCZ_GUARD(h, {
-    if (state) ccz::als_free(h, static_cast<ccz::AlsState*>(state));
+    if (state) ccz::free_state(h, static_cast<ccz::AlsState*>(state));
   })
 }
 
 int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host) {
   CCZ_GUARD(h, {
     ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
-    ccz::sync(h);   // the pinned status slots may still be in use by an earlier fit on this state
-    S.drv.reset();
+    S.restart(h);
     ccz::als_set_init(h, S, w0_host);
   })
 }
@@ -1200,14 +1124,13 @@ int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void*
     ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     if (!S.has_init) ccz::fail(CCZ_EINVAL, "als: ccz_als_set_init has not been called");
     if (S.rule == ccz::RULE_ADMM && !S.admm_ready) ccz::fail(CCZ_EINVAL, "als: ccz_als_admm_setup has not been called");
-    if (n_sweeps < 0 || n_sweeps > S.chunk) ccz::fail(CCZ_EINVAL, "als: n_sweeps must be 0..%lld", (long long)S.chunk);
-    const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
-    for (int i = 0; i < S.M; ++i) S.last_cs[i] = vw.cs[i];
-    const ccz::AlsStatus* seen = S.drv.wait(S.drv.slot);
-    if (sweeps_known) *sweeps_known = seen ? seen->total : -1;
-    if (stopped_known) *stopped_known = seen ? seen->stopped : 0;
-    for (int64_t t = 0; t < n_sweeps; ++t) ccz::enqueue_sweep(h, S, vw);
-    S.drv.publish(h);
+    ccz::run_chunk(h, "als", "n_sweeps", S, n_sweeps, sweeps_known, stopped_known, &ccz::AlsStatus::total,
+                   [&] {
+                     const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
+                     for (int i = 0; i < S.M; ++i) S.last_cs[i] = vw.cs[i];
+                     return vw;
+                   },
+                   [&](const ccz::AlsViews& vw, int64_t) { ccz::enqueue_sweep(h, S, vw); });
   })
 }
 
@@ -1228,14 +1151,13 @@ int ccz_als_status(ccz_handle h, void* state, int* dims_done, int* stopped, int6
 int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, void* mean_dev) {
   CCZ_GUARD(h, {
     if (!view || !view->data || !mean_dev || n_rows < 1 || view->cols < 1 || view->ld < view->cols) ccz::fail(CCZ_EINVAL, "als: bad argument");
-    if (dtype != CCZ_F32 && dtype != CCZ_F64) ccz::fail(CCZ_EUNSUP, "als: dtype must be CCZ_F32 or CCZ_F64");
+    ccz::check_dtype("als", dtype);
     const dim3 grid(unsigned((view->cols + 255) / 256));
-    if (dtype == CCZ_F32)
-      hipLaunchKernelGGL((ccz::k_als_colmeans<float>), grid, dim3(256), 0, ccz::stream(h), static_cast<const float*>(view->data), view->ld,
-                         view->cols, n_rows, static_cast<float*>(mean_dev));
-    else
-      hipLaunchKernelGGL((ccz::k_als_colmeans<double>), grid, dim3(256), 0, ccz::stream(h), static_cast<const double*>(view->data), view->ld,
-                         view->cols, n_rows, static_cast<double*>(mean_dev));
+    ccz::by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((ccz::k_als_colmeans<T>), grid, dim3(256), 0, ccz::stream(h), static_cast<const T*>(view->data), view->ld,
+                         view->cols, n_rows, static_cast<T*>(mean_dev));
+    });
     CCZ_LAUNCH_CHECK();
   })
 }

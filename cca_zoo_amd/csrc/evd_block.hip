@@ -33,6 +33,7 @@
 
 #include "hip_common.h"
 #include "jacobi_dev.h"
+#include "reduce.h"
 
 namespace ccz {
 
@@ -727,8 +728,7 @@ __global__ __launch_bounds__(64) void k_bj_prep_rows(const double* __restrict__ 
   const double* w = W + int64_t(blockIdx.x) * ldw;
   double s = 0.0;
   for (int64_t t = threadIdx.x; t < q; t += 64) { const double x = w[t]; s += x * x; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if (threadIdx.x == 0) atomic_max_nonneg(&st->hmax, s);
 }
 

@@ -428,11 +428,10 @@ __global__ void __launch_bounds__(256) k_ey_finish(EyViews vw, const double* __r
 }
 
 // ---- host driver ----------------------------------------------------------------------------------------------------
-struct EyState {
-  int dtype, M;
-  int64_t k, bs, chunk;
+struct EyState : FitState<EyStatus> {
+  int64_t k, bs;
   double c, lr, mom, tol;
-  std::vector<int64_t> p, woff;
+  std::vector<int64_t> woff;
   int64_t ptot;
   int Q, KT, cols_per_blk, nblk_max;
   double* W[2] = {nullptr, nullptr};
@@ -441,11 +440,13 @@ struct EyState {
   double* Z = nullptr;
   double* small = nullptr;   // zmean | V | vblend | B | reward
   double* Bpart = nullptr;
-  ChunkDriver<EyStatus> drv;
   int* idx_dev[2] = {nullptr, nullptr};   // the chunk's row indices ride on the driver's slots and events
   int* idx_pin[2] = {nullptr, nullptr};
   long long enqueued = 0;    // steps enqueued since the last set_weights
-  std::vector<void*> allocs;
+  ~EyState() {
+    for (int i = 0; i < 2; ++i)
+      if (idx_pin[i]) (void)hipHostFree(idx_pin[i]);
+  }
   EyScratch scratch() const {
     EyScratch s;
     s.zmean = small;
@@ -463,13 +464,10 @@ int kt_for(int64_t k) {
 }
 
 EyViews make_views(const EyState& S, const ccz_view* views, const void* const* means) {
-  check_views("ey", views, S.p);
   EyViews vw;
   memset(&vw, 0, sizeof(vw));
+  fill_views("ey", vw, views, means, S.p);
   for (int i = 0; i < S.M; ++i) {
-    vw.X[i] = views[i].data;
-    vw.mu[i] = means ? means[i] : nullptr;
-    vw.ld[i] = views[i].ld;
     vw.p[i] = S.p[i];
     vw.woff[i] = S.woff[i];
     vw.nblk[i] = int((S.p[i] + S.cols_per_blk - 1) / S.cols_per_blk);
@@ -478,8 +476,10 @@ EyViews make_views(const EyState& S, const ccz_view* views, const void* const* m
 }
 
 template <typename T>
-void launch_project(ccz_ctx* c, const EyState& S, const EyViews& vw, const T* Wt, const int* idx, int64_t bs, double* Z,
-                    const EyStatus* st) {
+void launch_project(ccz_ctx* c, const EyState& S, const EyViews& vw, const int* idx, int64_t bs, double* Z, const EyStatus* st) {
+  const T* Wt;     // fp32 views read the rounded copy of the current weights
+  if constexpr (sizeof(T) == 4) Wt = S.Wf;
+  else Wt = S.W[int(S.enqueued & 1)];
   const dim3 grid(unsigned((bs + EY_ROWS - 1) / EY_ROWS), unsigned(S.M));
   switch (S.KT) {
     case 1: hipLaunchKernelGGL((k_ey_project<T, 1>), grid, dim3(256), 0, stream(c), vw, Wt, S.k, idx, bs, Z, st); break;
@@ -513,74 +513,50 @@ void launch_update(ccz_ctx* c, const EyState& S, const EyViews& vw, int cur, con
 void enqueue_step(ccz_ctx* c, EyState& S, const EyViews& vw, const int* idx) {
   const int cur = int(S.enqueued & 1);
   const EyScratch s = S.scratch();
-  if (S.dtype == CCZ_F32) launch_project<float>(c, S, vw, S.Wf, idx, S.bs, S.Z, S.drv.dev);
-  else launch_project<double>(c, S, vw, S.W[cur], idx, S.bs, S.Z, S.drv.dev);
+  by_dtype(S.dtype, [&](auto t) { launch_project<decltype(t)>(c, S, vw, idx, S.bs, S.Z, S.drv.dev); });
   hipLaunchKernelGGL(k_ey_moments, dim3(1), dim3(1024), 0, stream(c), S.Z, S.M, S.bs, S.k, S.c, s, S.drv.dev);
   CCZ_LAUNCH_CHECK();
-  if (S.dtype == CCZ_F32) launch_update<float>(c, S, vw, cur, idx);
-  else launch_update<double>(c, S, vw, cur, idx);
+  by_dtype(S.dtype, [&](auto t) { launch_update<decltype(t)>(c, S, vw, cur, idx); });
   hipLaunchKernelGGL(k_ey_finish, dim3(1), dim3(256), 0, stream(c), vw, S.Bpart, S.nblk_max, S.M, S.k, S.c, S.tol, s, S.drv.dev,
                      (long long)S.enqueued);
   CCZ_LAUNCH_CHECK();
   ++S.enqueued;
 }
 
-void ey_free(ccz_ctx* c, EyState* S) {
-  sync(c);
-  for (void* a : S->allocs) dev_free(c, a);
-  S->drv.destroy(c);
-  for (int i = 0; i < 2; ++i)
-    if (S->idx_pin[i]) (void)hipHostFree(S->idx_pin[i]);
-  delete S;
-}
-
 EyState* ey_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t k, int64_t bs, int64_t chunk, double cc, double lr,
                    double mom, double tol) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "ey: dtype must be CCZ_F32 or CCZ_F64");
-  if (M < 1 || M > EY_MAXV) fail(CCZ_EUNSUP, "ey: 1 to %d views are supported, got %d", EY_MAXV, M);
+  check_dtype("ey", dtype);
+  check_view_count("ey", M, EY_MAXV);
   if (!p || k < 1 || k > 128 || bs < 1 || chunk < 1) fail(CCZ_EINVAL, "ey: bad argument (k must be 1..128)");
   if (bs > (int64_t(1) << 30)) fail(CCZ_EINVAL, "ey: batch too large");
-  EyState* S = new EyState();
-  S->dtype = dtype;
-  S->M = M;
-  S->k = k;
-  S->bs = bs;
-  S->chunk = chunk;
-  S->c = cc;
-  S->lr = lr;
-  S->mom = mom;
-  S->tol = tol;
-  S->ptot = 0;
-  for (int i = 0; i < M; ++i) {
-    if (p[i] < k) { delete S; fail(CCZ_EINVAL, "ey: view %d has %lld features < k = %lld", i, (long long)p[i], (long long)k); }
-    S->p.push_back(p[i]);
-    S->woff.push_back(S->ptot * k);
-    S->ptot += p[i];
-  }
-  S->KT = kt_for(k);
-  S->Q = S->KT <= 2 ? 4 : 1;
-  S->cols_per_blk = 64 * S->Q;
-  S->nblk_max = 0;
-  for (int i = 0; i < M; ++i) S->nblk_max = std::max<int>(S->nblk_max, int((p[i] + S->cols_per_blk - 1) / S->cols_per_blk));
-  try {
-    auto get = [&](size_t bytes) { S->allocs.push_back(dev_alloc(c, bytes)); return S->allocs.back(); };
-    const size_t wn = size_t(S->ptot * k);
-    for (int i = 0; i < 2; ++i) S->W[i] = static_cast<double*>(get(wn * 8));
-    S->vel = static_cast<double*>(get(wn * 8));
-    if (dtype == CCZ_F32) S->Wf = static_cast<float*>(get(wn * 4));
-    S->Z = static_cast<double*>(get(size_t(M) * bs * k * 8));
-    S->small = static_cast<double*>(get((size_t(M) * k + 3 * k * k + 1) * 8));
-    S->Bpart = static_cast<double*>(get(size_t(M) * S->nblk_max * k * k * 8));
-    S->drv.create(c);
-    for (int i = 0; i < 2; ++i) {
-      S->idx_dev[i] = static_cast<int*>(get(size_t(chunk) * bs * 4));
-      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S->idx_pin[i]), size_t(chunk) * bs * 4, hipHostMallocDefault));
+  return new_state<EyState>(c, [&](EyState& S) {
+    S.dtype = dtype; S.M = M; S.k = k; S.bs = bs; S.chunk = chunk;
+    S.c = cc; S.lr = lr; S.mom = mom; S.tol = tol;
+    S.ptot = 0;
+    for (int i = 0; i < M; ++i) {
+      if (p[i] < k) fail(CCZ_EINVAL, "ey: view %d has %lld features < k = %lld", i, (long long)p[i], (long long)k);
+      S.p.push_back(p[i]);
+      S.woff.push_back(S.ptot * k);
+      S.ptot += p[i];
     }
-  } catch (...) {
-    ey_free(c, S);
-    throw;
-  }
-  return S;
+    S.KT = kt_for(k);
+    S.Q = S.KT <= 2 ? 4 : 1;
+    S.cols_per_blk = 64 * S.Q;
+    S.nblk_max = 0;
+    for (int i = 0; i < M; ++i) S.nblk_max = std::max<int>(S.nblk_max, int((p[i] + S.cols_per_blk - 1) / S.cols_per_blk));
+    const size_t wn = size_t(S.ptot * k);
+    for (int i = 0; i < 2; ++i) S.W[i] = S.get(c, wn);
+    S.vel = S.get(c, wn);
+    if (dtype == CCZ_F32) S.Wf = S.get<float>(c, wn);
+    S.Z = S.get(c, size_t(M) * bs * k);
+    S.small = S.get(c, size_t(M) * k + 3 * k * k + 1);
+    S.Bpart = S.get(c, size_t(M) * S.nblk_max * k * k);
+    S.drv.create(c);
+    for (int i = 0; i < 2; ++i) {
+      S.idx_dev[i] = S.get<int>(c, size_t(chunk) * bs);
+      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S.idx_pin[i]), size_t(chunk) * bs * 4, hipHostMallocDefault));
+    }
+  });
 }
 
 void ey_set_weights(ccz_ctx* c, EyState& S, const double* W_host) {
@@ -588,7 +564,7 @@ void ey_set_weights(ccz_ctx* c, EyState& S, const double* W_host) {
   const size_t wn = size_t(S.ptot * S.k);
   h2d(c, S.W[0], W_host, wn * 8);
   zero(c, S.vel, wn * 8);
-  if (S.dtype == CCZ_F32) {
+  if (S.Wf) {
     std::vector<float> wf(W_host, W_host + wn);
     h2d(c, S.Wf, wf.data(), wn * 4);
   }
@@ -642,15 +618,14 @@ int ccz_ey_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_
 
 int ccz_ey_destroy(ccz_handle h, void* state) {
   CCZ_GUARD(h, {
-    if (state) ccz::ey_free(h, static_cast<ccz::EyState*>(state));
+    if (state) ccz::free_state(h, static_cast<ccz::EyState*>(state));
   })
 }
 
 int ccz_ey_set_weights(ccz_handle h, void* state, const double* W_host) {
   CCZ_GUARD(h, {
     ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
-    ccz::sync(h);   // the pinned slots / status may still be in use by an earlier fit on this state
-    S.drv.reset();
+    S.restart(h);
     ccz::ey_set_weights(h, S, W_host);
   })
 }
@@ -665,8 +640,7 @@ int ccz_ey_project(ccz_handle h, void* state, const ccz_view* views, const void*
     ccz::sync(h);
     const int* idx = idx_host ? ccz::upload_idx(h, S, 0, idx_host, 1, n_rows) : nullptr;
     S.drv.used[0] = false;
-    if (S.dtype == CCZ_F32) ccz::launch_project<float>(h, S, vw, S.Wf, idx, S.bs, S.Z, nullptr);
-    else ccz::launch_project<double>(h, S, vw, S.W[int(S.enqueued & 1)], idx, S.bs, S.Z, nullptr);
+    ccz::by_dtype(S.dtype, [&](auto t) { ccz::launch_project<decltype(t)>(h, S, vw, idx, S.bs, S.Z, nullptr); });
     ccz::d2h(h, Z_host, S.Z, size_t(S.M) * S.bs * S.k * 8);
   })
 }
@@ -675,16 +649,14 @@ int ccz_ey_steps(ccz_handle h, void* state, const ccz_view* views, const void* c
                  const int64_t* idx_host, int64_t n_steps, int64_t* steps_known, int* stopped_known) {
   CCZ_GUARD(h, {
     ccz::EyState& S = *ccz::as_state<ccz::EyState>("ey", state);
-    if (n_steps < 0 || n_steps > S.chunk) ccz::fail(CCZ_EINVAL, "ey: n_steps must be 0..%lld", (long long)S.chunk);
-    if (!idx_host && n_rows != S.bs) ccz::fail(CCZ_EINVAL, "ey: a full-batch step needs n_rows == batch rows");
-    const ccz::EyViews vw = ccz::make_views(S, views, means_dev);
-    const int slot = S.drv.slot;
-    const ccz::EyStatus* seen = S.drv.wait(slot);
-    if (steps_known) *steps_known = seen ? seen->steps : -1;
-    if (stopped_known) *stopped_known = seen ? seen->stopped : 0;
-    const int* idx = idx_host ? ccz::upload_idx(h, S, slot, idx_host, n_steps, n_rows) : nullptr;
-    for (int64_t t = 0; t < n_steps; ++t) ccz::enqueue_step(h, S, vw, idx ? idx + t * S.bs : nullptr);
-    S.drv.publish(h);
+    const int* idx = nullptr;
+    ccz::run_chunk(h, "ey", "n_steps", S, n_steps, steps_known, stopped_known, &ccz::EyStatus::steps,
+                   [&] {
+                     if (!idx_host && n_rows != S.bs) ccz::fail(CCZ_EINVAL, "ey: a full-batch step needs n_rows == batch rows");
+                     return ccz::make_views(S, views, means_dev);
+                   },
+                   [&](const ccz::EyViews& vw, int64_t t) { ccz::enqueue_step(h, S, vw, idx ? idx + t * S.bs : nullptr); },
+                   [&](int slot) { if (idx_host) idx = ccz::upload_idx(h, S, slot, idx_host, n_steps, n_rows); });
   })
 }
 

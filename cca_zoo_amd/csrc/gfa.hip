@@ -35,6 +35,7 @@
 #include "hip_common.h"
 #include "abi_guard.h"
 #include "fit_driver.h"
+#include "reduce.h"
 #include "row_load.h"
 
 namespace ccz {
@@ -112,24 +113,6 @@ struct GfaBuf {
   double tol;
   int max_iter, drop_k;
 };
-
-__device__ __forceinline__ double gfa_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// deterministic sum over a workgroup of NW waves (every thread gets the result)
-template <int NW>
-__device__ __forceinline__ double gfa_block_sum(double v, double* sh) {
-  v = gfa_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += sh[w];
-  return t;
-}
 
 // X = A^-1 for a symmetric positive definite k x k A in LDS (row stride GFA_LD), as the reference forms it: the lower Cholesky
 // factor L (left in A's lower triangle), Y = L^-1, X = L^-T Y (cca_zoo/probabilistic/_gfa.py:222-223).  Whole workgroup;
@@ -353,13 +336,6 @@ __global__ void __launch_bounds__(GFA_PT) k_gfa_covz(GfaBuf B, GfaViews vw, cons
 }
 
 // ---- X w: column-split partial sums -------------------------------------------------------------------------------------
-// the column range of split `s` of `cs`, in units of 4 columns so that every split starts on a whole line
-__device__ __forceinline__ void gfa_split_range(int64_t p, int cs, int s, int64_t* c0, int64_t* c1) {
-  const int64_t units = (p + 3) / 4, per = (units + cs - 1) / cs;
-  *c0 = 4 * per * s;
-  *c1 = *c0 + 4 * per < p ? *c0 + 4 * per : p;
-}
-
 // plain: grid (ceil(n / 4), cs), 256 threads: 4 rows x one column range per workgroup, 4 consecutive columns per thread and step
 template <typename T>
 __global__ void __launch_bounds__(256) k_gfa_xw_plain(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
@@ -370,7 +346,7 @@ __global__ void __launch_bounds__(256) k_gfa_xw_plain(const T* __restrict__ X, c
   const int k = st->k;
   const int r0 = blockIdx.x * GFA_SROWS;
   int64_t c0, c1;
-  gfa_split_range(p, gridDim.y, blockIdx.y, &c0, &c1);
+  split_range(p, gridDim.y, int(blockIdx.y), &c0, &c1);
   const bool vec = vec_ok(X, ld, mu);
   double acc[GFA_SROWS][GFA_PLAIN_K];
 #pragma unroll
@@ -409,7 +385,7 @@ __global__ void __launch_bounds__(256) k_gfa_xw_plain(const T* __restrict__ X, c
   for (int t = 0; t < GFA_SROWS; ++t)
 #pragma unroll
     for (int a = 0; a < GFA_PLAIN_K; ++a) {
-      const double s = gfa_block_sum<4>(acc[t][a], sh);
+      const double s = block_sum<4>(acc[t][a], sh);
       if (threadIdx.x == 0 && live[t] && a < k) part[(int64_t(blockIdx.y) * n + r0 + t) * K + a] = s;
     }
 }
@@ -427,7 +403,7 @@ __global__ void __launch_bounds__(256) k_gfa_xw_mfma(const T* __restrict__ X, co
   const int li = lane & 15, lg = lane >> 4;
   const int64_t R0 = int64_t(blockIdx.x) * GFA_XROWS;
   int64_t c0, c1;
-  gfa_split_range(p, gridDim.y, blockIdx.y, &c0, &c1);
+  split_range(p, gridDim.y, int(blockIdx.y), &c0, &c1);
   const bool vec = vec_ok(X, ld, mu);
   v4f64 acc[4][KT];
 #pragma unroll
@@ -546,11 +522,11 @@ __global__ void __launch_bounds__(256) k_gfa_z(GfaBuf B, GfaViews vw, const GfaS
   for (int j = 0; j < 4; ++j) out[t + 256 * j] = acc[j];
 #pragma unroll
   for (int m = 0; m < GFA_MAXV; ++m) {
-    const double s = gfa_block_sum<4>(zx[m], sh);
+    const double s = block_sum<4>(zx[m], sh);
     if (t == 0) out[GFA_KK + m] = s;
   }
-  dd = gfa_block_sum<4>(dd, sh);
-  pp = gfa_block_sum<4>(pp, sh);
+  dd = block_sum<4>(dd, sh);
+  pp = block_sum<4>(pp, sh);
   if (t == 0) {
     out[GFA_KK + GFA_MAXV] = dd;
     out[GFA_KK + GFA_MAXV + 1] = pp;
@@ -585,8 +561,8 @@ __global__ void __launch_bounds__(GFA_PT) k_gfa_finish(GfaBuf B, GfaViews vw, Gf
   const double zzv = in ? s + double(n) * B.covz[e] : 0.0;
   if (in) B.zz[e] = zzv;
   if (in && a == b) z2[a] = s / double(n);
-  const double dd = gfa_block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + GFA_MAXV] : 0.0, sh);
-  const double pp = gfa_block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + GFA_MAXV + 1] : 0.0, sh);
+  const double dd = block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + GFA_MAXV] : 0.0, sh);
+  const double pp = block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + GFA_MAXV + 1] : 0.0, sh);
   if (e < M * GFA_MAXK) {
     const int m = e >> 5, c = e & 31;
     if (c < k) {
@@ -596,8 +572,8 @@ __global__ void __launch_bounds__(GFA_PT) k_gfa_finish(GfaBuf B, GfaViews vw, Gf
     }
   }
   for (int m = 0; m < M; ++m) {
-    const double zx = gfa_block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + m] : 0.0, sh);
-    const double wz = gfa_block_sum<GFA_PT / 64>(in ? B.ww[m * GFA_KK + e] * zzv : 0.0, sh);
+    const double zx = block_sum<GFA_PT / 64>(e < B.gz ? B.zpart[int64_t(e) * GFA_ZP + GFA_KK + m] : 0.0, sh);
+    const double wz = block_sum<GFA_PT / 64>(in ? B.ww[m * GFA_KK + e] * zzv : 0.0, sh);
     if (e == 0) {
       const double btau = GFA_PRIOR + (B.yconst[m] + wz - 2.0 * zx) / 2.0;
       B.btau[m] = btau;
@@ -702,7 +678,7 @@ __global__ void __launch_bounds__(GFA_PT) k_gfa_stat_fold(const double* __restri
     if (!pass) cmean[f] = s / double(n);
     tot += pass ? s2 / double(n - 1) : s2;
   }
-  tot = gfa_block_sum<GFA_PT / 64>(tot, sh);
+  tot = block_sum<GFA_PT / 64>(tot, sh);
   if (threadIdx.x == 0) *(pass ? out1 : out0) = tot;
 }
 
@@ -758,25 +734,16 @@ __global__ void __launch_bounds__(GFA_PT) k_gfa_init(GfaBuf B, GfaViews vw, GfaS
 }
 
 // ---- host driver ----------------------------------------------------------------------------------------------------
-struct GfaState {
-  int dtype, M;
-  int64_t n, K, chunk;
-  std::vector<int64_t> p;
+struct GfaState : FitState<GfaStatus> {
+  int64_t n, K;
   GfaBuf B;
   GfaViews shape;                  // cs, gw, off, xwoff per view (the pointers are filled per call)
-  ChunkDriver<GfaStatus> drv;
   bool has_init = false, ready = false;
-  std::vector<void*> allocs;
 };
 
 GfaViews make_views(const GfaState& S, const ccz_view* views, const void* const* means) {
-  check_views("gfa", views, S.p);
   GfaViews vw = S.shape;
-  for (int i = 0; i < S.M; ++i) {
-    vw.X[i] = views[i].data;
-    vw.mu[i] = means ? means[i] : nullptr;
-    vw.ld[i] = views[i].ld;
-  }
+  fill_views("gfa", vw, views, means, S.p);
   return vw;
 }
 
@@ -823,17 +790,13 @@ void enqueue_iteration(ccz_ctx* c, const GfaState& S, const GfaViews& vw) {
   hipLaunchKernelGGL(k_gfa_covw, dim3(S.M), dim3(256), 0, stream(c), B, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   for (int i = 0; i < S.M; ++i) {
-    if (S.dtype == CCZ_F32) launch_xtz<float>(c, S, vw, i);
-    else launch_xtz<double>(c, S, vw, i);
+    by_dtype(S.dtype, [&](auto t) { launch_xtz<decltype(t)>(c, S, vw, i); });
     hipLaunchKernelGGL(k_gfa_wfold, dim3(vw.gw[i]), dim3(256), 0, stream(c), B, i, vw.p[i], vw.off[i], S.drv.dev);
     CCZ_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_gfa_covz, dim3(1), dim3(GFA_PT), 0, stream(c), B, vw, S.drv.dev);
   CCZ_LAUNCH_CHECK();
-  for (int i = 0; i < S.M; ++i) {
-    if (S.dtype == CCZ_F32) launch_xw<float>(c, S, vw, i);
-    else launch_xw<double>(c, S, vw, i);
-  }
+  for (int i = 0; i < S.M; ++i) by_dtype(S.dtype, [&](auto t) { launch_xw<decltype(t)>(c, S, vw, i); });
   hipLaunchKernelGGL(k_gfa_z, dim3(B.gz), dim3(256), 0, stream(c), B, vw, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_gfa_finish, dim3(1), dim3(GFA_PT), 0, stream(c), B, vw, S.drv.dev);
@@ -858,99 +821,68 @@ void launch_stats(ccz_ctx* c, const void* X, const void* mu, int64_t ld, int64_t
   }
 }
 
-void stat_chunks(int64_t n, int cap, int* sc, int* src) {
-  int s = int(std::max<int64_t>(1, std::min<int64_t>(cap, (n + 63) / 64)));
-  *src = int((n + s - 1) / s);
-  *sc = int((n + *src - 1) / *src);
-}
-
-void gfa_free(ccz_ctx* c, GfaState* S) {
-  sync(c);
-  for (void* a : S->allocs) dev_free(c, a);
-  S->drv.destroy(c);
-  delete S;
-}
-
 GfaState* gfa_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, int64_t k, double tol, int64_t max_iter, int drop_k,
                      int64_t chunk) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "gfa: dtype must be CCZ_F32 or CCZ_F64");
-  if (M < 1 || M > GFA_MAXV) fail(CCZ_EUNSUP, "gfa: 1 to %d views are supported, got %d", GFA_MAXV, M);
+  check_dtype("gfa", dtype);
+  check_view_count("gfa", M, GFA_MAXV);
   if (k < 1 || k > GFA_MAXK) fail(CCZ_EUNSUP, "gfa: 1 to %d latent dimensions are supported, got %lld", GFA_MAXK, (long long)k);
   if (!p || n < 2 || n > (int64_t(1) << 30) || max_iter < 1 || max_iter > (int64_t(1) << 30) || chunk < 1 || !(tol >= 0.0))
     fail(CCZ_EINVAL, "gfa: bad argument");
-  GfaState* S = new GfaState();
-  S->dtype = dtype; S->M = M; S->n = n; S->K = k; S->chunk = chunk;
-  GfaBuf& B = S->B;
-  memset(&B, 0, sizeof(B));
-  memset(&S->shape, 0, sizeof(S->shape));
-  B.n = int(n); B.M = M; B.K = int(k); B.tol = tol; B.max_iter = int(max_iter); B.drop_k = drop_k ? 1 : 0;
-  const bool plain = k <= GFA_PLAIN_K;
-  int64_t xwtot = 0;
-  for (int i = 0; i < M; ++i) {
-    if (p[i] < 1) { delete S; fail(CCZ_EINVAL, "gfa: view %d has no columns", i); }
-    S->p.push_back(p[i]);
-    GfaViews& sh = S->shape;
-    sh.p[i] = p[i];
-    sh.off[i] = B.ptot;
-    B.ptot += p[i];
-    B.pmax = std::max(B.pmax, p[i]);
-    // enough X w workgroups to fill the device when there are few rows; every split at least 4096 columns wide
-    const int64_t rowgroups = plain ? (n + GFA_SROWS - 1) / GFA_SROWS : (n + GFA_XROWS - 1) / GFA_XROWS;
-    const int64_t cs = std::min<int64_t>((2048 + rowgroups - 1) / rowgroups, std::max<int64_t>(1, p[i] / 4096));
-    sh.cs[i] = int(std::max<int64_t>(1, std::min<int64_t>(cs, GFA_CSMAX)));
-    sh.xwoff[i] = xwtot;
-    xwtot += int64_t(sh.cs[i]) * n * k;
-    sh.gw[i] = int(std::max<int64_t>(1, std::min<int64_t>(GFA_G, (p[i] + GFA_FB - 1) / GFA_FB)));
-  }
-  // the X'z partials are nchunk x pmax x k doubles: as many row chunks as the scratch budget holds, 64 at most, of >= 64 rows
-  const int64_t per_chunk = B.pmax * k * 8;
-  int64_t nchunk = std::min<int64_t>(std::min<int64_t>(64, (n + 63) / 64), std::max<int64_t>(1, GFA_SCRATCH_BYTES / per_chunk));
-  B.rc = int((n + nchunk - 1) / nchunk);
-  B.nchunk = int((n + B.rc - 1) / B.rc);
-  B.gz = int(std::max<int64_t>(1, std::min<int64_t>(GFA_G, (n + GFA_ZR - 1) / GFA_ZR)));
-  // the setup pass keeps 2 sc pmax partials in the same scratch
-  stat_chunks(n, int(std::max<int64_t>(1, int64_t(B.nchunk) * k / 2)), &B.sc, &B.src);
-  try {
-    auto get = [&](size_t doubles) {
-      void* a = dev_alloc(c, std::max<size_t>(doubles, 1) * 8);
-      S->allocs.push_back(a);
-      return static_cast<double*>(a);
-    };
-    B.z = get(size_t(n) * k);
-    B.w = get(size_t(B.ptot) * k);
-    B.xw = get(size_t(M) * n * k);
-    B.xwpart = get(size_t(xwtot));
-    B.xpart = get(std::max<size_t>(size_t(B.nchunk) * B.pmax * k, size_t(2) * B.sc * B.pmax));
-    B.covz = get(GFA_KK);
-    B.zz = get(GFA_KK);
-    B.covw = get(size_t(M) * GFA_KK);
-    B.ww = get(size_t(M) * GFA_KK);
-    B.alpha = get(size_t(M) * GFA_MAXK);
-    B.bard = get(size_t(M) * GFA_MAXK);
-    B.tau = get(M);
-    B.btau = get(M);
-    B.yconst = get(M);
-    B.datavar = get(M);
-    B.wwpart = get(size_t(M) * GFA_G * GFA_KK);
-    B.zpart = get(size_t(GFA_G) * GFA_ZP);
-    B.cmean = get(size_t(B.pmax));
-    S->drv.create(c);
-  } catch (...) {
-    gfa_free(c, S);
-    throw;
-  }
-  return S;
+  check_no_empty_view("gfa", M, p);
+  return new_state<GfaState>(c, [&](GfaState& S) {
+    S.dtype = dtype; S.M = M; S.n = n; S.K = k; S.chunk = chunk;
+    S.p.assign(p, p + M);
+    GfaBuf& B = S.B;
+    memset(&B, 0, sizeof(B));
+    memset(&S.shape, 0, sizeof(S.shape));
+    B.n = int(n); B.M = M; B.K = int(k); B.tol = tol; B.max_iter = int(max_iter); B.drop_k = drop_k ? 1 : 0;
+    const bool plain = k <= GFA_PLAIN_K;
+    int64_t xwtot = 0;
+    for (int i = 0; i < M; ++i) {
+      GfaViews& sh = S.shape;
+      sh.p[i] = p[i];
+      sh.off[i] = B.ptot;
+      B.ptot += p[i];
+      B.pmax = std::max(B.pmax, p[i]);
+      sh.cs[i] = column_splits(n, plain ? GFA_SROWS : GFA_XROWS, p[i], GFA_CSMAX);
+      sh.xwoff[i] = xwtot;
+      xwtot += int64_t(sh.cs[i]) * n * k;
+      sh.gw[i] = int(std::max<int64_t>(1, std::min<int64_t>(GFA_G, (p[i] + GFA_FB - 1) / GFA_FB)));
+    }
+    // the X'z partials are nchunk x pmax x k doubles: as many row chunks as the scratch budget holds, 64 at most, of >= 64 rows
+    row_chunks(n, std::min<int64_t>(64, GFA_SCRATCH_BYTES / (B.pmax * k * 8)), &B.nchunk, &B.rc);
+    B.gz = int(std::max<int64_t>(1, std::min<int64_t>(GFA_G, (n + GFA_ZR - 1) / GFA_ZR)));
+    // the setup pass keeps 2 sc pmax partials in the same scratch
+    row_chunks(n, int64_t(B.nchunk) * k / 2, &B.sc, &B.src);
+    B.z = S.get(c, size_t(n) * k);
+    B.w = S.get(c, size_t(B.ptot) * k);
+    B.xw = S.get(c, size_t(M) * n * k);
+    B.xwpart = S.get(c, size_t(xwtot));
+    B.xpart = S.get(c, std::max<size_t>(size_t(B.nchunk) * B.pmax * k, size_t(2) * B.sc * B.pmax));
+    B.covz = S.get(c, GFA_KK);
+    B.zz = S.get(c, GFA_KK);
+    B.covw = S.get(c, size_t(M) * GFA_KK);
+    B.ww = S.get(c, size_t(M) * GFA_KK);
+    B.alpha = S.get(c, size_t(M) * GFA_MAXK);
+    B.bard = S.get(c, size_t(M) * GFA_MAXK);
+    B.tau = S.get(c, M);
+    B.btau = S.get(c, M);
+    B.yconst = S.get(c, M);
+    B.datavar = S.get(c, M);
+    B.wwpart = S.get(c, size_t(M) * GFA_G * GFA_KK);
+    B.zpart = S.get(c, size_t(GFA_G) * GFA_ZP);
+    B.cmean = S.get(c, size_t(B.pmax));
+    S.drv.create(c);
+  });
 }
 
 void gfa_setup(ccz_ctx* c, GfaState& S, const ccz_view* views, const void* const* means) {
   const GfaViews vw = make_views(S, views, means);
   const GfaBuf& B = S.B;
-  for (int i = 0; i < S.M; ++i) {
-    if (S.dtype == CCZ_F32)
-      launch_stats<float>(c, vw.X[i], vw.mu[i], vw.ld[i], vw.p[i], S.n, B.sc, B.src, B.xpart, B.cmean, B.yconst + i, B.datavar + i);
-    else
-      launch_stats<double>(c, vw.X[i], vw.mu[i], vw.ld[i], vw.p[i], S.n, B.sc, B.src, B.xpart, B.cmean, B.yconst + i, B.datavar + i);
-  }
+  for (int i = 0; i < S.M; ++i)
+    by_dtype(S.dtype, [&](auto t) {
+      launch_stats<decltype(t)>(c, vw.X[i], vw.mu[i], vw.ld[i], vw.p[i], S.n, B.sc, B.src, B.xpart, B.cmean, B.yconst + i, B.datavar + i);
+    });
   zero(c, B.w, size_t(B.ptot) * S.K * 8);
   zero(c, B.xw, size_t(S.M) * S.n * S.K * 8);
   hipLaunchKernelGGL(k_gfa_zz0, dim3(B.gz), dim3(256), 0, stream(c), B);
@@ -989,7 +921,7 @@ int ccz_gfa_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64
 
 int ccz_gfa_destroy(ccz_handle h, void* state) {
   CCZ_GUARD(h, {
-    if (state) ccz::gfa_free(h, static_cast<ccz::GfaState*>(state));
+    if (state) ccz::free_state(h, static_cast<ccz::GfaState*>(state));
   })
 }
 
@@ -997,8 +929,7 @@ int ccz_gfa_set_init(ccz_handle h, void* state, const double* z0_host) {
   CCZ_GUARD(h, {
     ccz::GfaState& S = *ccz::as_state<ccz::GfaState>("gfa", state);
     if (!z0_host) ccz::fail(CCZ_EINVAL, "gfa: null initial z");
-    ccz::sync(h);   // the pinned status slots may still be in use by an earlier fit on this state
-    S.drv.reset();
+    S.restart(h);
     ccz::h2d(h, S.B.z, z0_host, size_t(S.n) * S.K * 8);
     S.has_init = true;
     S.ready = false;
@@ -1020,13 +951,9 @@ int ccz_gfa_iterations(ccz_handle h, void* state, const ccz_view* views, const v
   CCZ_GUARD(h, {
     ccz::GfaState& S = *ccz::as_state<ccz::GfaState>("gfa", state);
     if (!S.ready) ccz::fail(CCZ_EINVAL, "gfa: ccz_gfa_setup has not been called");
-    if (n_iters < 0 || n_iters > S.chunk) ccz::fail(CCZ_EINVAL, "gfa: n_iters must be 0..%lld", (long long)S.chunk);
-    const ccz::GfaViews vw = ccz::make_views(S, views, means_dev);
-    const ccz::GfaStatus* seen = S.drv.wait(S.drv.slot);
-    if (iters_known) *iters_known = seen ? seen->iters : -1;
-    if (stopped_known) *stopped_known = seen ? seen->stopped : 0;
-    for (int64_t t = 0; t < n_iters; ++t) ccz::enqueue_iteration(h, S, vw);
-    S.drv.publish(h);
+    ccz::run_chunk(h, "gfa", "n_iters", S, n_iters, iters_known, stopped_known, &ccz::GfaStatus::iters,
+                   [&] { return ccz::make_views(S, views, means_dev); },
+                   [&](const ccz::GfaViews& vw, int64_t) { ccz::enqueue_iteration(h, S, vw); });
   })
 }
 
@@ -1103,14 +1030,13 @@ int ccz_gfa_sumsq(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows,
   CCZ_GUARD(h, {
     if (!view || !view->data || !sumsq_host || n_rows < 1 || n_rows > (int64_t(1) << 30) || view->cols < 1 || view->ld < view->cols)
       ccz::fail(CCZ_EINVAL, "gfa: bad argument");
-    if (dtype != CCZ_F32 && dtype != CCZ_F64) ccz::fail(CCZ_EUNSUP, "gfa: dtype must be CCZ_F32 or CCZ_F64");
+    ccz::check_dtype("gfa", dtype);
     int sc, src;
-    ccz::stat_chunks(n_rows, 64, &sc, &src);
+    ccz::row_chunks(n_rows, 64, &sc, &src);
     ccz::DBuf part(h, int64_t(2) * sc * view->cols), cmean(h, view->cols), out(h, 1);
-    if (dtype == CCZ_F32)
-      ccz::launch_stats<float>(h, view->data, mean_dev, view->ld, view->cols, n_rows, sc, src, part, cmean, out, nullptr);
-    else
-      ccz::launch_stats<double>(h, view->data, mean_dev, view->ld, view->cols, n_rows, sc, src, part, cmean, out, nullptr);
+    ccz::by_dtype(dtype, [&](auto t) {
+      ccz::launch_stats<decltype(t)>(h, view->data, mean_dev, view->ld, view->cols, n_rows, sc, src, part, cmean, out, nullptr);
+    });
     ccz::d2h(h, sumsq_host, out, 8);
   })
 }

@@ -16,6 +16,7 @@
 
 #include "hip_common.h"
 #include "jacobi_dev.h"
+#include "reduce.h"
 #include "rng_hash.h"
 
 namespace ccz {
@@ -722,24 +723,6 @@ void randn_fill(ccz_ctx* c, int64_t rows, int64_t cols, double* A, int64_t lda, 
 // ===========================================================================
 // reductions
 // ===========================================================================
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide sum; result valid in every thread.  red: >= (blockDim/64) doubles of LDS
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < nw; ++i) t += red[i];
-  return t;
-}
-
 __global__ void k_col_sqnorms(int64_t rows, int64_t cols, const double* __restrict__ A, int64_t lda,
                               double* __restrict__ out, int64_t rows_per_block) {
   const int64_t r0 = int64_t(blockIdx.x) * rows_per_block;
@@ -765,7 +748,7 @@ __global__ void k_row_abs_sums(int64_t cols, const double* __restrict__ A, int64
   const double* a = A + int64_t(blockIdx.x) * lda;
   double acc = 0.0;
   for (int64_t j = threadIdx.x; j < cols; j += blockDim.x) acc += fabs(a[j]);
-  acc = block_sum(acc, red);
+  acc = block_sum_dyn(acc, red);
   if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 double norm_inf(ccz_ctx* c, int64_t rows, int64_t cols, const double* A, int64_t lda) {
@@ -788,7 +771,7 @@ __global__ void k_row_dots(int64_t cols, const double* __restrict__ A, int64_t l
   const double* b = B + int64_t(blockIdx.x) * ldb;
   double acc = 0.0;
   for (int64_t j = threadIdx.x; j < cols; j += blockDim.x) acc += a[j] * b[j];
-  acc = block_sum(acc, red);
+  acc = block_sum_dyn(acc, red);
   if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 void row_dots(ccz_ctx* c, int64_t rows, int64_t cols, const double* A, int64_t lda, const double* B, int64_t ldb,

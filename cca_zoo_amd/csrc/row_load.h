@@ -1,5 +1,5 @@
-// Row loads of the kernels that read the views where they lie (ey.hip, als.hip): four consecutive features per lane,
-// by 16-byte loads where the alignment allows.
+// Row loads of the kernels that read the views where they lie (ey.hip, als.hip, gfa.hip): four consecutive features per lane,
+// by 16-byte loads where the alignment allows; the column range of a workgroup that takes one split of a view's columns.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +32,15 @@ __device__ __forceinline__ void load4(const T* base, int64_t f0, int64_t p, bool
 #pragma unroll
     for (int q = 0; q < 4; ++q) v[q] = f0 + q < p ? base[f0 + q] : T(0);
   }
+}
+
+// the column range [c0, c1) of split `s` of `cs`, in units of 4 columns so that every split starts on a whole line; `s` enters
+// the product in the caller's type (blockIdx.y as it is, or an int), so that a kernel's index arithmetic stays what it was
+template <typename Index>
+__device__ __forceinline__ void split_range(int64_t p, int cs, Index s, int64_t* c0, int64_t* c1) {
+  const int64_t units = (p + 3) / 4, per = (units + cs - 1) / cs;
+  *c0 = 4 * per * s;
+  *c1 = *c0 + 4 * per < p ? *c0 + 4 * per : p;
 }
 
 }  // namespace ccz

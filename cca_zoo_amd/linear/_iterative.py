@@ -23,7 +23,8 @@ import numpy as np
 from sklearn.utils._param_validation import Interval
 
 from cca_zoo_amd._base import BaseModel
-from cca_zoo_amd._utils._resident import MEANS_COLMEANS, ResidentViews
+from cca_zoo_amd._utils._resident import (MEANS_COLMEANS, ResidentViews, check_limits, fit_state, refuse_row_sharded,
+                                           run_chunks)
 from cca_zoo_amd._utils._validation import perview_parameter
 
 #: sweeps per ``ccz_als_sweeps`` call: one host wait (for the chunk two calls back) per chunk
@@ -99,23 +100,15 @@ class _BaseIterative(BaseModel):
         """Model-specific calls between ``ccz_als_create`` and the first sweep."""
 
     def fit(self, views, y=None):
-        from cca_zoo_amd import _dist
-
-        if _dist.is_sharded():
-            raise NotImplementedError(
-                f"{type(self).__name__} alternates over whole feature vectors, which this build does not shard by rows: "
-                "fit it outside row_sharded()"
-            )
+        refuse_row_sharded(f"{type(self).__name__} alternates over whole feature vectors, which this build does not shard "
+                           "by rows")
         self._validate_params()
         # the means of device rows in NumPy's own order of summation (ccz_als_colmeans): torch's tree-ordered float32 mean
         # differs from v.mean(axis=0) in the last bits, and with it the whole trajectory
         res = ResidentViews(views, self.center, MEANS_COLMEANS)
         m, n, p = len(res.p), res.n, res.p
         k = int(self.latent_dimensions)
-        if k > MAX_DIMS:
-            raise ValueError(f"latent_dimensions={k}: the device path supports at most {MAX_DIMS}")
-        if m > MAX_VIEWS:
-            raise ValueError(f"{m} views: the device path supports at most {MAX_VIEWS} views")
+        check_limits(k, m, MAX_DIMS, MAX_VIEWS)
         if n < 1:
             raise ValueError("at least 1 sample is required")
         self._check_shapes(n, p)
@@ -123,22 +116,20 @@ class _BaseIterative(BaseModel):
         par = self._rule_parameters(p)
         total = k * int(self.max_iter)
         chunk = max(1, min(CHUNK_SWEEPS, total))
-        state = C.c_void_p()
         with res:
             h = res.handle
-            h.check(h.lib.ccz_als_create(h.raw, res.code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
-                                         (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter),
-                                         chunk, C.byref(state)))
-            try:
+            with fit_state(h, "als", res.code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
+                           (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter), chunk) as state:
                 self._setup_state(h, state, res)
                 w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
                 h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
-                done = 0
                 known, stopped = C.c_int64(-1), C.c_int(0)
-                while done < total and not stopped.value:
-                    s = min(chunk, total - done)
+
+                def sweeps(s):
                     h.check(h.lib.ccz_als_sweeps(h.raw, state, res.varr, res.marr, s, C.byref(known), C.byref(stopped)))
-                    done += s
+                    return stopped.value
+
+                run_chunks(total, chunk, sweeps)
                 dims, stop = C.c_int(0), C.c_int(0)
                 iters = (C.c_int64 * k)()
                 deltas = (C.c_double * k)()
@@ -147,8 +138,6 @@ class _BaseIterative(BaseModel):
                     raise RuntimeError(f"ALS fit ended after {dims.value} of {k} dimensions")   # cannot happen: k * max_iter sweeps
                 wflat = np.empty(sum(p) * k)
                 h.check(h.lib.ccz_als_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
-            finally:
-                h.lib.ccz_als_destroy(h.raw, state)
         self.n_iter_ = [int(x) for x in iters]
         self.last_delta_ = [float(x) for x in deltas]
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])

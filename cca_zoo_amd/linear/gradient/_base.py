@@ -14,7 +14,7 @@ from typing import Any, ClassVar
 import numpy as np
 
 from cca_zoo_amd._base import BaseModel
-from cca_zoo_amd._utils._resident import MEANS_TORCH, ResidentViews
+from cca_zoo_amd._utils._resident import MEANS_TORCH, ResidentViews, fit_state, refuse_row_sharded, run_chunks
 
 #: steps per ``ccz_ey_steps`` call: one host wait (for the chunk two calls back) and one index upload per chunk
 CHUNK_STEPS = 64
@@ -78,13 +78,7 @@ class BaseGradientModel(BaseModel):
         return float(self.c)
 
     def fit(self, views, y=None):
-        from cca_zoo_amd import _dist
-
-        if _dist.is_sharded():
-            raise NotImplementedError(
-                f"{type(self).__name__} takes a global mini-batch per step, which does not shard by rows: "
-                "fit it outside row_sharded()"
-            )
+        refuse_row_sharded(f"{type(self).__name__} takes a global mini-batch per step, which does not shard by rows")
         self._validate_params()
         # the reference's _setup_fit: v.mean(axis=0) in the input dtype (torch's mean for device rows)
         res = ResidentViews(views, self.center, MEANS_TORCH)
@@ -100,12 +94,10 @@ class BaseGradientModel(BaseModel):
         bs = n if self.batch_size is None else min(int(self.batch_size), n)
         full = bs == n
         chunk = max(1, min(CHUNK_STEPS, int(self.max_iter)))
-        state = C.c_void_p()
         with res:
             h, varr, marr = res.handle, res.varr, res.marr
-            h.check(h.lib.ccz_ey_create(h.raw, res.code, m, (C.c_int64 * m)(*p), k, bs, chunk, self._ridge(),
-                                        float(self.learning_rate), float(self.momentum), float(self.tol), C.byref(state)))
-            try:
+            with fit_state(h, "ey", res.code, m, (C.c_int64 * m)(*p), k, bs, chunk, self._ridge(), float(self.learning_rate),
+                           float(self.momentum), float(self.tol)) as state:
                 rng = np.random.default_rng(self.random_state)
 
                 def project(idx, w0s):
@@ -118,20 +110,19 @@ class BaseGradientModel(BaseModel):
 
                 W0 = initial_weights(self._init_kind, p, k, n, bs, rng, project)
                 h.check(h.lib.ccz_ey_set_weights(h.raw, state, _dp(_wblocks(W0))))
-                done = 0
                 known, stopped = C.c_int64(-1), C.c_int(0)
-                while done < self.max_iter and not stopped.value:
-                    s = min(chunk, int(self.max_iter) - done)
+
+                def steps_chunk(s):
                     idx = None if full else draw_batches(rng, n, bs, s)
                     ip = None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int64))
                     h.check(h.lib.ccz_ey_steps(h.raw, state, varr, marr, n, ip, s, C.byref(known), C.byref(stopped)))
-                    done += s
+                    return stopped.value
+
+                run_chunks(int(self.max_iter), chunk, steps_chunk)
                 steps, stop, obj = C.c_int64(0), C.c_int(0), C.c_double(0.0)
                 h.check(h.lib.ccz_ey_status(h.raw, state, C.byref(steps), C.byref(stop), C.byref(obj)))
                 wflat = np.empty(sum(p) * k)
                 h.check(h.lib.ccz_ey_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
-            finally:
-                h.lib.ccz_ey_destroy(h.raw, state)
         self.n_iter_ = int(steps.value)
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
         self._store(weights, res.means_host(), "f32" if res.f32 else "f64", weights_like_input=False)

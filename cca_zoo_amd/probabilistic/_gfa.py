@@ -19,7 +19,8 @@ from sklearn.utils._param_validation import Interval
 from sklearn.utils.validation import check_is_fitted
 
 from cca_zoo_amd._base import BaseModel, _device_project, _host_project
-from cca_zoo_amd._utils._resident import MEANS_COLMEANS, MEANS_TORCH, ResidentViews
+from cca_zoo_amd._utils._resident import (MEANS_COLMEANS, MEANS_TORCH, ResidentViews, check_limits, fit_state,
+                                           refuse_row_sharded, run_chunks)
 from cca_zoo_amd._utils._validation import is_device_tensor, validate_views
 
 #: iterations per ``ccz_gfa_iterations`` call: one host wait (for the chunk two calls back) per chunk; the result does
@@ -104,22 +105,14 @@ class GFA(BaseModel):
     # -- fit -------------------------------------------------------------------------------------------------------
     def fit(self, views, y=None):
         """Fit to a list of (n_samples, n_features_i) host arrays or CUDA tensors."""
-        from cca_zoo_amd import _dist
-
-        if _dist.is_sharded():
-            raise NotImplementedError(
-                "GFA updates whole feature vectors and the shared latent variable in turn, which this build does not "
-                "shard by rows: fit it outside row_sharded()"
-            )
+        refuse_row_sharded("GFA updates whole feature vectors and the shared latent variable in turn, which this build does not "
+                           "shard by rows")
         self._validate_params()
         res = ResidentViews(views, self.center, MEANS_COLMEANS)
         m, n, p = len(res.p), res.n, res.p
         k = int(self.latent_dimensions)
         s = int(self.num_posterior_samples)
-        if k > MAX_DIMS:
-            raise ValueError(f"latent_dimensions={k}: the device path supports at most {MAX_DIMS}")
-        if m > MAX_VIEWS:
-            raise ValueError(f"{m} views: the device path supports at most {MAX_VIEWS} views")
+        check_limits(k, m, MAX_DIMS, MAX_VIEWS)
         if n < 2:
             raise ValueError("at least 2 samples are required")
         self._check_sample_size(s, n, k)       # before any device work: pruning can only shrink it
@@ -129,20 +122,19 @@ class GFA(BaseModel):
         rng = np.random.default_rng(self.random_state)
         z0 = np.ascontiguousarray(rng.standard_normal((n, k)))
         pd = C.POINTER(C.c_double)
-        state = C.c_void_p()
         with res:
             h = res.handle
-            h.check(h.lib.ccz_gfa_create(h.raw, res.code, m, (C.c_int64 * m)(*p), n, k, float(self.tol), total,
-                                         int(bool(self.drop_k)), chunk, C.byref(state)))
-            try:
+            with fit_state(h, "gfa", res.code, m, (C.c_int64 * m)(*p), n, k, float(self.tol), total, int(bool(self.drop_k)),
+                           chunk) as state:
                 h.check(h.lib.ccz_gfa_set_init(h.raw, state, z0.ctypes.data_as(pd)))
                 h.check(h.lib.ccz_gfa_setup(h.raw, state, res.varr, res.marr))
-                done = 0
                 known, stopped = C.c_int64(-1), C.c_int(0)
-                while done < total and not stopped.value:
-                    step = min(chunk, total - done)
+
+                def iterations(step):
                     h.check(h.lib.ccz_gfa_iterations(h.raw, state, res.varr, res.marr, step, C.byref(known), C.byref(stopped)))
-                    done += step
+                    return stopped.value
+
+                run_chunks(total, chunk, iterations)
                 iters, stop, ka, stable, nprune = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
                 rel = C.c_double(0.0)
                 piters, pk = (C.c_int64 * MAX_DIMS)(), (C.c_int * MAX_DIMS)()
@@ -157,8 +149,6 @@ class GFA(BaseModel):
                 tau, b_tau = np.empty(m), np.empty(m)
                 h.check(h.lib.ccz_gfa_get_result(h.raw, state, C.byref(ka), *[a.ctypes.data_as(pd) for a in
                                                                               (z, cov_z, w, cov_w, alpha, b_ard, tau, b_tau)]))
-            finally:
-                h.lib.ccz_gfa_destroy(h.raw, state)
         if not all(np.all(np.isfinite(a)) for a in (z, cov_z, w, cov_w, alpha, tau)):
             raise np.linalg.LinAlgError("GFA: an update lost positive definiteness (the reference's Cholesky raises here)")
         self.n_iter_ = int(iters.value)
