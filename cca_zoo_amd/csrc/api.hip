@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -62,25 +63,27 @@ int ccz_create(ccz_handle* out, int device) {
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { (void)hipGetLastError(); return CCZ_EHIP; }
   if (device < 0 || device >= count) return CCZ_EINVAL;
   if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return CCZ_EHIP; }
-  ccz_ctx* c = new (std::nothrow) ccz_ctx();
-  Impl* im = new (std::nothrow) Impl();
-  if (!c || !im) { delete c; delete im; return CCZ_ENOMEM; }
+  // both are owners: whatever exists when a step fails is destroyed on the way out
+  std::unique_ptr<ccz_ctx> c(new (std::nothrow) ccz_ctx());
+  std::unique_ptr<Impl> im(new (std::nothrow) Impl());
+  if (!c || !im) return CCZ_ENOMEM;
   c->device = device;
-  c->impl = im;
   bool ok = hipGetDeviceProperties(&im->props, device) == hipSuccess;
-  for (int i = 0; ok && i < 4; ++i) ok = hipEventCreate(&im->ev[i]) == hipSuccess;
+  for (int i = 0; ok && i < 4; ++i) ok = hipEventCreate(im->ev[i].out()) == hipSuccess;
   // a real (blocking) stream instead of the legacy null stream: it keeps the implicit ordering with
   // null-stream work (PyTorch's default stream) and, unlike the null stream, can be captured into graphs
-  ok = ok && hipStreamCreate(&im->own_stream) == hipSuccess;
-  if (ok) c->stream = im->own_stream;
+  ok = ok && hipStreamCreate(im->own_stream.out()) == hipSuccess;
+  if (ok) c->stream = im->own_stream.get();
   im->graphs_on = env::live(env::GRAPHS);
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&im->d_flag), 64 * sizeof(int)) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&im->d_small), im->small_cap * sizeof(double)) == hipSuccess;
-  if (!ok) { (void)hipGetLastError(); delete im; delete c; return CCZ_EHIP; }
-  *out = c;
+  ok = ok && hipMalloc(im->d_flag.out(), 64 * sizeof(int)) == hipSuccess;
+  ok = ok && hipMalloc(im->d_small.out(), im->small_cap * sizeof(double)) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); return CCZ_EHIP; }
+  c->impl = im.release();
+  *out = c.release();
   return CCZ_OK;
 }
 
+// three ordered steps, then ownership does the rest (hip_common.h: Impl's members in reverse order of declaration)
 int ccz_destroy(ccz_handle h) {
   if (!h) return CCZ_OK;
   Impl* im = impl(h);
@@ -88,38 +91,6 @@ int ccz_destroy(ccz_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     if (im->comm) (void)ccz_comm_destroy(h);
-    for (auto& g : im->graphs) (void)hipGraphExecDestroy(g.exec);
-    if (im->own_stream) (void)hipStreamDestroy(im->own_stream);
-    for (auto& b : im->pool) (void)hipFree(b.p);
-    for (auto& t : im->tile_tabs) if (t.dev) (void)hipFree(t.dev);
-    for (auto& e : im->chain_sync) if (e.second) (void)hipFree(e.second);
-    for (auto& e : im->colsum_sync) if (e.second) (void)hipFree(e.second);
-    for (auto& e : im->k1_plans) if (e.dev) (void)hipFree(e.dev);
-    if (im->chain_dbg) (void)hipFree(im->chain_dbg);
-    if (im->xchg_buf) (void)hipFree(im->xchg_buf);
-    if (im->xchg_stream) (void)hipStreamDestroy(im->xchg_stream);
-    for (auto& e : im->xchg_ev) if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(im->ev[i]);
-    for (int i = 0; i < 4; ++i) if (im->pipe_ev[i]) (void)hipEventDestroy(im->pipe_ev[i]);
-    for (auto& e : im->sp_ev) if (e) (void)hipEventDestroy(e);
-    if (im->split_stream) (void)hipStreamDestroy(im->split_stream);
-    for (auto& e : im->split_tabs) { (void)hipFree(e.panels); (void)hipFree(e.tiles); (void)hipFree(e.gtiles); }
-    for (int i = 0; i < 2; ++i) if (im->pin_buf[i]) (void)hipHostFree(im->pin_buf[i]);
-    for (int i = 0; i < Impl::kSmallSlots; ++i) {
-      if (im->small_ev[i]) (void)hipEventDestroy(im->small_ev[i]);
-      if (im->small_pin[i]) (void)hipHostFree(im->small_pin[i]);
-    }
-    if (im->copy_stream) (void)hipStreamDestroy(im->copy_stream);
-    for (int i = 0; i < 2; ++i) if (im->aux_ev[i]) (void)hipEventDestroy(im->aux_ev[i]);
-    if (im->aux_stream) (void)hipStreamDestroy(im->aux_stream);
-    for (int i = 0; i < 2; ++i) if (im->xs_ev[i]) (void)hipEventDestroy(im->xs_ev[i]);
-    if (im->loss_status) (void)hipHostFree(im->loss_status);
-    if (im->wait_ev) (void)hipEventDestroy(im->wait_ev);
-    if (im->defer_own_ev) (void)hipEventDestroy(im->defer_own_ev);
-    if (im->d2h_pin) (void)hipHostFree(im->d2h_pin);
-    for (hipEvent_t& e : im->d2h_tev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(im->d_flag);
-    (void)hipFree(im->d_small);
     delete im;
   }
   delete h;
@@ -131,7 +102,7 @@ const char* ccz_last_error(ccz_handle h) { return h ? h->err.c_str() : "null han
 int ccz_set_stream(ccz_handle h, void* s) {
   CCZ_GUARD(h, {
     CCZ_HIP(hipStreamSynchronize(stream(h)));
-    h->stream = s ? s : static_cast<void*>(impl(h)->own_stream);       // NULL: back to the handle's own stream
+    h->stream = s ? s : static_cast<void*>(impl(h)->own_stream.get());       // NULL: back to the handle's own stream
     impl(h)->adopted = false;
   })
 }
@@ -145,10 +116,11 @@ int ccz_sync(ccz_handle h) { CCZ_GUARD(h, sync(h)) }
 static void stream_join(ccz_ctx* c, hipStream_t from, hipStream_t to, int slot) {
   if (from == to) return;
   Impl* im = impl(c);
-  const bool implicit = (from == im->own_stream && to == nullptr) || (from == nullptr && to == im->own_stream);
+  const hipStream_t own = im->own_stream.get();
+  const bool implicit = (from == own && to == nullptr) || (from == nullptr && to == own);
   if (implicit) return;                                                // legacy null-stream ordering
-  if (!im->xs_ev[slot]) CCZ_HIP(hipEventCreateWithFlags(&im->xs_ev[slot], hipEventDisableTiming));
-  const hipError_t rec = hipEventRecord(im->xs_ev[slot], from);
+  if (!im->xs_ev[slot]) CCZ_HIP(hipEventCreateWithFlags(im->xs_ev[slot].out(), hipEventDisableTiming));
+  const hipError_t rec = hipEventRecord(im->xs_ev[slot].get(), from);
   if (rec != hipSuccess) {
     (void)hipGetLastError();
     // a DESTROYED source stream has nothing pending: no dependency to establish.  Anything else (a capturing stream, a
@@ -157,15 +129,15 @@ static void stream_join(ccz_ctx* c, hipStream_t from, hipStream_t to, int slot) 
     CCZ_HIP(hipDeviceSynchronize());
     return;
   }
-  CCZ_HIP(hipStreamWaitEvent(to, im->xs_ev[slot], 0));
+  CCZ_HIP(hipStreamWaitEvent(to, im->xs_ev[slot].get(), 0));
 }
 
 // the handle goes back to its own stream (after ccz_stream_adopt), ordered after what it enqueued on the adopted one
 static void stream_home(ccz_ctx* c) {
   Impl* im = impl(c);
-  if (stream(c) == im->own_stream || !im->adopted) return;
-  stream_join(c, stream(c), im->own_stream, 0);
-  c->stream = im->own_stream;
+  if (stream(c) == im->own_stream.get() || !im->adopted) return;
+  stream_join(c, stream(c), im->own_stream.get(), 0);
+  c->stream = im->own_stream.get();
   im->adopted = false;
 }
 
@@ -327,9 +299,9 @@ int ccz_moments_unpack_blocks(ccz_handle h, const double* packed_dev, int64_t D,
       // OWNS behind it and make the next solve wait for it on the device.  (A borrowed event -- ccz_solve_defer --
       // can be destroyed by its owner while still registered; this one lives as long as the handle.)
       Impl* im = impl(h);
-      if (!im->defer_own_ev) CCZ_HIP(hipEventCreateWithFlags(&im->defer_own_ev, hipEventDisableTiming));
-      CCZ_HIP(hipEventRecord(im->defer_own_ev, static_cast<hipStream_t>(on_stream)));
-      im->deferred_event = im->defer_own_ev;
+      if (!im->defer_own_ev) CCZ_HIP(hipEventCreateWithFlags(im->defer_own_ev.out(), hipEventDisableTiming));
+      CCZ_HIP(hipEventRecord(im->defer_own_ev.get(), static_cast<hipStream_t>(on_stream)));
+      im->deferred_event = im->defer_own_ev.get();
     }
   })
 }
@@ -353,12 +325,7 @@ int ccz_moments_last_ms(ccz_handle h, double* gram_ms, double* colsum_ms) {
 
 int ccz_pool_trim(ccz_handle h, size_t* released_bytes) {
   CCZ_GUARD(h, {
-    Impl* im = impl(h);
-    CCZ_HIP(hipStreamSynchronize(stream(h)));       // pooled blocks are recycled in stream order: nothing may still use them
-    size_t freed = 0;
-    for (auto it = im->pool.begin(); it != im->pool.end();) {
-      if (!it->used) { freed += it->bytes; (void)hipFree(it->p); it = im->pool.erase(it); } else ++it;
-    }
+    const size_t freed = pool_trim(h);
     if (released_bytes) *released_bytes = freed;
   })
 }
@@ -445,16 +412,11 @@ int ccz_cholinv(ccz_handle h, int count, double* const* A_dev, const int64_t* d,
       T[b] = DBuf(h, (d[b] + 63) / 64 * 4096);
       Tp[b] = T[b].get();
     }
-    int* info_dev = static_cast<int*>(dev_alloc(h, 8 * sizeof(int)));
+    PoolBuf<int> info_dev(h, 8);
     int got[8];
-    try {
-      cholinv_batched(h, count, A_dev, d, d, L_dev, d, X_dev, d, Tp.data(), info_dev);
-      d2h(h, got, info_dev, size_t(count) * sizeof(int));
-    } catch (...) {
-      dev_free(h, info_dev);
-      throw;
-    }
-    dev_free(h, info_dev);
+    cholinv_batched(h, count, A_dev, d, d, L_dev, d, X_dev, d, Tp.data(), info_dev);
+    d2h(h, got, info_dev, size_t(count) * sizeof(int));
+    info_dev.reset();
     for (int b = 0; b < count; ++b)
       if (got[b] != 0x7fffffff) fail(CCZ_ENOTSPD, "cholinv: matrix %d is not positive definite (pivot %d)", b, got[b] - 1);
   })

@@ -1320,17 +1320,11 @@ static int cholinv_form() {
 static ChainSync* chain_sync_for(ccz_ctx* c) {
   Impl* im = impl(c);
   hipStream_t st = stream(c);
-  for (auto& e : im->chain_sync)
-    if (e.first == static_cast<void*>(st)) return static_cast<ChainSync*>(e.second);
-  if (im->chain_sync.size() >= 32) return nullptr;
+  if (void* p = im->chain_sync.find(st)) return static_cast<ChainSync*>(p);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   if (cs != hipStreamCaptureStatusNone) return nullptr;      // no allocation inside a capture: the launch-per-link form runs
-  void* p = nullptr;
-  if (hipMalloc(&p, sizeof(ChainSync)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemsetAsync(p, 0, sizeof(ChainSync), st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return nullptr; }
-  im->chain_sync.emplace_back(static_cast<void*>(st), p);
-  return static_cast<ChainSync*>(p);
+  return static_cast<ChainSync*>(im->chain_sync.get(st, sizeof(ChainSync)));
 }
 
 // CCZ_CHOLINV_CHAIN=0: the launch-per-link form (rounds 2-4).  CCZ_CHAIN_WGS: workgroups of the persistent launch
@@ -1361,8 +1355,8 @@ static bool chain_launch(ccz_ctx* c, const CholInvBatch& bt, int nbmax, int* inf
   const int debug = env::once(env::CHAIN_DEBUG);     // stamps of matrix 0's chain workgroup, printed per launch
   unsigned long long* dbg = nullptr;
   if (debug) {
-    if (!im->chain_dbg) CCZ_HIP(hipMalloc(&im->chain_dbg, 8 * (CH_MAXNB + 1) * sizeof(unsigned long long)));
-    dbg = static_cast<unsigned long long*>(im->chain_dbg);
+    if (!im->chain_dbg) CCZ_HIP(hipMalloc(im->chain_dbg.out(), 8 * (CH_MAXNB + 1) * sizeof(unsigned long long)));
+    dbg = static_cast<unsigned long long*>(im->chain_dbg.get());
     CCZ_HIP(hipMemsetAsync(dbg, 0, 8 * (CH_MAXNB + 1) * sizeof(unsigned long long), stream(c)));
   }
   if (form == 2) hipLaunchKernelGGL(k_cholinv_chain<2>, dim3(grid), dim3(256), CHAIN_LDS, stream(c), bt, plan, sy, info_dev, dbg);

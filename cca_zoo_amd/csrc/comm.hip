@@ -198,40 +198,37 @@ int ccz_moments_exchange(ccz_handle h, double* moments_dev, int64_t D, const int
     const int64_t count = D * (D + 1) / 2 + D + 1, n_tail = count - n_head;
     if (n_tail < 0) fail(CCZ_EINVAL, "moments_exchange: dims do not sum to D");
     hipStream_t s0 = stream(h);
-    if (!im->xchg_stream) {
-      CCZ_HIP(hipStreamCreateWithFlags(&im->xchg_stream, hipStreamNonBlocking));
-      for (auto& e : im->xchg_ev) CCZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    hipStream_t sx = im->xchg_stream;
+    if (!im->xchg && !make_side_stream(im->xchg)) fail(CCZ_EHIP, "moments_exchange: cannot create the exchange stream and its events");
+    hipStream_t sx = im->xchg->st.get();
+    hipEvent_t xev[3] = {im->xchg->ev[0].get(), im->xchg->ev[1].get(), im->xchg->ev[2].get()};
     // the buffer may still be read by the previous fit's tail unpack (a caller that exchanged and never solved)
-    CCZ_HIP(hipStreamWaitEvent(s0, im->xchg_ev[2], 0));
+    CCZ_HIP(hipStreamWaitEvent(s0, xev[2], 0));
     if (im->xchg_cap < size_t(count) * 8) {
       CCZ_HIP(hipStreamSynchronize(sx));
       CCZ_HIP(hipStreamSynchronize(s0));
-      if (im->xchg_buf) CCZ_HIP(hipFree(im->xchg_buf));
-      im->xchg_buf = nullptr;
+      im->xchg_buf.reset();
       im->xchg_cap = 0;
-      CCZ_HIP(hipMalloc(&im->xchg_buf, size_t(count) * 8));
+      CCZ_HIP(hipMalloc(im->xchg_buf.out(), size_t(count) * 8));
       im->xchg_cap = size_t(count) * 8;
     }
-    double* packed = static_cast<double*>(im->xchg_buf);
+    double* packed = static_cast<double*>(im->xchg_buf.get());
     moments_blocks(h, true, moments_dev, D, dims, n_views, packed, 3, nullptr);
     fill2d(h, 1, 1, packed + n_head - 1, 1, double(n_local));
-    CCZ_HIP(hipEventRecord(im->xchg_ev[0], s0));
-    CCZ_HIP(hipStreamWaitEvent(sx, im->xchg_ev[0], 0));
+    CCZ_HIP(hipEventRecord(xev[0], s0));
+    CCZ_HIP(hipStreamWaitEvent(sx, xev[0], 0));
     check(r, r.AllReduce(packed, packed, size_t(n_head), kFloat64, kSum, im->comm, sx), "ncclAllReduce (head)");
-    CCZ_HIP(hipEventRecord(im->xchg_ev[1], sx));
+    CCZ_HIP(hipEventRecord(xev[1], sx));
     if (n_tail > 0) {
       check(r, r.AllReduce(packed + n_head, packed + n_head, size_t(n_tail), kFloat64, kSum, im->comm, sx), "ncclAllReduce (tail)");
       moments_blocks(h, false, moments_dev, D, dims, n_views, packed, 2, sx);
     }
-    CCZ_HIP(hipEventRecord(im->xchg_ev[2], sx));
-    CCZ_HIP(hipStreamWaitEvent(s0, im->xchg_ev[1], 0));
+    CCZ_HIP(hipEventRecord(xev[2], sx));
+    CCZ_HIP(hipStreamWaitEvent(s0, xev[1], 0));
     moments_blocks(h, false, moments_dev, D, dims, n_views, packed, 1, nullptr);
     double nt = 0.0;
     d2h(h, &nt, packed + n_head - 1, 8);                    // waits for the head only; the tail is still in flight
     *n_total_out = int64_t(nt + 0.5);
-    if (n_tail > 0) im->deferred_event = im->xchg_ev[2];    // consumed by the next solve (ops_hip.hip: wait_deferred)
+    if (n_tail > 0) im->deferred_event = xev[2];    // consumed by the next solve (ops_hip.hip: wait_deferred)
   })
 }
 

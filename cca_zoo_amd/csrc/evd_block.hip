@@ -743,13 +743,12 @@ int bj_max_gram_split() {
 }
 
 struct StatusBuf {     // BjStatus followed by one "pair at rest" flag per pair
-  ccz_ctx* c;
+  PoolBuf<char> mem;
   BjStatus* dev;
   int* ident;
-  StatusBuf(ccz_ctx* c_, int np) : c(c_), dev(static_cast<BjStatus*>(dev_alloc(c_, sizeof(BjStatus) + size_t(np) * sizeof(int)))) {
+  StatusBuf(ccz_ctx* c, int np) : mem(c, int64_t(sizeof(BjStatus) + size_t(np) * sizeof(int))), dev(reinterpret_cast<BjStatus*>(mem.get())) {
     ident = reinterpret_cast<int*>(dev + 1);
   }
-  ~StatusBuf() { dev_free(c, dev); }
 };
 
 constexpr size_t kApplyLds = size_t(BJP) * (AP_SB + AP_SX) * 8;     // 74752 B: two workgroups per CU

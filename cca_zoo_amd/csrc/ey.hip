@@ -441,12 +441,8 @@ struct EyState : FitState<EyStatus> {
   double* small = nullptr;   // zmean | V | vblend | B | reward
   double* Bpart = nullptr;
   int* idx_dev[2] = {nullptr, nullptr};   // the chunk's row indices ride on the driver's slots and events
-  int* idx_pin[2] = {nullptr, nullptr};
+  PinMem<int> idx_pin[2];
   long long enqueued = 0;    // steps enqueued since the last set_weights
-  ~EyState() {
-    for (int i = 0; i < 2; ++i)
-      if (idx_pin[i]) (void)hipHostFree(idx_pin[i]);
-  }
   EyScratch scratch() const {
     EyScratch s;
     s.zmean = small;
@@ -554,7 +550,7 @@ EyState* ey_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t k, in
     S.drv.create(c);
     for (int i = 0; i < 2; ++i) {
       S.idx_dev[i] = S.get<int>(c, size_t(chunk) * bs);
-      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&S.idx_pin[i]), size_t(chunk) * bs * 4, hipHostMallocDefault));
+      CCZ_HIP(hipHostMalloc(S.idx_pin[i].out(), size_t(chunk) * bs * 4, hipHostMallocDefault));
     }
   });
 }
@@ -592,7 +588,7 @@ void ey_set_weights(ccz_ctx* c, EyState& S, const double* W_host) {
 // upload `rows` x bs host indices into slot `slot` (waits for the slot's previous chunk); returns the device pointer
 const int* upload_idx(ccz_ctx* c, EyState& S, int slot, const int64_t* idx_host, int64_t rows, int64_t n_rows_data) {
   S.drv.wait(slot);
-  int* pin = S.idx_pin[slot];
+  int* pin = S.idx_pin[slot].get();
   for (int64_t e = 0; e < rows * S.bs; ++e) {
     const int64_t v = idx_host[e];
     if (v < 0 || v >= n_rows_data) fail(CCZ_EINVAL, "ey: row index %lld out of range [0, %lld)", (long long)v, (long long)n_rows_data);

@@ -19,39 +19,33 @@ __device__ __forceinline__ bool fit_stopped(const Status* st) { return st->stopp
 template <typename Status>
 struct ChunkDriver {
   Status* dev = nullptr;                 // the device status, written by the family's finish kernel
-  Status* pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PinMem<Status> pin[2];
+  Event ev[2];
   bool used[2] = {false, false};
   int slot = 0;
 
-  // throws on failure; destroy() then frees what exists
+  // throws on failure; what exists then goes with the state
   void create(ccz_ctx* c) {
     dev = static_cast<Status*>(dev_alloc(c, sizeof(Status)));
     for (int i = 0; i < 2; ++i) {
-      CCZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&pin[i]), sizeof(Status), hipHostMallocDefault));
-      CCZ_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+      CCZ_HIP(hipHostMalloc(pin[i].out(), sizeof(Status), hipHostMallocDefault));
+      CCZ_HIP(hipEventCreateWithFlags(ev[i].out(), hipEventDisableTiming));
     }
   }
-  // the handle's stream must be idle
-  void destroy(ccz_ctx* c) {
-    dev_free(c, dev);
-    for (int i = 0; i < 2; ++i) {
-      if (pin[i]) (void)hipHostFree(pin[i]);
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-  }
+  // the handle's stream must be idle (the pinned slots and the events go with the state)
+  void destroy(ccz_ctx* c) { dev_free(c, dev); }
   // a new fit on this state, after a handle sync: no slot holds a chunk any more
   void reset() { used[0] = used[1] = false; }
   // wait for the chunk published in slot s: its status copy (valid on the host now), or null when the slot is unused
   const Status* wait(int s) {
     if (!used[s]) return nullptr;
-    CCZ_HIP(hipEventSynchronize(ev[s]));
-    return pin[s];
+    CCZ_HIP(hipEventSynchronize(ev[s].get()));
+    return pin[s].get();
   }
   // behind the chunk just enqueued: copy the status to the current slot, record its event, move to the other slot
   void publish(ccz_ctx* c) {
-    CCZ_HIP(hipMemcpyAsync(pin[slot], dev, sizeof(Status), hipMemcpyDeviceToHost, stream(c)));
-    CCZ_HIP(hipEventRecord(ev[slot], stream(c)));
+    CCZ_HIP(hipMemcpyAsync(pin[slot].get(), dev, sizeof(Status), hipMemcpyDeviceToHost, stream(c)));
+    CCZ_HIP(hipEventRecord(ev[slot].get(), stream(c)));
     used[slot] = true;
     slot ^= 1;
   }

@@ -651,7 +651,8 @@ void gemm_f32_big(ccz_ctx* c, int64_t M, int64_t N, int64_t K, double alpha, con
                   const double* B, int64_t ldb, double beta, float* C, int64_t ldc, const double* bias_row) {
   hipStream_t st = stream(c);
   if (tall_eligible(M, N, K, lda, A, C)) {
-    float* B32 = static_cast<float*>(dev_alloc(c, size_t(K + 1) * TN * 4));
+    PoolBuf<float> B32_own(c, (K + 1) * TN);      // pooled scratch is recycled in stream order: no host wait
+    float* B32 = B32_own;
     float* bias32 = bias_row ? B32 + K * TN : nullptr;
     hipLaunchKernelGGL(k_f64_to_f32_pad, dim3((unsigned)std::min<int64_t>((K * TN + 255) / 256, 1 << 20)), dim3(256), 0, st, K,
                        N, int64_t(TN), B, ldb, B32);
@@ -674,10 +675,10 @@ void gemm_f32_big(ccz_ctx* c, int64_t M, int64_t N, int64_t K, double alpha, con
                          A, lda, B32, float(beta), C, ldc, bias32);
     }
     CCZ_LAUNCH_CHECK();
-    dev_free(c, B32);                    // pooled scratch is recycled in stream order: no host wait
     return;
   }
-  float* B32 = static_cast<float*>(dev_alloc(c, size_t(K) * N * 4 + (bias_row ? size_t(N) * 4 : 0)));
+  PoolBuf<float> B32_own(c, K * N + (bias_row ? N : 0));
+  float* B32 = B32_own;
   float* bias32 = bias_row ? B32 + K * N : nullptr;
   {
     const int64_t total = K * N;
@@ -703,7 +704,6 @@ void gemm_f32_big(ccz_ctx* c, int64_t M, int64_t N, int64_t K, double alpha, con
                        N, float(beta), C, ldc, bias32);
   }
   CCZ_LAUNCH_CHECK();
-  dev_free(c, B32);                      // pooled scratch is recycled in stream order: no host wait
 }
 
 // ---------------------------------------------------------------------------------------------------

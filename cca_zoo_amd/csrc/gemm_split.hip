@@ -200,39 +200,28 @@ void gemm_split_pair(ccz_ctx* c, int64_t M, int64_t N, int64_t K, int64_t K1, fl
   int64_t tiles_per_launch = std::max<int64_t>(32, int64_t((budget > bytesB ? budget - bytesB : 0) / per_tile) / 32 * 32);
   const int64_t row_tiles_all = (M + 255) / 256;
   tiles_per_launch = std::min(tiles_per_launch, (row_tiles_all + 31) / 32 * 32);
-  char* planesB = static_cast<char*>(dev_alloc(c, bytesB));
-  char* planesA = nullptr;
-  auto release = [&] {
-    if (planesA) dev_free(c, planesA);
-    dev_free(c, planesB);
-  };
-  try {
-    split_k1_layout(c, gamma32, K, N, N, S, planesB);
-    planesA = static_cast<char*>(dev_alloc(c, size_t(std::min(tiles_per_launch, row_tiles_all)) * per_tile));
-    SplitTViews vw{};
-    vw.m = 2;
-    vw.data[0] = A1; vw.ld[0] = lda1; vw.off[0] = 0;
-    vw.data[1] = A2; vw.ld[1] = lda2; vw.off[1] = int(K1);
-    vw.off[2] = int(K);
-    const size_t fifo_bytes = size_t(SP_NST) * SP_STAGE;
-    sp_allow_lds(reinterpret_cast<const void*>(&k_gemm_bf16x2_nn), c->device, int(fifo_bytes));
-    for (int64_t t0 = 0; t0 < row_tiles_all; t0 += tiles_per_launch) {
-      const int64_t tiles = std::min(tiles_per_launch, row_tiles_all - t0);
-      hipLaunchKernelGGL(k_splitT_bf16x2, dim3((unsigned)(S / 4), (unsigned)tiles), dim3(256), 0, st, vw, t0 * 256, M, K, S, mean, planesA);
-      const int64_t rgroups = (tiles + 3) / 4;
-      const int64_t per_group = (col_tiles + 7) / 8 * 32;
-      const int halves = tiles * col_tiles < int64_t(impl(c)->props.multiProcessorCount) ? 2 : 1;
-      const int64_t nblocks = (rgroups + 7) / 8 * per_group * 8 * halves;
-      if (nblocks > 0x7fffffffLL) fail(CCZ_EUNSUP, "gemm (split route): grid too large");
-      hipLaunchKernelGGL(k_gemm_bf16x2_nn, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, M, N, S, tiles, col_tiles, planesA, planesB, alpha,
-                         alpha_dev, corr, C1, ldc1, C2, ldc2, nsplit, t0 * 256, halves);
-      CCZ_LAUNCH_CHECK();
-    }
-  } catch (...) {
-    release();
-    throw;
+  PoolBuf<char> planesB(c, int64_t(bytesB));
+  split_k1_layout(c, gamma32, K, N, N, S, planesB.get());
+  PoolBuf<char> planesA(c, std::min(tiles_per_launch, row_tiles_all) * int64_t(per_tile));
+  SplitTViews vw{};
+  vw.m = 2;
+  vw.data[0] = A1; vw.ld[0] = lda1; vw.off[0] = 0;
+  vw.data[1] = A2; vw.ld[1] = lda2; vw.off[1] = int(K1);
+  vw.off[2] = int(K);
+  const size_t fifo_bytes = size_t(SP_NST) * SP_STAGE;
+  sp_allow_lds(reinterpret_cast<const void*>(&k_gemm_bf16x2_nn), c->device, int(fifo_bytes));
+  for (int64_t t0 = 0; t0 < row_tiles_all; t0 += tiles_per_launch) {
+    const int64_t tiles = std::min(tiles_per_launch, row_tiles_all - t0);
+    hipLaunchKernelGGL(k_splitT_bf16x2, dim3((unsigned)(S / 4), (unsigned)tiles), dim3(256), 0, st, vw, t0 * 256, M, K, S, mean, planesA.get());
+    const int64_t rgroups = (tiles + 3) / 4;
+    const int64_t per_group = (col_tiles + 7) / 8 * 32;
+    const int halves = tiles * col_tiles < int64_t(impl(c)->props.multiProcessorCount) ? 2 : 1;
+    const int64_t nblocks = (rgroups + 7) / 8 * per_group * 8 * halves;
+    if (nblocks > 0x7fffffffLL) fail(CCZ_EUNSUP, "gemm (split route): grid too large");
+    hipLaunchKernelGGL(k_gemm_bf16x2_nn, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, M, N, S, tiles, col_tiles, planesA.get(), planesB.get(), alpha,
+                       alpha_dev, corr, C1, ldc1, C2, ldc2, nsplit, t0 * 256, halves);
+    CCZ_LAUNCH_CHECK();
   }
-  release();
 }
 
 }  // namespace ccz

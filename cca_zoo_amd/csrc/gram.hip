@@ -951,7 +951,7 @@ struct TileTable {
 };
 
 template <typename T>
-TileTable build_tile_table(ccz_ctx* c, const ccz_view* views, int n_views, void** tile_cache) {
+TileTable build_tile_table(ccz_ctx* c, const ccz_view* views, int n_views, PoolBuf<GramTile>* tile_cache) {
   Impl* im = impl(c);
   hipStream_t st = stream(c);
   constexpr bool is32 = sizeof(T) == 4;
@@ -1045,7 +1045,7 @@ TileTable build_tile_table(ccz_ctx* c, const ccz_view* views, int n_views, void*
   GramTile* d_tiles;
   bool tiles_from_handle_cache = false;
   if (tile_cache && *tile_cache) {
-    d_tiles = static_cast<GramTile*>(*tile_cache);
+    d_tiles = tile_cache->get();
   } else if (!tile_cache) {
     // handle-level cache keyed on the table's content (FNV-1a over its bytes): repeated launches on the same buffers
     // (a training loop; the bench's fit loop) enqueue no copy at all.  An evicted entry's buffer is rewritten by a
@@ -1060,31 +1060,30 @@ TileTable build_tile_table(ccz_ctx* c, const ccz_view* views, int n_views, void*
       if (e.hash == hsh && e.bytes == tb) { hit = &e; break; }
     if (!hit) {
       if (im->tile_tabs.size() < 16) {
-        void* dp = nullptr;
-        CCZ_HIP(hipMalloc(&dp, std::max<size_t>(tb, 4096)));
-        im->tile_tabs.push_back({hsh, tb, dp, 0});
+        DevMem<> dp;
+        CCZ_HIP(hipMalloc(dp.out(), std::max<size_t>(tb, 4096)));
+        im->tile_tabs.push_back({hsh, tb, std::move(dp), 0});
         hit = &im->tile_tabs.back();
       } else {
         hit = &im->tile_tabs[0];
         for (auto& e : im->tile_tabs) if (e.tick < hit->tick) hit = &e;
         if (std::max<size_t>(hit->bytes, 4096) < tb) {
           CCZ_HIP(hipStreamSynchronize(st));
-          CCZ_HIP(hipFree(hit->dev));
-          hit->dev = nullptr;
-          CCZ_HIP(hipMalloc(&hit->dev, tb));
+          hit->dev.reset();
+          CCZ_HIP(hipMalloc(hit->dev.out(), tb));
         }
         hit->hash = hsh;
         hit->bytes = tb;
       }
-      h2d_small(c, hit->dev, tiles.data(), tb);
+      h2d_small(c, hit->dev.get(), tiles.data(), tb);
     }
     hit->tick = ++tick;
-    d_tiles = static_cast<GramTile*>(hit->dev);
+    d_tiles = static_cast<GramTile*>(hit->dev.get());
     tiles_from_handle_cache = true;
   } else {
-    d_tiles = static_cast<GramTile*>(dev_alloc(c, tiles.size() * sizeof(GramTile)));
+    *tile_cache = PoolBuf<GramTile>(c, int64_t(tiles.size()));
+    d_tiles = tile_cache->get();
     h2d_small(c, d_tiles, tiles.data(), tiles.size() * sizeof(GramTile));   // through a pinned slot: no stream sync
-    *tile_cache = d_tiles;
   }
 
   TileTable tt;
@@ -1166,7 +1165,7 @@ RowPlan plan_rows(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, int
 // read-back), 2 = always (device-side only, no host synchronisation).  Returns whether the pilot path ran.
 template <typename T>
 bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, double* G, double* s, int64_t D,
-                    bool time_it, void** tile_cache = nullptr, int pilot_mode = 0) {
+                    bool time_it, PoolBuf<GramTile>* tile_cache = nullptr, int pilot_mode = 0) {
   Impl* im = impl(c);
   hipStream_t st = stream(c);
   constexpr bool is32 = sizeof(T) == 4;
@@ -1202,20 +1201,23 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   const double pilot_thr = env::once(env::GRAM_PILOT_RATIO);
   double* s_launch = s;            // column sums of THIS launch's rows (separate from the running sums in pilot modes)
   double* sq = nullptr;
+  PoolBuf<double> s_own;
   if (pilot_mode != 0) {
-    s_launch = static_cast<double*>(dev_alloc(c, size_t(D) * 8 * (pilot_mode == 1 ? 2 : 1)));
+    s_own = PoolBuf<double>(c, D * (pilot_mode == 1 ? 2 : 1));
+    s_launch = s_own;
     zero(c, s_launch, size_t(D) * 8 * (pilot_mode == 1 ? 2 : 1));
     if (pilot_mode == 1) sq = s_launch + D;
   }
-  if (time_it) CCZ_HIP(hipEventRecord(im->ev[2], st));
+  if (time_it) CCZ_HIP(hipEventRecord(im->ev[2].get(), st));
   int64_t off = 0;
+  PoolBuf<float> pilot_own;
   float* pilot = nullptr;
   if (split) {
     // Split route: the exact column sums ride in the split pass (one read of the rows instead of two), so the pilot cannot be
     // their mean -- it is the mean of a strided sample of <= 2048 rows spread over the whole launch (sorted / drifting inputs
     // included).  Any pilot near the mean serves: the fix-up  sum x x' = sum (x-p)(x-p)' + p s' + s p' - n p p'  is exact in p.
     const int64_t nsamp = std::min<int64_t>(n, 2048), stride = n / nsamp;
-    double* samp = static_cast<double*>(dev_alloc(c, size_t(D) * 8));
+    PoolBuf<double> samp(c, D);
     zero(c, samp, size_t(D) * 8);
     for (int v = 0; v < n_views; ++v) {
       const int64_t colblocks = (views[v].cols + 255) / 256;
@@ -1223,12 +1225,12 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
       while (rpb > 16 && colblocks * ((nsamp + rpb - 1) / rpb) < 2 * int64_t(ncu)) rpb /= 2;
       dim3 grid((unsigned)colblocks, (unsigned)((nsamp + rpb - 1) / rpb));
       hipLaunchKernelGGL((k_colsum<T, false>), grid, dim3(256), 0, st, static_cast<const T*>(views[v].data), nsamp, views[v].cols,
-                         views[v].ld * stride, samp + off, static_cast<double*>(nullptr), rpb);
+                         views[v].ld * stride, samp.get() + off, static_cast<double*>(nullptr), rpb);
       off += views[v].cols;
     }
-    pilot = static_cast<float*>(dev_alloc(c, size_t(D) * 4));
-    hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp, D, 1.0 / double(nsamp), pilot);
-    dev_free(c, samp);
+    pilot = pilot_own = PoolBuf<float>(c, D);
+    hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), D, 1.0 / double(nsamp), pilot);
+    samp.reset();
   }
   for (int v = 0; v < n_views && !split; ++v) {
     // enough row blocks to cover the chip even for narrow / short views
@@ -1245,7 +1247,7 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
     off += views[v].cols;
   }
   CCZ_LAUNCH_CHECK();
-  if (time_it) CCZ_HIP(hipEventRecord(im->ev[3], st));
+  if (time_it) CCZ_HIP(hipEventRecord(im->ev[3].get(), st));
   bool use_pilot = pilot_mode == 2;
   if (pilot_mode == 1) {
     // largest |mean| / std over the columns: fp32 accumulation of raw products loses ~ eps32 sqrt(rows) (mean/std)^2 of
@@ -1263,11 +1265,11 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
     use_pilot = worst > pilot_thr;
   }
   if (use_pilot && !split) {
-    pilot = static_cast<float*>(dev_alloc(c, size_t(D) * 4));
+    pilot = pilot_own = PoolBuf<float>(c, D);
     hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, s_launch, D, 1.0 / double(n), pilot);
   }
 
-  if (time_it) CCZ_HIP(hipEventRecord(im->ev[0], st));
+  if (time_it) CCZ_HIP(hipEventRecord(im->ev[0].get(), st));
   const int impl_sel = env::once(env::GRAM_IMPL);
   // pilot-shifted data on a chip-filling grid: the FIFO kernel with the subtraction at the fragment read, on the rows
   // that form whole ring periods; the (< 32) rows left over go through the staged kernel, same pilot
@@ -1275,11 +1277,12 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   const int64_t n_main = n / (FB * FR) * (FB * FR);
   const bool fifo_pilot = is32 && fast && impl_sel != 0 && use_pilot && fifo_pilot_env != 0 && sliced && n_main >= rows_per_wg;
   // staged fp32 kernel on a small grid: per-(chunk, tile) partial sums + one reduce instead of contended atomics
+  PoolBuf<float> partial_own;
   float* partial = nullptr;
   const bool staged32 = is32 && !(fast && impl_sel != 0 && !use_pilot) && !fifo_pilot;
   if (staged32 && ksplit >= 2 && !sliced && !split) {
     const int64_t bytes = ksplit * int64_t(ntiles) * T32 * T32 * 4;
-    if (bytes <= env::gram_partial_cap()) partial = static_cast<float*>(dev_alloc(c, size_t(bytes)));
+    if (bytes <= env::gram_partial_cap()) partial = partial_own = PoolBuf<float>(c, bytes / 4);
   }
   if (split) {
     gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it);
@@ -1323,9 +1326,9 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   if (partial) {
     hipLaunchKernelGGL(k_gram_reduce, dim3(256, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, ksplit, G, D);
     CCZ_LAUNCH_CHECK();
-    dev_free(c, partial);
+    partial_own.reset();
   }
-  if (time_it) CCZ_HIP(hipEventRecord(im->ev[1], st));
+  if (time_it) CCZ_HIP(hipEventRecord(im->ev[1].get(), st));
   if (use_pilot) {
     if (D > 65535) fail(CCZ_EUNSUP, "gram: pilot fix-up supports D <= 65535");
     hipLaunchKernelGGL(k_pilot_fixup, dim3((unsigned)((D + 255) / 256), (unsigned)D), dim3(256), 0, st, G, D, s_launch, double(n), pilot);
@@ -1333,40 +1336,30 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   if (s_launch != s) hipLaunchKernelGGL(k_vec_add, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, s, s_launch, D);
   CCZ_LAUNCH_CHECK();
   if (time_it) {
-    CCZ_HIP(hipEventSynchronize(im->ev[1]));
+    CCZ_HIP(hipEventSynchronize(im->ev[1].get()));
     float g = 0.f, cs = 0.f;
-    CCZ_HIP(hipEventElapsedTime(&g, im->ev[0], im->ev[1]));
-    CCZ_HIP(hipEventElapsedTime(&cs, im->ev[2], im->ev[3]));
+    CCZ_HIP(hipEventElapsedTime(&g, im->ev[0].get(), im->ev[1].get()));
+    CCZ_HIP(hipEventElapsedTime(&cs, im->ev[2].get(), im->ev[3].get()));
     c->last_gram_ms += g;
     c->last_colsum_ms += cs;
   }
   c->last_pilot = use_pilot ? 1 : 0;
-  // scratch goes back to the handle's pool right away: the pool is stream-ordered (one stream per handle), so a later
-  // allocation that reuses a block can only touch it after the kernels enqueued above
-  if (pilot) dev_free(c, pilot);
-  if (s_launch != s) dev_free(c, s_launch);
+  // the pilot and this launch's sums go back to the handle's pool here: the pool is stream-ordered (one stream per handle), so a
+  // later allocation that reuses a block can only touch it after the kernels enqueued above
   return use_pilot;
 }
 
 // pinned bounce buffers + copy stream of the host-input pipeline; false if pinned memory is unavailable
 bool ensure_pipe(ccz_ctx* c, size_t bytes) {
   Impl* im = impl(c);
-  if (!im->copy_stream) {
-    if (hipStreamCreateWithFlags(&im->copy_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); im->copy_stream = nullptr; return false; }
-    for (int i = 0; i < 4; ++i)
-      if (hipEventCreateWithFlags(&im->pipe_ev[i], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
-  }
-  for (int i = 0; i < 4; ++i) if (!im->pipe_ev[i]) return false;
+  if (!im->pipe && !make_side_stream(im->pipe)) return false;
   if (im->pin_cap >= bytes) return true;
-  for (int i = 0; i < 2; ++i) {
-    if (im->pin_buf[i]) (void)hipHostFree(im->pin_buf[i]);
-    im->pin_buf[i] = nullptr;
-  }
+  for (auto& b : im->pin_buf) b.reset();
   im->pin_cap = 0;
-  for (int i = 0; i < 2; ++i)
-    if (hipHostMalloc(&im->pin_buf[i], bytes, hipHostMallocDefault) != hipSuccess) {
+  for (auto& b : im->pin_buf)
+    if (hipHostMalloc(b.out(), bytes, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
-      for (int j = 0; j < 2; ++j) { if (im->pin_buf[j]) (void)hipHostFree(im->pin_buf[j]); im->pin_buf[j] = nullptr; }
+      for (auto& b2 : im->pin_buf) b2.reset();
       return false;
     }
   im->pin_cap = bytes;
@@ -1412,16 +1405,9 @@ bool colsum_pilot_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n,
   const int64_t rowblocks = (n + rpb - 1) / rpb;
   // arrival counters of k_colsum_pilot: one block of 64 words per STREAM (like the chain kernel's sync block): two losses on
   // one handle enqueued on different streams may overlap, and shared counters would elect the wrong "last row block"
-  unsigned* counters = nullptr;
-  for (auto& e : im->colsum_sync)
-    if (e.first == static_cast<void*>(st)) { counters = static_cast<unsigned*>(e.second); break; }
-  if (!counters) {
-    if (im->colsum_sync.size() >= 32) return false;         // (a caller cycling through streams: the general route)
-    CCZ_HIP(hipMalloc(reinterpret_cast<void**>(&counters), 64 * sizeof(unsigned)));
-    CCZ_HIP(hipMemsetAsync(counters, 0, 64 * sizeof(unsigned), st));
-    im->colsum_sync.emplace_back(static_cast<void*>(st), static_cast<void*>(counters));
-  }
-  double* part = static_cast<double*>(dev_alloc(c, size_t(rowblocks) * D * 8));
+  unsigned* counters = static_cast<unsigned*>(im->colsum_sync.get(st, 64 * sizeof(unsigned)));
+  if (!counters) return false;                              // (a caller cycling through streams: the general route)
+  PoolBuf<double> part(c, rowblocks * D);
   ColsumViews cv{};
   cv.m = n_views;
   cv.off[0] = 0;
@@ -1430,9 +1416,9 @@ bool colsum_pilot_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n,
     cv.ld[v] = views[v].ld;
     cv.off[v + 1] = cv.off[v] + int(views[v].cols);
   }
-  hipLaunchKernelGGL(k_colsum_pilot, dim3((unsigned)colblocks, (unsigned)rowblocks), dim3(256), 0, st, cv, n, D, rpb, part, counters, colsum, pilot,
+  hipLaunchKernelGGL(k_colsum_pilot, dim3((unsigned)colblocks, (unsigned)rowblocks), dim3(256), 0, st, cv, n, D, rpb, part.get(), counters, colsum, pilot,
                      zero_me, nzero);
-  dev_free(c, part);                    // stream-ordered pool: reused only behind the kernel above
+  part.reset();                         // stream-ordered pool: reused only behind the kernel above
   return true;
 }
 
@@ -1467,7 +1453,7 @@ bool gram_partials_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n
     mix(uint64_t(n)); mix(uint64_t(tt.ntiles)); mix(uint64_t(ncu));
     for (unsigned char dflag : tt.diag) mix(dflag);
     for (auto& e : im->k1_plans)
-      if (e.key == key) { fifo_plan_dev = static_cast<int*>(e.dev); fifo_wgs = e.wgs; break; }
+      if (e.key == key) { fifo_plan_dev = e.dev.get(); fifo_wgs = e.wgs; break; }
     if (!fifo_plan_dev) {
       int n_diag = 0;
       for (unsigned char dflag : tt.diag) n_diag += dflag ? 1 : 0;
@@ -1494,11 +1480,11 @@ bool gram_partials_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n
           plan_h[size_t(3 * t + 2)] = int(per * FB * FR);
           first += wgs;
         }
-        void* dp = nullptr;
-        CCZ_HIP(hipMalloc(&dp, plan_h.size() * sizeof(int)));
-        h2d_small(c, dp, plan_h.data(), plan_h.size() * sizeof(int));
-        im->k1_plans.push_back({key, dp, first});
-        fifo_plan_dev = static_cast<int*>(dp);
+        DevMem<int> dp;
+        CCZ_HIP(hipMalloc(dp.out(), plan_h.size() * sizeof(int)));
+        h2d_small(c, dp.get(), plan_h.data(), plan_h.size() * sizeof(int));
+        fifo_plan_dev = dp.get();
+        im->k1_plans.push_back({key, std::move(dp), first});
         fifo_wgs = first;
       }
     }
@@ -1603,81 +1589,81 @@ void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int
     }
   }
   src_pinned = src_pinned && env::once(env::H2D_PINNED_DIRECT) != 0;
-  std::vector<void*> stage(size_t(nslots) * n_views, nullptr);
+  std::vector<PoolBuf<char>> stage(size_t(nslots) * n_views);
   std::vector<ccz_view> dv(size_t(nslots) * n_views);
-  void* tile_tab[2] = {nullptr, nullptr};
-  auto cleanup = [&] {
-    (void)hipStreamSynchronize(stream(c));
-    if (piped) (void)hipStreamSynchronize(im->copy_stream);
-    for (void* p : stage) if (p) dev_free(c, p);
-    for (void* p : tile_tab) if (p) dev_free(c, p);
-  };
-  try {
-    for (int sl = 0; sl < nslots; ++sl)
-      for (int v = 0; v < n_views; ++v) {
-        stage[sl * n_views + v] = dev_alloc(c, size_t(chunk) * views[v].cols * es);
-        dv[sl * n_views + v] = ccz_view{stage[sl * n_views + v], views[v].cols, views[v].cols};
-      }
-    if (piped) {
-      // pooled scratch is recycled in stream order on the handle's stream: make the copy stream a part of that order
-      // before it writes into freshly pooled staging blocks
-      CCZ_HIP(hipEventRecord(im->pipe_ev[2], stream(c)));
-      CCZ_HIP(hipStreamWaitEvent(im->copy_stream, im->pipe_ev[2], 0));
+  PoolBuf<GramTile> tile_tab[2];
+  // leaving, by return or by a throw: the staging blocks go back to the pool only when both streams are done with them (this is
+  // declared after them, hence runs before they are released)
+  struct Drain {
+    ccz_ctx* c; hipStream_t copy;
+    ~Drain() {
+      (void)hipStreamSynchronize(stream(c));
+      if (copy) (void)hipStreamSynchronize(copy);
     }
-    int64_t ci = 0;
-    // Streamed chunks ALWAYS take the pilot-shifted kernel (each chunk with the pilot of its own rows): it hides behind
-    // the PCIe copy (47 GB/s against > 100 TF), needs no read-back, and a decision taken on the first chunk alone
-    // would be wrong for data whose later rows drift away from zero (sorted / padded / time-ordered inputs).
-    const int chunk_mode = pilot_mode == 1 ? 2 : pilot_mode;
-    // The pipeline is bound by the copy; what it cannot hide is the K1 of the LAST chunk.  So the chunks taper towards
-    // the end (each at most half of what is left, down to ~128 MiB): the drain shrinks from one full chunk's K1 to a
-    // few milliseconds, while the bulk still moves in large chunks on which K1 runs at its full rate.
-    const int64_t min_chunk = std::max<int64_t>(64, ((int64_t(128) << 20) / row_bytes) / 64 * 64);
-    int64_t rows = 0;
-    for (int64_t r0 = 0; r0 < n_rows; r0 += rows, ++ci) {
-      const int64_t left = n_rows - r0;
-      rows = std::min(chunk, left);
-      if (piped && left < 2 * chunk && left > min_chunk) rows = std::min(rows, std::max(min_chunk, (left / 2 + 63) / 64 * 64));
-      const int sl = piped ? int(ci & 1) : 0;
-      if (piped) {
-        if (ci >= 2 && !src_pinned) CCZ_HIP(hipEventSynchronize(im->pipe_ev[sl]));   // DMA of chunk ci-2 has drained this bounce buffer
-        if (!src_pinned) pack_rows(static_cast<char*>(im->pin_buf[sl]), views, n_views, es, r0, rows, n_threads);
-        if (ci >= 2) CCZ_HIP(hipStreamWaitEvent(im->copy_stream, im->pipe_ev[2 + sl], 0));   // K1 of chunk ci-2 done with this staging slot
-        size_t off = 0;
-        for (int v = 0; v < n_views; ++v) {
-          const size_t bytes = size_t(rows) * views[v].cols * es;
-          if (src_pinned) {
-            const char* src = static_cast<const char*>(views[v].data) + size_t(r0) * views[v].ld * es;
-            if (views[v].ld == views[v].cols) CCZ_HIP(hipMemcpyAsync(stage[sl * n_views + v], src, bytes, hipMemcpyHostToDevice, im->copy_stream));
-            else CCZ_HIP(hipMemcpy2DAsync(stage[sl * n_views + v], size_t(views[v].cols) * es, src, size_t(views[v].ld) * es,
-                                          size_t(views[v].cols) * es, size_t(rows), hipMemcpyHostToDevice, im->copy_stream));
-          } else {
-            CCZ_HIP(hipMemcpyAsync(stage[sl * n_views + v], static_cast<char*>(im->pin_buf[sl]) + off, bytes, hipMemcpyHostToDevice, im->copy_stream));
-          }
-          off += bytes;
-        }
-        CCZ_HIP(hipEventRecord(im->pipe_ev[sl], im->copy_stream));
-        CCZ_HIP(hipStreamWaitEvent(stream(c), im->pipe_ev[sl], 0));
-      } else {
-        for (int v = 0; v < n_views; ++v) {
-          const char* src = static_cast<const char*>(views[v].data) + size_t(r0) * views[v].ld * es;
-          CCZ_HIP(hipMemcpy2DAsync(stage[v], size_t(views[v].cols) * es, src, size_t(views[v].ld) * es,
-                                   size_t(views[v].cols) * es, size_t(rows), hipMemcpyHostToDevice, stream(c)));
-        }
-        CCZ_HIP(hipStreamSynchronize(stream(c)));
-      }
-      if (dtype == CCZ_F32) {
-        launch_moments<float>(c, &dv[sl * n_views], n_views, rows, G, s, D, false, &tile_tab[sl], chunk_mode);
-      } else {
-        launch_moments<double>(c, &dv[sl * n_views], n_views, rows, G, s, D, false, &tile_tab[sl], 0);
-      }
-      if (piped) CCZ_HIP(hipEventRecord(im->pipe_ev[2 + sl], stream(c)));
+  } drain{c, piped ? im->pipe->st.get() : nullptr};
+  for (int sl = 0; sl < nslots; ++sl)
+    for (int v = 0; v < n_views; ++v) {
+      stage[sl * n_views + v] = PoolBuf<char>(c, chunk * views[v].cols * int64_t(es));
+      dv[sl * n_views + v] = ccz_view{stage[sl * n_views + v].get(), views[v].cols, views[v].cols};
     }
-  } catch (...) {
-    cleanup();
-    throw;
+  hipStream_t copy = drain.copy;
+  hipEvent_t pev[4] = {};
+  for (int i = 0; piped && i < 4; ++i) pev[i] = im->pipe->ev[i].get();
+  if (piped) {
+    // pooled scratch is recycled in stream order on the handle's stream: make the copy stream a part of that order
+    // before it writes into freshly pooled staging blocks
+    CCZ_HIP(hipEventRecord(pev[2], stream(c)));
+    CCZ_HIP(hipStreamWaitEvent(copy, pev[2], 0));
   }
-  cleanup();
+  int64_t ci = 0;
+  // Streamed chunks ALWAYS take the pilot-shifted kernel (each chunk with the pilot of its own rows): it hides behind
+  // the PCIe copy (47 GB/s against > 100 TF), needs no read-back, and a decision taken on the first chunk alone
+  // would be wrong for data whose later rows drift away from zero (sorted / padded / time-ordered inputs).
+  const int chunk_mode = pilot_mode == 1 ? 2 : pilot_mode;
+  // The pipeline is bound by the copy; what it cannot hide is the K1 of the LAST chunk.  So the chunks taper towards
+  // the end (each at most half of what is left, down to ~128 MiB): the drain shrinks from one full chunk's K1 to a
+  // few milliseconds, while the bulk still moves in large chunks on which K1 runs at its full rate.
+  const int64_t min_chunk = std::max<int64_t>(64, ((int64_t(128) << 20) / row_bytes) / 64 * 64);
+  int64_t rows = 0;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += rows, ++ci) {
+    const int64_t left = n_rows - r0;
+    rows = std::min(chunk, left);
+    if (piped && left < 2 * chunk && left > min_chunk) rows = std::min(rows, std::max(min_chunk, (left / 2 + 63) / 64 * 64));
+    const int sl = piped ? int(ci & 1) : 0;
+    if (piped) {
+      if (ci >= 2 && !src_pinned) CCZ_HIP(hipEventSynchronize(pev[sl]));   // DMA of chunk ci-2 has drained this bounce buffer
+      if (!src_pinned) pack_rows(static_cast<char*>(im->pin_buf[sl].get()), views, n_views, es, r0, rows, n_threads);
+      if (ci >= 2) CCZ_HIP(hipStreamWaitEvent(copy, pev[2 + sl], 0));   // K1 of chunk ci-2 done with this staging slot
+      size_t off = 0;
+      for (int v = 0; v < n_views; ++v) {
+        const size_t bytes = size_t(rows) * views[v].cols * es;
+        if (src_pinned) {
+          const char* src = static_cast<const char*>(views[v].data) + size_t(r0) * views[v].ld * es;
+          if (views[v].ld == views[v].cols) CCZ_HIP(hipMemcpyAsync(stage[sl * n_views + v].get(), src, bytes, hipMemcpyHostToDevice, copy));
+          else CCZ_HIP(hipMemcpy2DAsync(stage[sl * n_views + v].get(), size_t(views[v].cols) * es, src, size_t(views[v].ld) * es,
+                                        size_t(views[v].cols) * es, size_t(rows), hipMemcpyHostToDevice, copy));
+        } else {
+          CCZ_HIP(hipMemcpyAsync(stage[sl * n_views + v].get(), static_cast<char*>(im->pin_buf[sl].get()) + off, bytes, hipMemcpyHostToDevice, copy));
+        }
+        off += bytes;
+      }
+      CCZ_HIP(hipEventRecord(pev[sl], copy));
+      CCZ_HIP(hipStreamWaitEvent(stream(c), pev[sl], 0));
+    } else {
+      for (int v = 0; v < n_views; ++v) {
+        const char* src = static_cast<const char*>(views[v].data) + size_t(r0) * views[v].ld * es;
+        CCZ_HIP(hipMemcpy2DAsync(stage[v].get(), size_t(views[v].cols) * es, src, size_t(views[v].ld) * es,
+                                 size_t(views[v].cols) * es, size_t(rows), hipMemcpyHostToDevice, stream(c)));
+      }
+      CCZ_HIP(hipStreamSynchronize(stream(c)));
+    }
+    if (dtype == CCZ_F32) {
+      launch_moments<float>(c, &dv[sl * n_views], n_views, rows, G, s, D, false, &tile_tab[sl], chunk_mode);
+    } else {
+      launch_moments<double>(c, &dv[sl * n_views], n_views, rows, G, s, D, false, &tile_tab[sl], 0);
+    }
+    if (piped) CCZ_HIP(hipEventRecord(pev[2 + sl], stream(c)));
+  }
 }
 
 }  // namespace ccz

@@ -352,9 +352,9 @@ static SplitTables split_tables(ccz_ctx* c, const int64_t* cols, int n_views) {
   tb.np = np;
   for (auto& e : im->split_tabs)
     if (e.key == key && e.np == np) {                   // the hot path: a lookup, no allocation
-      tb.panels = static_cast<const SplitPanel*>(e.panels);
-      tb.tiles = static_cast<const SplitTile*>(e.tiles);
-      tb.gtiles = static_cast<const GramTile*>(e.gtiles);
+      tb.panels = static_cast<const SplitPanel*>(e.panels.get());
+      tb.tiles = static_cast<const SplitTile*>(e.tiles.get());
+      tb.gtiles = static_cast<const GramTile*>(e.gtiles.get());
       tb.ntiles = e.ntiles;
       return tb;
     }
@@ -383,20 +383,19 @@ static SplitTables split_tables(ccz_ctx* c, const int64_t* cols, int n_views) {
   tb.ntiles = int(tiles.size());
   if (im->split_tabs.size() >= 32) {                      // a caller cycling through many shapes: start over
     CCZ_HIP(hipStreamSynchronize(stream(c)));
-    for (auto& e : im->split_tabs) { (void)hipFree(e.panels); (void)hipFree(e.tiles); (void)hipFree(e.gtiles); }
     im->split_tabs.clear();
   }
-  void *dp = nullptr, *dt = nullptr, *dg = nullptr;
-  CCZ_HIP(hipMalloc(&dp, std::max<size_t>(panels.size() * sizeof(SplitPanel), 256)));
-  CCZ_HIP(hipMalloc(&dt, std::max<size_t>(tiles.size() * sizeof(SplitTile), 256)));
-  CCZ_HIP(hipMalloc(&dg, std::max<size_t>(gt.size() * sizeof(GramTile), 256)));
-  h2d_small(c, dp, panels.data(), panels.size() * sizeof(SplitPanel));
-  h2d_small(c, dt, tiles.data(), tiles.size() * sizeof(SplitTile));
-  h2d_small(c, dg, gt.data(), gt.size() * sizeof(GramTile));
-  im->split_tabs.push_back({key, dp, dt, dg, tb.np, tb.ntiles});
-  tb.panels = static_cast<const SplitPanel*>(dp);
-  tb.tiles = static_cast<const SplitTile*>(dt);
-  tb.gtiles = static_cast<const GramTile*>(dg);
+  DevMem<> dp, dt, dg;
+  CCZ_HIP(hipMalloc(dp.out(), std::max<size_t>(panels.size() * sizeof(SplitPanel), 256)));
+  CCZ_HIP(hipMalloc(dt.out(), std::max<size_t>(tiles.size() * sizeof(SplitTile), 256)));
+  CCZ_HIP(hipMalloc(dg.out(), std::max<size_t>(gt.size() * sizeof(GramTile), 256)));
+  h2d_small(c, dp.get(), panels.data(), panels.size() * sizeof(SplitPanel));
+  h2d_small(c, dt.get(), tiles.data(), tiles.size() * sizeof(SplitTile));
+  h2d_small(c, dg.get(), gt.data(), gt.size() * sizeof(GramTile));
+  tb.panels = static_cast<const SplitPanel*>(dp.get());
+  tb.tiles = static_cast<const SplitTile*>(dt.get());
+  tb.gtiles = static_cast<const GramTile*>(dg.get());
+  im->split_tabs.push_back({key, std::move(dp), std::move(dt), std::move(dg), tb.np, tb.ntiles});
   return tb;
 }
 
@@ -574,16 +573,10 @@ static hipStream_t split_side_stream(ccz_ctx* c) {
   Impl* im = impl(c);
   const int ncu = std::max(1, im->props.multiProcessorCount);
   const int cus = env::live(env::SPLIT_PIPE_CUS);
-  if (im->split_stream_tried && cus == im->split_stream_req) return im->split_stream;
-  if (im->split_stream) {
-    (void)hipStreamSynchronize(im->split_stream);
-    (void)hipStreamDestroy(im->split_stream);
-    im->split_stream = nullptr;
-  }
-  im->split_stream_tried = true;
-  im->split_stream_req = cus;
-  im->split_stream_cus = 0;
-  hipStream_t st = nullptr;
+  if (im->split_side && cus == im->split_side->req) return im->split_side->st.get();
+  if (im->split_side && im->split_side->st) (void)hipStreamSynchronize(im->split_side->st.get());
+  Impl::SplitSide side;
+  side.req = cus;
   if (cus > 0 && cus < ncu && ncu % 8 == 0) {
     // bit i set iff (i / 8) % stride == 0: 8-bit groups, every stride-th one -- uniform over the XCDs whether the runtime deals the
     // mask's bits round-robin over the XCDs (bit i -> XCD i % 8) or XCD by XCD
@@ -592,12 +585,12 @@ static hipStream_t split_side_stream(ccz_ctx* c) {
     int set = 0;
     for (int i = 0; i < ncu; ++i)
       if ((i / 8) % stride == 0) { mask[size_t(i >> 5)] |= 1u << (i & 31); ++set; }
-    if (hipExtStreamCreateWithCUMask(&st, uint32_t(mask.size()), mask.data()) == hipSuccess) im->split_stream_cus = set;
-    else { (void)hipGetLastError(); st = nullptr; }
+    if (hipExtStreamCreateWithCUMask(side.st.out(), uint32_t(mask.size()), mask.data()) == hipSuccess) side.cus = set;
+    else { (void)hipGetLastError(); side.st.reset(); }
   }
-  if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }
-  im->split_stream = st;
-  return st;
+  if (!side.st && hipStreamCreateWithFlags(side.st.out(), hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); side.st.reset(); }
+  im->split_side = std::move(side);     // (an earlier side stream, drained above, is destroyed here)
+  return im->split_side->st.get();
 }
 
 // G (upper tiles) += sum over rows of d d' for d = x - pilot (pilot may be null: d = x), through the split-bf16 route;
@@ -618,136 +611,133 @@ void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   const bool aligned = split_views_arg(views, n_views, &vws);
   const int np = tb.np, ntiles = tb.ntiles;
   const SplitTile* d_tiles = tb.tiles;
-  double* msq = static_cast<double*>(dev_alloc(c, size_t(D) * 8));
+  PoolBuf<double> msq_own(c, D);
+  PoolBuf<char> planes_own;
+  PoolBuf<float> partial_own;
+  double* msq = msq_own;
   char* planes = nullptr;
   float* partial = nullptr;
-  bool side_busy = false;                  // split passes enqueued on the side stream that the main stream has not waited for yet
-  auto release = [&] {
-    // (unwinding between the side stream's launches and the main stream's waits: the pool recycles in the order of the MAIN stream)
-    if (side_busy && im->split_stream) (void)hipStreamSynchronize(im->split_stream);
-    if (partial) dev_free(c, partial);
-    if (planes) dev_free(c, planes);
-    dev_free(c, msq);
-  };
+  // unwinding between the side stream's launches and the main stream's waits: the pool recycles in the order of the MAIN stream, so
+  // the side stream is drained before the buffers above go back (this is declared after them, hence unwinds before them)
+  struct Drain {
+    hipStream_t side = nullptr;            // set while split passes on the side stream have not been waited for by the main stream
+    ~Drain() { if (side) (void)hipStreamSynchronize(side); }
+  } drain;
+  // ---- rows per launch (scratch budget) and per workgroup ----
+  const int ncu = std::max(1, im->props.multiProcessorCount);
+  const int64_t max_steps = std::max<int64_t>(1, env::live(env::SPLIT_ROWS) / SP_K);
+  const double per_row = double(np) * SP_PSTEP / SP_K + double(ntiles) * (SP_T * SP_T * 4) / double(max_steps * SP_K);
+  const size_t budget = split_scratch_budget(c);
+  int64_t launch_rows = int64_t(double(budget) / per_row) / (max_steps * SP_K) * (max_steps * SP_K);
+  launch_rows = std::max<int64_t>(launch_rows, max_steps * SP_K);
+  const int64_t n_launch = (n + launch_rows - 1) / launch_rows;
+  launch_rows = ((n + n_launch - 1) / n_launch + SP_K - 1) / SP_K * SP_K;       // equal super-chunks
+  const size_t fifo_bytes = size_t(SP_NST) * SP_STAGE;
+  sp_allow_lds(reinterpret_cast<const void*>(&k_gram_bf16x2), c->device, int(fifo_bytes));
+  c->last_split_ms = c->last_mfma_ms = c->last_reduce_ms = 0.0;
+  size_t planes_cap = 0, partial_cap = 0;
+  bool launched = false;
+ retry_smaller:
   try {
-    // ---- rows per launch (scratch budget) and per workgroup ----
-    const int ncu = std::max(1, im->props.multiProcessorCount);
-    const int64_t max_steps = std::max<int64_t>(1, env::live(env::SPLIT_ROWS) / SP_K);
-    const double per_row = double(np) * SP_PSTEP / SP_K + double(ntiles) * (SP_T * SP_T * 4) / double(max_steps * SP_K);
-    const size_t budget = split_scratch_budget(c);
-    int64_t launch_rows = int64_t(double(budget) / per_row) / (max_steps * SP_K) * (max_steps * SP_K);
-    launch_rows = std::max<int64_t>(launch_rows, max_steps * SP_K);
-    const int64_t n_launch = (n + launch_rows - 1) / launch_rows;
-    launch_rows = ((n + n_launch - 1) / n_launch + SP_K - 1) / SP_K * SP_K;       // equal super-chunks
-    const size_t fifo_bytes = size_t(SP_NST) * SP_STAGE;
-    sp_allow_lds(reinterpret_cast<const void*>(&k_gram_bf16x2), c->device, int(fifo_bytes));
-    c->last_split_ms = c->last_mfma_ms = c->last_reduce_ms = 0.0;
-    size_t planes_cap = 0, partial_cap = 0;
-    bool launched = false;
-   retry_smaller:
-    try {
-    for (int64_t r0 = 0; r0 < n; r0 += launch_rows) {
-      const int64_t rows = std::min(launch_rows, n - r0);
-      // row pieces of this super-chunk: the split pass of piece p + 1 runs on the side stream under the MFMA kernel of piece p
-      std::vector<int64_t> piece_rows = split_pieces(rows, max_steps * SP_K);
-      hipStream_t side = piece_rows.size() > 1 ? split_side_stream(c) : nullptr;
-      if (!side) piece_rows.assign(1, rows);
-      const int npc = int(piece_rows.size());
-      struct Piece { int64_t r0, rows, ksteps, slice0; size_t planes_off; SplitRowPlan rp; };
-      std::vector<Piece> pcs;
-      pcs.resize(size_t(npc));
-      size_t planes_bytes = 0;
-      int64_t slices = 0;
-      {
-        int64_t off = 0;
-        for (int p = 0; p < npc; ++p) {
-          Piece& pc = pcs[size_t(p)];
-          pc.r0 = r0 + off;
-          pc.rows = piece_rows[size_t(p)];
-          pc.ksteps = (pc.rows + SP_K - 1) / SP_K;
-          pc.rp = split_row_plan(pc.ksteps, ntiles, max_steps, ncu);
-          pc.planes_off = planes_bytes;
-          pc.slice0 = slices;
-          planes_bytes += size_t(np) * size_t(pc.ksteps) * SP_PSTEP;
-          slices += pc.rp.ksplit;
-          off += pc.rows;
-        }
-      }
-      const size_t partial_bytes = size_t(slices) * size_t(ntiles) * (SP_T * SP_T * 4);
-      if (planes_bytes > planes_cap) { if (planes) dev_free(c, planes); planes = static_cast<char*>(dev_alloc(c, planes_bytes)); planes_cap = planes_bytes; }
-      if (partial_bytes > partial_cap) { if (partial) dev_free(c, partial); partial = static_cast<float*>(dev_alloc(c, partial_bytes)); partial_cap = partial_bytes; }
-      // events: [0] before split 0, [1] after it (the side stream's go-ahead), [4p + 2] after the MFMA kernel of piece p; per piece
-      // p >= 1: [4p - 1] / [4p] before / after its split (side stream), [4p + 1] after the main stream's wait; [4 npc - 1] after the reduce
-      const size_t nev = size_t(4 * npc);
-      while (im->sp_ev.size() < nev) {
-        hipEvent_t e = nullptr;
-        CCZ_HIP(hipEventCreate(&e));
-        im->sp_ev.push_back(e);
-      }
-      hipEvent_t* ev = im->sp_ev.data();
-      launched = true;                     // (from here on the super-chunks are no larger than this one: no further allocation)
-      side_busy = side != nullptr;
-      zero(c, msq, size_t(D) * 8);
-      if (time_it) CCZ_HIP(hipEventRecord(ev[0], st));
-      launch_split_pass(c, tb, vws, aligned, pcs[0].r0, pcs[0].rows, pcs[0].ksteps, pilot, planes, msq, colsum, st);
-      if (time_it || side) CCZ_HIP(hipEventRecord(ev[1], st));
-      if (side) {
-        // (the go-ahead also orders the side stream behind the zeroing of msq, the pilot and the previous super-chunk's readers of `planes`)
-        CCZ_HIP(hipStreamWaitEvent(side, ev[1], 0));
-        for (int p = 1; p < npc; ++p) {
-          const Piece& pc = pcs[size_t(p)];
-          if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p - 1], side));
-          launch_split_pass(c, tb, vws, aligned, pc.r0, pc.rows, pc.ksteps, pilot, planes + pc.planes_off, msq, colsum, side);
-          CCZ_HIP(hipEventRecord(ev[4 * p], side));
-        }
-      }
+  for (int64_t r0 = 0; r0 < n; r0 += launch_rows) {
+    const int64_t rows = std::min(launch_rows, n - r0);
+    // row pieces of this super-chunk: the split pass of piece p + 1 runs on the side stream under the MFMA kernel of piece p
+    std::vector<int64_t> piece_rows = split_pieces(rows, max_steps * SP_K);
+    hipStream_t side = piece_rows.size() > 1 ? split_side_stream(c) : nullptr;
+    if (!side) piece_rows.assign(1, rows);
+    const int npc = int(piece_rows.size());
+    struct Piece { int64_t r0, rows, ksteps, slice0; size_t planes_off; SplitRowPlan rp; };
+    std::vector<Piece> pcs;
+    pcs.resize(size_t(npc));
+    size_t planes_bytes = 0;
+    int64_t slices = 0;
+    {
+      int64_t off = 0;
       for (int p = 0; p < npc; ++p) {
+        Piece& pc = pcs[size_t(p)];
+        pc.r0 = r0 + off;
+        pc.rows = piece_rows[size_t(p)];
+        pc.ksteps = (pc.rows + SP_K - 1) / SP_K;
+        pc.rp = split_row_plan(pc.ksteps, ntiles, max_steps, ncu);
+        pc.planes_off = planes_bytes;
+        pc.slice0 = slices;
+        planes_bytes += size_t(np) * size_t(pc.ksteps) * SP_PSTEP;
+        slices += pc.rp.ksplit;
+        off += pc.rows;
+      }
+    }
+    const size_t partial_bytes = size_t(slices) * size_t(ntiles) * (SP_T * SP_T * 4);
+    // (the old block goes back BEFORE the larger one is asked for: the pool may hand the same block out again)
+    if (planes_bytes > planes_cap) { planes_own.reset(); planes = planes_own = PoolBuf<char>(c, int64_t(planes_bytes)); planes_cap = planes_bytes; }
+    if (partial_bytes > partial_cap) { partial_own.reset(); partial = partial_own = PoolBuf<float>(c, int64_t(partial_bytes / 4)); partial_cap = partial_bytes; }
+    // events: [0] before split 0, [1] after it (the side stream's go-ahead), [4p + 2] after the MFMA kernel of piece p; per piece
+    // p >= 1: [4p - 1] / [4p] before / after its split (side stream), [4p + 1] after the main stream's wait; [4 npc - 1] after the reduce
+    const size_t nev = size_t(4 * npc);
+    while (im->sp_ev.size() < nev) {
+      Event e;
+      CCZ_HIP(hipEventCreate(e.out()));
+      im->sp_ev.push_back(std::move(e));
+    }
+    hipEvent_t ev[4 * 7];                  // (split_pieces gives at most 7 pieces)
+    for (size_t q = 0; q < nev; ++q) ev[q] = im->sp_ev[q].get();
+    launched = true;                     // (from here on the super-chunks are no larger than this one: no further allocation)
+    drain.side = side;
+    zero(c, msq, size_t(D) * 8);
+    if (time_it) CCZ_HIP(hipEventRecord(ev[0], st));
+    launch_split_pass(c, tb, vws, aligned, pcs[0].r0, pcs[0].rows, pcs[0].ksteps, pilot, planes, msq, colsum, st);
+    if (time_it || side) CCZ_HIP(hipEventRecord(ev[1], st));
+    if (side) {
+      // (the go-ahead also orders the side stream behind the zeroing of msq, the pilot and the previous super-chunk's readers of `planes`)
+      CCZ_HIP(hipStreamWaitEvent(side, ev[1], 0));
+      for (int p = 1; p < npc; ++p) {
         const Piece& pc = pcs[size_t(p)];
-        if (p > 0) {
-          CCZ_HIP(hipStreamWaitEvent(st, ev[4 * p], 0));
-          if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 1], st));
-        }
-        hipLaunchKernelGGL(k_gram_bf16x2, dim3((unsigned)pc.rp.nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, pc.rp.per_xcd, pc.rp.ksplit,
-                           planes + pc.planes_off, pc.ksteps, pc.rp.steps_per_wg, partial + pc.slice0 * int64_t(ntiles) * (SP_T * SP_T));
-        if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 2], st));
+        if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p - 1], side));
+        launch_split_pass(c, tb, vws, aligned, pc.r0, pc.rows, pc.ksteps, pilot, planes + pc.planes_off, msq, colsum, side);
+        CCZ_HIP(hipEventRecord(ev[4 * p], side));
       }
-      side_busy = false;                   // (the main stream has waited for every split pass of the side stream)
-      hipLaunchKernelGGL(k_split_reduce, dim3(64, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, slices, G, D, msq);
-      CCZ_LAUNCH_CHECK();
-      if (time_it) {
-        hipEvent_t last = ev[4 * npc - 1];
-        CCZ_HIP(hipEventRecord(last, st));
-        CCZ_HIP(hipEventSynchronize(last));
-        float a = 0.f;
-        CCZ_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-        c->last_split_ms += a;
-        CCZ_HIP(hipEventElapsedTime(&a, ev[1], ev[2]));
+    }
+    for (int p = 0; p < npc; ++p) {
+      const Piece& pc = pcs[size_t(p)];
+      if (p > 0) {
+        CCZ_HIP(hipStreamWaitEvent(st, ev[4 * p], 0));
+        if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 1], st));
+      }
+      hipLaunchKernelGGL(k_gram_bf16x2, dim3((unsigned)pc.rp.nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, pc.rp.per_xcd, pc.rp.ksplit,
+                         planes + pc.planes_off, pc.ksteps, pc.rp.steps_per_wg, partial + pc.slice0 * int64_t(ntiles) * (SP_T * SP_T));
+      if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 2], st));
+    }
+    drain.side = nullptr;                 // (the main stream has waited for every split pass of the side stream)
+    hipLaunchKernelGGL(k_split_reduce, dim3(64, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, slices, G, D, msq);
+    CCZ_LAUNCH_CHECK();
+    if (time_it) {
+      hipEvent_t last = ev[4 * npc - 1];
+      CCZ_HIP(hipEventRecord(last, st));
+      CCZ_HIP(hipEventSynchronize(last));
+      float a = 0.f;
+      CCZ_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+      c->last_split_ms += a;
+      CCZ_HIP(hipEventElapsedTime(&a, ev[1], ev[2]));
+      c->last_mfma_ms += a;
+      for (int p = 1; p < npc; ++p) {
+        CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p - 1], ev[4 * p]));
+        c->last_split_ms += a;             // (under the previous piece's MFMA kernel: the stage times of a piped launch overlap)
+        CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p + 1], ev[4 * p + 2]));
         c->last_mfma_ms += a;
-        for (int p = 1; p < npc; ++p) {
-          CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p - 1], ev[4 * p]));
-          c->last_split_ms += a;             // (under the previous piece's MFMA kernel: the stage times of a piped launch overlap)
-          CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p + 1], ev[4 * p + 2]));
-          c->last_mfma_ms += a;
-        }
-        CCZ_HIP(hipEventElapsedTime(&a, ev[4 * (npc - 1) + 2], last));
-        c->last_reduce_ms += a;
       }
+      CCZ_HIP(hipEventElapsedTime(&a, ev[4 * (npc - 1) + 2], last));
+      c->last_reduce_ms += a;
     }
-    } catch (const Error& e) {
-      // the scratch did not fit (another library holds most of HBM): halve the row super-chunk and start over -- nothing has
-      // been enqueued yet when the FIRST super-chunk's buffers cannot be allocated
-      if (e.code != CCZ_ENOMEM || launched || launch_rows <= max_steps * SP_K) throw;
-      if (planes) { dev_free(c, planes); planes = nullptr; }
-      if (partial) { dev_free(c, partial); partial = nullptr; }
-      planes_cap = partial_cap = 0;
-      launch_rows = std::max<int64_t>(max_steps * SP_K, launch_rows / 2 / (max_steps * SP_K) * (max_steps * SP_K));
-      goto retry_smaller;
-    }
-  } catch (...) {
-    release();
-    throw;
   }
-  release();
+  } catch (const Error& e) {
+    // the scratch did not fit (another library holds most of HBM): halve the row super-chunk and start over -- nothing has
+    // been enqueued yet when the FIRST super-chunk's buffers cannot be allocated
+    if (e.code != CCZ_ENOMEM || launched || launch_rows <= max_steps * SP_K) throw;
+    planes_own.reset(); planes = nullptr;
+    partial_own.reset(); partial = nullptr;
+    planes_cap = partial_cap = 0;
+    launch_rows = std::max<int64_t>(max_steps * SP_K, launch_rows / 2 / (max_steps * SP_K) * (max_steps * SP_K));
+    goto retry_smaller;
+  }
 }
 
 }  // namespace ccz

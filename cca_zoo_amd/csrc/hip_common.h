@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <optional>
 #include <utility>
 #include <vector>
 
@@ -10,91 +11,154 @@
 
 namespace ccz {
 
+// Move-only owner of one HIP resource: empty by default, destroys what it holds (the error code is dropped: a teardown has nobody
+// to report to).  out() is for the hipXxxCreate(&raw) idiom; it lets go of what was held first.
+template <typename H, auto Destroy>
+class Owned {
+ public:
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h_(o.release()) {}
+  Owned& operator=(Owned&& o) noexcept { if (this != &o) { reset(); h_ = o.release(); } return *this; }
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { reset(); }
+  H get() const { return h_; }
+  explicit operator bool() const { return h_ != H(); }
+  void reset() { if (h_ != H()) (void)Destroy(h_); h_ = H(); }
+  H release() { H h = h_; h_ = H(); return h; }
+  H* out() { reset(); return &h_; }
+ private:
+  H h_ = H();
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+template <typename T = void> using DevMem = Owned<T*, hipFree>;
+template <typename T = void> using PinMem = Owned<T*, hipHostFree>;
+
+// A second stream and the N events that tie it to the handle's stream: made in a local and moved into the handle only when
+// complete, so the handle holds all of it or none.  false: the runtime refused a part (nothing is kept, the caller falls back).
+template <int N>
+struct SideStream {
+  Stream st;
+  Event ev[N];
+};
+template <int N>
+bool make_side_stream(std::optional<SideStream<N>>& into) {
+  SideStream<N> s;
+  bool ok = hipStreamCreateWithFlags(s.st.out(), hipStreamNonBlocking) == hipSuccess;
+  for (int i = 0; ok && i < N; ++i) ok = hipEventCreateWithFlags(s.ev[i].out(), hipEventDisableTiming) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); return false; }
+  into.emplace(std::move(s));
+  return true;
+}
+
 struct PoolBlock {
-  void* p;
+  DevMem<> p;
   size_t bytes;
   bool used;
 };
 
 struct GraphEntry {
   uint64_t key;
-  hipGraphExec_t exec;
+  GraphExec exec;
   uint64_t tick;
 };
 
+// One zeroed device block of `bytes` per stream (at most 32 streams): the arrival counters of kernels whose workgroups meet
+// through device memory -- two launches of one handle on different streams may overlap and must not share them
+struct StreamSync {
+  std::vector<std::pair<hipStream_t, DevMem<>>> blocks;
+  void* find(hipStream_t st) const {
+    for (auto& e : blocks)
+      if (e.first == st) return e.second.get();
+    return nullptr;
+  }
+  // the block of `st`, made and zeroed (in stream order) on first use; null: 32 streams already, or no memory
+  void* get(hipStream_t st, size_t bytes) {
+    if (void* p = find(st)) return p;
+    if (blocks.size() >= 32) return nullptr;
+    DevMem<> p;
+    if (hipMalloc(p.out(), bytes) != hipSuccess || hipMemsetAsync(p.get(), 0, bytes, st) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    blocks.emplace_back(st, std::move(p));
+    return blocks.back().second.get();
+  }
+};
+
+// The handle.  Every member that holds a HIP resource owns it; members are destroyed in reverse order of declaration, which
+// ccz_destroy relies on: the pool and the caches are declared before the streams (destroyed after them), the graph execs last
+// (destroyed first, before the streams they were captured on).
 struct Impl {
   hipDeviceProp_t props;
   std::vector<PoolBlock> pool;
-  // launch-bound fixed-shape sequences (blocked Cholesky / triangular solves: hundreds of tiny kernels)
-  // are captured once per (shape, pointers) into a hipGraph and replayed
-  std::vector<GraphEntry> graphs;
+  // device copies of recently used K1 tile tables (gram.hip): the table is a pure function of the views' pointers,
+  // widths and strides, so a training loop (same pooled staging buffer every step) never copies one again
+  struct TileTab { uint64_t hash; size_t bytes; DevMem<> dev; uint64_t tick; };
+  std::vector<TileTab> tile_tabs;
+  struct K1Plan { uint64_t key; DevMem<int> dev; int wgs; };
+  std::vector<K1Plan> k1_plans;          // gram.hip: per-tile row splits of k_gram_f32_fifo_small, by batch shape
+  struct SplitTab { uint64_t key; DevMem<> panels, tiles, gtiles; int np, ntiles; };
+  std::vector<SplitTab> split_tabs;      // gram_split.hip: panel / tile tables by view widths (pointer-free: uploaded once per shape)
+  StreamSync chain_sync;                 // cholinv.hip: sync blocks of the persistent chain kernel
+  StreamSync colsum_sync;                // gram.hip: arrival counters of k_colsum_pilot (64 words each, zero between launches)
+  int chain_cap = 0;                     // > 0 limits the chain kernel's workgroups (set by callers that run throughput work on another stream next to it)
+  DevMem<> chain_dbg;                    // CCZ_CHAIN_DEBUG stamps
+  DevMem<int> d_flag;                    // small device scratch: ints
+  DevMem<double> d_small;                // small device scratch: 64K doubles
+  size_t small_cap = 65536;
   uint64_t tick = 0;
   int graphs_on = 0;            // set by ccz_create (CCZ_GRAPHS); cleared for good when a capture fails
-  hipStream_t own_stream = nullptr;   // the handle's default stream (blocking: ordered with the null stream)
-  hipEvent_t ev[4];
-  int* d_flag = nullptr;      // small device scratch: ints
-  double* d_small = nullptr;  // small device scratch: 64K doubles
-  size_t small_cap = 65536;
-  // host -> device streaming of pageable inputs (gram.hip): two pinned bounce buffers, a copy stream and
-  // per-slot events; created on first use, kept for the life of the handle
-  void* pin_buf[2] = {nullptr, nullptr};
+  Stream own_stream;            // the handle's default stream (blocking: ordered with the null stream)
+  Event ev[4];
+  // host -> device streaming of pageable inputs (gram.hip): two pinned bounce buffers, a copy stream and per-slot events
+  // (h2d done [2], compute done [2]); created on first use, kept for the life of the handle
+  PinMem<> pin_buf[2];
   size_t pin_cap = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t pipe_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // h2d done [2], compute done [2]
+  std::optional<SideStream<4>> pipe;
   // ring of pinned slots for small asynchronous host -> device copies (tile tables, descriptors)
   static constexpr int kSmallSlots = 32;
   static constexpr size_t kSmallBytes = size_t(64) << 10;
-  void* small_pin[kSmallSlots] = {};
-  hipEvent_t small_ev[kSmallSlots] = {};
+  PinMem<> small_pin[kSmallSlots];
+  Event small_ev[kSmallSlots];
   int small_next = 0;
   // second stream + events for the look-ahead of the super-blocked Cholesky (ops_hip.hip), created on first use
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t aux_ev[2] = {nullptr, nullptr};
-  // device copies of recently used K1 tile tables (gram.hip): the table is a pure function of the views' pointers,
-  // widths and strides, so a training loop (same pooled staging buffer every step) never copies one again
-  struct TileTab { uint64_t hash; size_t bytes; void* dev; uint64_t tick; };
-  std::vector<TileTab> tile_tabs;
+  std::optional<SideStream<2>> aux;
   // sticky failure record of the stream-native loss (loss.hip): pinned + mapped host words written by the device
-  int* loss_status = nullptr;       // host view
-  int* loss_status_dev = nullptr;   // device view of the same words
+  PinMem<int> loss_status;          // host view
+  int* loss_status_dev = nullptr;   // device view of the same words (not owned)
   // hand-over events between a caller's stream and the handle's stream (ccz_stream_acquire / ccz_stream_release)
-  hipEvent_t xs_ev[2] = {nullptr, nullptr};
+  Event xs_ev[2];
   // polled waits (ops_hip.hip: wait_stream_short) and the pinned landing buffer of small device -> host copies
-  hipEvent_t wait_ev = nullptr;
-  void* d2h_pin = nullptr;
-  void* d2h_pin_dev = nullptr;      // device view of d2h_pin (host-mapped): written by a copy kernel
-  hipEvent_t d2h_tev[2] = {nullptr, nullptr};   // CCZ_TRACE_D2H: timing events around a read-back (this handle's device)
+  Event wait_ev;
+  PinMem<> d2h_pin;
+  void* d2h_pin_dev = nullptr;      // device view of d2h_pin (host-mapped, not owned): written by a copy kernel
+  Event d2h_tev[2];                 // CCZ_TRACE_D2H: timing events around a read-back (this handle's device)
   static constexpr size_t kD2hPinBytes = size_t(4) << 20;
-  void* deferred_event = nullptr;   // awaited by the next solve before it reads off-diagonal blocks (ccz_solve_defer, or the
-                                    // handle's own event behind an unpack on a foreign stream)
-  hipEvent_t defer_own_ev = nullptr;
+  void* deferred_event = nullptr;   // BORROWED (not owned): awaited by the next solve before it reads off-diagonal blocks
+                                    // (ccz_solve_defer, or the handle's own event behind an unpack on a foreign stream)
+  Event defer_own_ev;
   bool adopted = false;             // c->stream is a caller's stream (ccz_stream_adopt) until the next acquire
-  // cholinv.hip: per-stream sync blocks of the persistent chain kernel (stream, device block); chain_cap > 0 limits its
-  // workgroups (set by callers that run throughput work on another stream next to the chain)
-  std::vector<std::pair<void*, void*>> chain_sync;
-  int chain_cap = 0;
-  void* chain_dbg = nullptr;             // CCZ_CHAIN_DEBUG stamps
-  struct K1Plan { uint64_t key; void* dev; int wgs; };
-  std::vector<K1Plan> k1_plans;          // gram.hip: per-tile row splits of k_gram_f32_fifo_small, by batch shape
-  // gram_split.hip: stage boundaries and hand-overs of a split-route launch (grown on demand), and the side stream the split pass
-  // of the NEXT row piece runs on under the MFMA kernel of the current one (CU-masked when the runtime allows; created on first use)
-  std::vector<hipEvent_t> sp_ev;
-  hipStream_t split_stream = nullptr;
-  bool split_stream_tried = false;
-  int split_stream_req = 0;              // CCZ_SPLIT_PIPE_CUS the side stream was made for
-  int split_stream_cus = 0;              // CUs the side stream is confined to (0: no mask)
-  struct SplitTab { uint64_t key; void* panels; void* tiles; void* gtiles; int np, ntiles; };
-  std::vector<SplitTab> split_tabs;      // gram_split.hip: panel / tile tables by view widths (pointer-free: uploaded once per shape)
-  std::vector<std::pair<void*, void*>> colsum_sync;   // gram.hip: per-stream arrival counters of k_colsum_pilot (64 words each, zero between launches)
+  // gram_split.hip: stage boundaries and hand-overs of a split-route launch (timing events, grown on demand), and the side stream the
+  // split pass of the NEXT row piece runs on under the MFMA kernel of the current one.  split_side is empty until the first piped
+  // launch asks; then it says what was asked for and holds the stream, or none when the runtime refused (one piece then)
+  std::vector<Event> sp_ev;
+  struct SplitSide {
+    Stream st;                      // CU-masked when the runtime allows
+    int req = 0;                    // CCZ_SPLIT_PIPE_CUS the side stream was made for
+    int cus = 0;                    // CUs the side stream is confined to (0: no mask)
+  };
+  std::optional<SplitSide> split_side;
   // comm.hip: ccz_moments_exchange -- the packed blocks buffer the handle keeps between fits (grown on demand), the stream its
-  // collectives run on and the events that tie it to the handle's stream
-  void* xchg_buf = nullptr;
+  // collectives run on and the events that tie it to the handle's stream: packed (main -> exchange), head reduced, tail unpacked
+  DevMem<> xchg_buf;
   size_t xchg_cap = 0;
-  hipStream_t xchg_stream = nullptr;
-  hipEvent_t xchg_ev[3] = {nullptr, nullptr, nullptr};   // packed (main -> exchange), head reduced, tail unpacked
-  // comm.hip: the RCCL communicator of this handle's device (ncclComm_t), its size and this handle's rank
+  std::optional<SideStream<3>> xchg;
+  // comm.hip: the RCCL communicator of this handle's device (ncclComm_t), its size and this handle's rank; ccz_comm_destroy ends it
   void* comm = nullptr;
   int comm_world = 0, comm_rank = -1;
+  // launch-bound fixed-shape sequences (blocked Cholesky / triangular solves: hundreds of tiny kernels)
+  // are captured once per (shape, pointers) into a hipGraph and replayed
+  std::vector<GraphEntry> graphs;
 };
 
 inline Impl* impl(ccz_ctx* c) { return static_cast<Impl*>(c->impl); }
@@ -147,6 +211,9 @@ void sync_short(ccz_ctx* c);   // polled wait for the handle's stream (short wai
 
 // evd_block.hip: one-sided block Jacobi on the rows of W (p a multiple of 64, even leading dimensions)
 int jacobi_rows_block(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double* Q, int64_t qc, int64_t ldq, int max_sweeps);
+
+// ops_hip.hip: wait for the handle's stream, then give the pool's unused blocks back to the driver; returns the bytes released
+size_t pool_trim(ccz_ctx* c);
 
 // api.hip: blocks layout of the sharded exchange (ccz.h), pack or unpack, head / tail / both, optionally on a foreign stream
 void moments_blocks(ccz_ctx* c, bool pack, double* mom, int64_t D, const int64_t* dims, int m, double* packed, int which,

@@ -442,17 +442,6 @@ void check_info(ccz_ctx* c, const int* info_dev, int m, const char* what) {
     if (got[a] != 0x7fffffff) fail(CCZ_ENOTSPD, "%s: S_%d%d + eps I is not positive definite (pivot %d)", what, a + 1, a + 1, got[a] - 1);
 }
 
-// pooled allocation of raw bytes that goes back to the pool on every exit path
-struct PoolPtr {
-  ccz_ctx* c;
-  void* p;
-  PoolPtr(ccz_ctx* c_, size_t bytes) : c(c_), p(bytes ? dev_alloc(c_, bytes) : nullptr) {}
-  ~PoolPtr() { if (p) dev_free(c, p); }
-  PoolPtr(const PoolPtr&) = delete;
-  PoolPtr& operator=(const PoolPtr&) = delete;
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 // The sticky failure record of the stream-native loss (hip_common.h::Impl::loss_status): two ints in pinned host
@@ -464,7 +453,7 @@ void loss_status_take(ccz_ctx* c, bool synchronise, int* view, int* pivot) {
   if (pivot) *pivot = 0;
   if (!im->loss_status) return;
   if (synchronise) sync(c);
-  volatile int* st = im->loss_status;
+  volatile int* st = im->loss_status.get();
   const int v = st[0];
   if (v != 0) {
     if (view) *view = v;
@@ -477,12 +466,14 @@ void loss_status_take(ccz_ctx* c, bool synchronise, int* view, int* pivot) {
 static int* loss_status_dev(ccz_ctx* c) {
   Impl* im = impl(c);
   if (!im->loss_status) {
-    void* hp = nullptr;
-    if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    std::memset(hp, 0, 64);
+    PinMem<int> hp;
     void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(hp); return nullptr; }
-    im->loss_status = static_cast<int*>(hp);
+    if (hipHostMalloc(hp.out(), 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp.get(), 0) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    std::memset(hp.get(), 0, 64);
+    im->loss_status = std::move(hp);
     im->loss_status_dev = static_cast<int*>(dp);
   }
   return im->loss_status_dev;
@@ -546,7 +537,7 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
   double* bias = want ? gamma + D * D : nullptr;
   float* g32 = (want && dtype == CCZ_F32) ? reinterpret_cast<float*>(gamma + (D + 3) * D) : nullptr;
   DBuf mean(c, D), acc(c, 1);
-  PoolPtr info(c, LMAXV * sizeof(int));
+  PoolBuf<int> info(c, LMAXV);
   // fp32 DCCA batch: K1's partial sums feed the preparation directly (no moments, no gather, no fills, no atomics).
   // Embeddings (post-ReLU, un-normalised) routinely sit far from zero, so the Gram is always pilot-shifted here.
   const int fast_env = env::once(env::LOSS_FAST);
@@ -558,21 +549,21 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
     ~Release() { if (on) gram_partials_release(c, gp); }
   } rel{c, &gp, fast};
   if (fast) {
-    pair_core(c, nullptr, n, sh.dims, m, eps, want, acc, gamma, mean, info.as<int>(), bias, &gp, true);
+    pair_core(c, nullptr, n, sh.dims, m, eps, want, acc, gamma, mean, info.get(), bias, &gp, true);
   } else {
     // general route: the moments [G | s] through ccz_moments' machinery.  Wide views (n ~ 1e6 rows x 8192): the automatic
     // pilot choice (one 2 D-double read-back) keeps centred data on the faster FIFO kernel.
     DBuf mom(c, D * D + D);
     moments_impl(c, dtype, z, m, n, true, mom, false, dtype == CCZ_F32 ? (narrow ? 2 : 1) : 0, false);
-    pair_core(c, mom, n, sh.dims, m, eps, want, acc, gamma, mean, info.as<int>(), bias, nullptr, narrow);
+    pair_core(c, mom, n, sh.dims, m, eps, want, acc, gamma, mean, info.get(), bias, nullptr, narrow);
   }
   if (want) {
     // the batch mean travels with the state (backward: pilot of the split route), and the pilot-correction row is formed with the centring row
     hipLaunchKernelGGL(k_state_rows, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, mean.get(), D, gamma + (D + 1) * D, gamma + (D + 2) * D);
     hipLaunchKernelGGL(k_loss_tail, dim3((unsigned)((D + 63) / 64), (unsigned)((D + 63) / 64)), dim3(256), 0, st, gamma, mean.get(), D, bias, g32,
-                       acc.get(), dtype, loss_dev, info.as<int>(), m, loss_status_dev(c), gamma + (D + 2) * D);
+                       acc.get(), dtype, loss_dev, info.get(), m, loss_status_dev(c), gamma + (D + 2) * D);
   } else {
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(1), 0, st, acc.get(), dtype, loss_dev, static_cast<double*>(nullptr), info.as<int>(), m,
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(1), 0, st, acc.get(), dtype, loss_dev, static_cast<double*>(nullptr), info.get(), m,
                        loss_status_dev(c));
   }
   CCZ_LAUNCH_CHECK();
@@ -651,9 +642,9 @@ void pair_loss_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int64_t n, 
       if (!ldg || ldg[a] < sh.dims[a]) fail(CCZ_EINVAL, "cca_loss: bad gradient stride (view %d)", a);
       want = true;
     }
-  PoolPtr state(c, want ? size_t(pair_loss_state_bytes_impl(dtype, sh.dims, m)) : 0);
-  pair_loss_forward_impl(c, dtype, z, m, n, eps, loss_dev, state.p);
-  if (want) pair_loss_backward_impl(c, dtype, z, m, n, state.p, nullptr, g, ldg);
+  PoolBuf<char> state(c, want ? pair_loss_state_bytes_impl(dtype, sh.dims, m) : 0);
+  pair_loss_forward_impl(c, dtype, z, m, n, eps, loss_dev, state.get());
+  if (want) pair_loss_backward_impl(c, dtype, z, m, n, state.get(), nullptr, g, ldg);
 }
 
 void cca_loss_impl(ccz_ctx* c, int dtype, const void* z1, const void* z2, int64_t n, int64_t d1, int64_t d2, int64_t ld1,
@@ -681,12 +672,12 @@ void pair_loss_moments_impl(ccz_ctx* c, const double* mom, int64_t n, const int6
   int64_t D = 0;
   for (int a = 0; a < m; ++a) D += dims[a];
   DBuf acc(c, 2), mean_tmp(c, want ? 0 : D);
-  PoolPtr info(c, LMAXV * sizeof(int));
-  pair_core(c, mom, n, dims, m, eps, want, acc, gamma_dev, want ? mean_dev : mean_tmp.get(), info.as<int>());
+  PoolBuf<int> info(c, LMAXV);
+  pair_core(c, mom, n, dims, m, eps, want, acc, gamma_dev, want ? mean_dev : mean_tmp.get(), info.get());
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(1), 0, stream(c), acc.get(), CCZ_F64, static_cast<void*>(nullptr), acc.get() + 1,
                      static_cast<const int*>(nullptr), 0, static_cast<int*>(nullptr));
   CCZ_LAUNCH_CHECK();
-  check_info(c, info.as<int>(), m, "pair_loss_moments");   // the loss goes back to the HOST here: this entry synchronises anyway
+  check_info(c, info.get(), m, "pair_loss_moments");   // the loss goes back to the HOST here: this entry synchronises anyway
   d2h(c, loss_host, acc.get() + 1, 8);
 }
 

@@ -67,28 +67,31 @@ struct DeviceScope {
   DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
-// RAII device buffer of doubles
-class DBuf {
+// RAII scratch of n elements of T from the handle's pool (n <= 0: empty).  The pool hands blocks out by size in stream order, so
+// WHERE a block goes back decides which later request gets it: reset() returns it before the end of the scope.
+template <typename T>
+class PoolBuf {
  public:
-  DBuf() = default;
-  DBuf(ccz_ctx* c, int64_t n) : c_(c), n_(n) { p_ = n > 0 ? static_cast<double*>(dev_alloc(c, size_t(n) * 8)) : nullptr; }
-  DBuf(const DBuf&) = delete;
-  DBuf& operator=(const DBuf&) = delete;
-  DBuf(DBuf&& o) noexcept : c_(o.c_), p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-  DBuf& operator=(DBuf&& o) noexcept {
+  PoolBuf() = default;
+  PoolBuf(ccz_ctx* c, int64_t n) : c_(c), n_(n) { p_ = n > 0 ? static_cast<T*>(dev_alloc(c, size_t(n) * sizeof(T))) : nullptr; }
+  PoolBuf(const PoolBuf&) = delete;
+  PoolBuf& operator=(const PoolBuf&) = delete;
+  PoolBuf(PoolBuf&& o) noexcept : c_(o.c_), p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  PoolBuf& operator=(PoolBuf&& o) noexcept {
     if (this != &o) { reset(); c_ = o.c_; p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
     return *this;
   }
-  ~DBuf() { reset(); }
+  ~PoolBuf() { reset(); }
   void reset() { if (p_) dev_free(c_, p_); p_ = nullptr; n_ = 0; }
-  double* get() const { return p_; }
-  operator double*() const { return p_; }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
   int64_t size() const { return n_; }
  private:
   ccz_ctx* c_ = nullptr;
-  double* p_ = nullptr;
+  T* p_ = nullptr;
   int64_t n_ = 0;
 };
+using DBuf = PoolBuf<double>;
 
 // ---- dense float64 ops ------------------------------------------------------
 // C (M x N) = alpha * op(A) * op(B) + beta * C

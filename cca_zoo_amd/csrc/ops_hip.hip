@@ -37,30 +37,37 @@ void* dev_alloc(ccz_ctx* c, size_t bytes) {
   }
   if (best >= 0) {
     im->pool[best].used = true;
-    return im->pool[best].p;
+    return im->pool[best].p.get();
   }
-  void* p = nullptr;
+  DevMem<> p;
   if (env::once(env::TRACE_POOL)) fprintf(stderr, "[ccz] pool miss: hipMalloc(%zu) (%zu blocks cached)\n", bytes, im->pool.size());
-  hipError_t e = hipMalloc(&p, bytes);
+  hipError_t e = hipMalloc(p.out(), bytes);
   if (e != hipSuccess) {
     // release cached blocks and retry once
     (void)hipGetLastError();
-    CCZ_HIP(hipStreamSynchronize(stream(c)));
-    for (auto it = im->pool.begin(); it != im->pool.end();) {
-      if (!it->used) { (void)hipFree(it->p); it = im->pool.erase(it); } else ++it;
-    }
-    e = hipMalloc(&p, bytes);
+    pool_trim(c);
+    e = hipMalloc(p.out(), bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); fail(CCZ_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); }
   }
-  im->pool.push_back({p, bytes, true});
-  return p;
+  im->pool.push_back({std::move(p), bytes, true});
+  return im->pool.back().p.get();
+}
+
+size_t pool_trim(ccz_ctx* c) {
+  Impl* im = impl(c);
+  CCZ_HIP(hipStreamSynchronize(stream(c)));       // pooled blocks are recycled in stream order: nothing may still use them
+  size_t freed = 0;
+  for (auto it = im->pool.begin(); it != im->pool.end();) {
+    if (!it->used) { freed += it->bytes; it = im->pool.erase(it); } else ++it;
+  }
+  return freed;
 }
 
 void dev_free(ccz_ctx* c, void* p) {
   if (!p) return;
   Impl* im = impl(c);
   for (auto& b : im->pool)
-    if (b.p == p) { b.used = false; return; }
+    if (b.p.get() == p) { b.used = false; return; }
   // not ours: stream-ordered work may still use it, so synchronise before freeing
   (void)hipStreamSynchronize(stream(c));
   (void)hipFree(p);
@@ -87,25 +94,25 @@ void h2d_small(ccz_ctx* c, void* dst, const void* src, size_t bytes) {
   for (int t = 0; t < Impl::kSmallSlots; ++t) {
     const int j = (im->small_next + t) % Impl::kSmallSlots;
     if (!im->small_pin[j]) { i = j; break; }
-    const hipError_t q = hipEventQuery(im->small_ev[j]);
+    const hipError_t q = hipEventQuery(im->small_ev[j].get());
     if (q == hipSuccess) { i = j; break; }
     if (q != hipErrorNotReady) { (void)hipGetLastError(); }
   }
   if (!im->small_pin[i]) {
-    if (hipHostMalloc(&im->small_pin[i], Impl::kSmallBytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&im->small_ev[i], hipEventDisableTiming) != hipSuccess) {
+    if (hipHostMalloc(im->small_pin[i].out(), Impl::kSmallBytes, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(im->small_ev[i].out(), hipEventDisableTiming) != hipSuccess) {
       (void)hipGetLastError();
-      if (im->small_pin[i]) { (void)hipHostFree(im->small_pin[i]); im->small_pin[i] = nullptr; }
+      im->small_pin[i].reset();
       h2d_blocking(c, dst, src, bytes);
       return;
     }
   } else {
-    CCZ_HIP(hipEventSynchronize(im->small_ev[i]));      // (returns at once for a drained slot)
+    CCZ_HIP(hipEventSynchronize(im->small_ev[i].get()));      // (returns at once for a drained slot)
   }
   im->small_next = (i + 1) % Impl::kSmallSlots;
-  std::memcpy(im->small_pin[i], src, bytes);
-  CCZ_HIP(hipMemcpyAsync(dst, im->small_pin[i], bytes, hipMemcpyHostToDevice, stream(c)));
-  CCZ_HIP(hipEventRecord(im->small_ev[i], stream(c)));
+  std::memcpy(im->small_pin[i].get(), src, bytes);
+  CCZ_HIP(hipMemcpyAsync(dst, im->small_pin[i].get(), bytes, hipMemcpyHostToDevice, stream(c)));
+  CCZ_HIP(hipEventRecord(im->small_ev[i].get(), stream(c)));
 }
 // ---- short host waits ---------------------------------------------------------------------------------------------
 // The solve is a chain of small launches with a handful of read-backs (pivot flags, residual norms, Ritz values).  A
@@ -137,10 +144,10 @@ static void wait_stream_short(ccz_ctx* c) {
   const double budget = spin_budget_ms();
   bool done = false;
   if (budget > 0.0) {
-    if (!im->wait_ev) CCZ_HIP(hipEventCreateWithFlags(&im->wait_ev, hipEventDisableTiming));
-    CCZ_HIP(hipEventRecord(im->wait_ev, st));
+    if (!im->wait_ev) CCZ_HIP(hipEventCreateWithFlags(im->wait_ev.out(), hipEventDisableTiming));
+    CCZ_HIP(hipEventRecord(im->wait_ev.get(), st));
     for (;;) {
-      const hipError_t q = hipEventQuery(im->wait_ev);
+      const hipError_t q = hipEventQuery(im->wait_ev.get());
       if (q == hipSuccess) { done = true; break; }
       if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }
       if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > budget) break;
@@ -162,20 +169,21 @@ void d2h(ccz_ctx* c, void* dst, const void* src, size_t bytes) {
   // staged by the runtime, which may block inside the call) and the wait below polls
   if (bytes <= Impl::kD2hPinBytes && spin_budget_ms() > 0.0) {
     if (!im->d2h_pin) {
-      if (hipHostMalloc(&im->d2h_pin, Impl::kD2hPinBytes, hipHostMallocMapped) != hipSuccess) {
+      if (hipHostMalloc(im->d2h_pin.out(), Impl::kD2hPinBytes, hipHostMallocMapped) != hipSuccess) {
         (void)hipGetLastError();
-        im->d2h_pin = nullptr;
-      } else if (hipHostGetDevicePointer(&im->d2h_pin_dev, im->d2h_pin, 0) != hipSuccess) {
+      } else if (hipHostGetDevicePointer(&im->d2h_pin_dev, im->d2h_pin.get(), 0) != hipSuccess) {
         (void)hipGetLastError();
         im->d2h_pin_dev = nullptr;
       }
     }
     const int mode = env::live(env::D2H_MODE);
     const bool trace = env::live(env::TRACE_D2H);
-    hipEvent_t* tev = im->d2h_tev;
+    hipEvent_t tev[2] = {im->d2h_tev[0].get(), im->d2h_tev[1].get()};
     const auto th0 = std::chrono::steady_clock::now();
     if (trace) {
-      if (!tev[0]) { CCZ_HIP(hipEventCreate(&tev[0])); CCZ_HIP(hipEventCreate(&tev[1])); }
+      if (!tev[1]) {       // (the pair exists when its second event does)
+        for (int i = 0; i < 2; ++i) { CCZ_HIP(hipEventCreate(im->d2h_tev[i].out())); tev[i] = im->d2h_tev[i].get(); }
+      }
       CCZ_HIP(hipEventRecord(tev[0], stream(c)));
     }
     auto report = [&](const char* what) {
@@ -206,12 +214,12 @@ void d2h(ccz_ctx* c, void* dst, const void* src, size_t bytes) {
         }
         CCZ_LAUNCH_CHECK();
       } else {
-        CCZ_HIP(hipMemcpyAsync(im->d2h_pin, src, bytes, hipMemcpyDeviceToHost, stream(c)));
+        CCZ_HIP(hipMemcpyAsync(im->d2h_pin.get(), src, bytes, hipMemcpyDeviceToHost, stream(c)));
       }
       if (trace) CCZ_HIP(hipEventRecord(tev[1], stream(c)));
       if (mode == 3) CCZ_HIP(hipStreamSynchronize(stream(c)));
       else wait_stream_short(c);
-      std::memcpy(dst, im->d2h_pin, bytes);
+      std::memcpy(dst, im->d2h_pin.get(), bytes);
       report(mode <= 1 ? "kernel" : "sdma");
       return;
     }
@@ -968,7 +976,7 @@ static void graph_run(ccz_ctx* c, uint64_t key, F&& fn) {
   for (auto& g : im->graphs)
     if (g.key == key) {
       g.tick = ++im->tick;
-      CCZ_HIP(hipGraphLaunch(g.exec, st));
+      CCZ_HIP(hipGraphLaunch(g.exec.get(), st));
       return;
     }
   if (env::once(env::TRACE_POOL)) fprintf(stderr, "[ccz] graph miss: capturing key %016llx (%zu cached)\n", (unsigned long long)key, im->graphs.size());
@@ -987,8 +995,8 @@ static void graph_run(ccz_ctx* c, uint64_t key, F&& fn) {
     throw;
   }
   CCZ_HIP(hipStreamEndCapture(st, &graph));
-  hipGraphExec_t exec = nullptr;
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+  GraphExec exec;
+  if (hipGraphInstantiate(exec.out(), graph, nullptr, nullptr, 0) != hipSuccess) {
     (void)hipGetLastError();
     (void)hipGraphDestroy(graph);
     im->graphs_on = 0;
@@ -1000,11 +1008,10 @@ static void graph_run(ccz_ctx* c, uint64_t key, F&& fn) {
     size_t lru = 0;
     for (size_t i = 1; i < im->graphs.size(); ++i)
       if (im->graphs[i].tick < im->graphs[lru].tick) lru = i;
-    (void)hipGraphExecDestroy(im->graphs[lru].exec);
     im->graphs.erase(im->graphs.begin() + lru);
   }
-  im->graphs.push_back({key, exec, ++im->tick});
-  CCZ_HIP(hipGraphLaunch(exec, st));
+  im->graphs.push_back({key, std::move(exec), ++im->tick});
+  CCZ_HIP(hipGraphLaunch(im->graphs.back().exec.get(), st));
 }
 
 // the same for other translation units (evd_block.hip): key helpers + a type-erased entry
@@ -1082,7 +1089,7 @@ static void potrf_lower_batched_steps(ccz_ctx* c, int count, double* const* A, c
       Tp[i] = Tb[i].get();
       ldl[i] = di;
     }
-    int* info_dev = impl(c)->d_flag + 8;
+    int* info_dev = impl(c)->d_flag.get() + 8;
     cholinv_batched(c, nbt, A + b0, lda + b0, d + b0, Lp.data(), ldl.data(), nullptr, nullptr, Tp.data(), info_dev);
     for (int i = 0; i < nbt; ++i) copy_lower(c, d[b0 + i], Lp[i], ldl[i], A[b0 + i], lda[b0 + i]);
     int got[8];
@@ -1139,38 +1146,22 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
   }
   // info of super-step J of matrix i: slot J * 8 + (position among the matrices alive at J); all start at "no failure"
   const int nslots = int(nsb) * 8;
-  int* info_dev = static_cast<int*>(dev_alloc(c, size_t(nslots) * sizeof(int)));
+  PoolBuf<int> info_dev(c, nslots);
   // Unwinding (an allocation or launch failure between the look-ahead launch and the main stream's wait): the pooled
-  // buffers below go back to the pool as the DBufs unwind, and the pool recycles them in the order of the MAIN stream --
-  // so the look-ahead stream must be drained first, and the pivot-flag block released.
+  // buffers above go back to the pool as they unwind, and the pool recycles them in the order of the MAIN stream --
+  // so the look-ahead stream must be drained first: this is declared after them, hence unwinds before them.
   struct Unwind {
-    ccz_ctx* c; Impl* im; int* info; bool armed = true;
-    ~Unwind() {
-      if (!armed) return;
-      if (im->aux_stream) (void)hipStreamSynchronize(im->aux_stream);
-      dev_free(c, info);
-    }
-  } unwind{c, im, info_dev};
+    Impl* im; bool armed = true;
+    ~Unwind() { if (armed && im->aux) (void)hipStreamSynchronize(im->aux->st.get()); }
+  } unwind{im};
 
   hipStream_t s_main = stream(c), s_aux = s_main;
   bool la = potrf_lookahead() != 0 && nsb > 1;
   if (la) {
-    if (!im->aux_stream) {
-      hipStream_t st = nullptr;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-          hipEventCreateWithFlags(&e0, hipEventDisableTiming) == hipSuccess &&
-          hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess) {
-        im->aux_stream = st; im->aux_ev[0] = e0; im->aux_ev[1] = e1;
-      } else {
-        (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        if (st) (void)hipStreamDestroy(st);
-        la = false;
-      }
-    }
-    if (la) s_aux = im->aux_stream;
+    if (!im->aux && !make_side_stream(im->aux)) la = false;
+    if (la) s_aux = im->aux->st.get();
   }
+  const hipEvent_t aux_ev[2] = {la ? im->aux->ev[0].get() : nullptr, la ? im->aux->ev[1].get() : nullptr};
 
   // diagonal super-block J of every matrix still alive: factor, invert (on the CURRENT c->stream)
   auto factor = [&](int64_t J) {
@@ -1234,8 +1225,8 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
     }
     if (J + 1 < nsb) {
       if (la) {
-        CCZ_HIP(hipEventRecord(im->aux_ev[0], s_main));
-        CCZ_HIP(hipStreamWaitEvent(s_aux, im->aux_ev[0], 0));
+        CCZ_HIP(hipEventRecord(aux_ev[0], s_main));
+        CCZ_HIP(hipStreamWaitEvent(s_aux, aux_ev[0], 0));
         {
           StreamSwap sw(c, s_aux);
           // the chain kernel's helper workgroups spin while they wait: next to the update GEMMs of the main stream they get a
@@ -1245,7 +1236,7 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
           try { factor(J + 1); } catch (...) { im->chain_cap = cap0; throw; }
           im->chain_cap = cap0;
         }
-        CCZ_HIP(hipEventRecord(im->aux_ev[1], s_aux));
+        CCZ_HIP(hipEventRecord(aux_ev[1], s_aux));
       } else {
         factor(J + 1);
       }
@@ -1281,13 +1272,13 @@ static void potrf_lower_batched_sb(ccz_ctx* c, int count, double* const* A, cons
       if (rem > 0)
         gemm(c, false, true, rider->r, rem, w, -1.0, rtmp, SB, A[i] + (j0 + w) * lda[i] + j0, lda[i], 1.0, X + j0 + w, rider->ldx);
     }
-    if (la && J + 1 < nsb) CCZ_HIP(hipStreamWaitEvent(s_main, im->aux_ev[1], 0));
+    if (la && J + 1 < nsb) CCZ_HIP(hipStreamWaitEvent(s_main, aux_ev[1], 0));
   }
   std::vector<int> got(nslots, 0x7fffffff);
   // slots of (J, t) with t >= cnt of that super-step were never written: only read what cholinv_batched initialised
   d2h(c, got.data(), info_dev, size_t(nslots) * sizeof(int));
   unwind.armed = false;
-  dev_free(c, info_dev);
+  info_dev.reset();
   for (int i = 0; i < count; ++i) info[i] = 0;
   for (int64_t J = 0; J < nsb; ++J) {
     int cnt = 0;
@@ -1404,7 +1395,7 @@ int potrf_lower_inv(ccz_ctx* c, double* A, int64_t d, int64_t lda, double* Linv,
   double* Tp[1] = {Tb.get()};
   const int64_t dd[1] = {d}, la[1] = {lda}, ll[1] = {d}, lx[1] = {ldi};
   fill2d(c, d, d, Linv, ldi, 0.0);                     // (the chain writes the lower triangle only)
-  int* info_dev = impl(c)->d_flag + 8;
+  int* info_dev = impl(c)->d_flag.get() + 8;
   cholinv_batched(c, 1, Ap, la, dd, Lp, ll, Xp, lx, Tp, info_dev);
   int got = 0;
   d2h(c, &got, info_dev, sizeof(int));
@@ -1589,10 +1580,10 @@ int jacobi_rows(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double
     const double floor2 = mx * 1e-28;
     CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_jacobi_lds), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_need + 16)));
     hipLaunchKernelGGL(k_jacobi_lds, dim3(1), dim3(1024), lds_need + 16, stream(c), int(p), int(q), W, ldw, Q, int(Q ? qc : 0), ldq,
-                       tol, floor2, max_sweeps, im->d_flag + 1);
+                       tol, floor2, max_sweeps, im->d_flag.get() + 1);
     CCZ_LAUNCH_CHECK();
     int sw = 0;
-    d2h(c, &sw, im->d_flag + 1, sizeof(int));
+    d2h(c, &sw, im->d_flag.get() + 1, sizeof(int));
     if (sw < 0) fail(CCZ_ENOCONV, "Jacobi did not converge in %d sweeps (p=%lld, q=%lld)", max_sweeps, (long long)p, (long long)q);
     return sw;
   }
@@ -2156,25 +2147,25 @@ int syev_small(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_de
     auto launch = [&](auto kern) {
       CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_need)));
       hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds_need, stream(c), int(d), A, lda, w_dev, log, tol,
-                         max_sweeps, im->d_flag + 2);
+                         max_sweeps, im->d_flag.get() + 2);
     };
     if (env::once(env::SYEV_CHASE) && Vrows) {
       // one launch: the solve and, next to it, the replay chasing its log (k_syev_chase)
-      unsigned* sync = reinterpret_cast<unsigned*>(im->d_flag + 32);      // (words 8 .. 15 are the pivot flags of the factorizations)
+      unsigned* sync = reinterpret_cast<unsigned*>(im->d_flag.get() + 32);      // (words 8 .. 15 are the pivot flags of the factorizations)
       CCZ_HIP(hipMemsetAsync(sync, 0, 2 * sizeof(unsigned), stream(c)));
       const size_t lds_chase = std::max(lds_need, size_t(160 * (JR_COLS + 1) * 8 + JR_CHUNK * 80 * 16 + 16));
       const dim3 grid(1u + unsigned((d + JR_COLS - 1) / JR_COLS));
       auto launch2 = [&](auto kern) {
         CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_chase)));
         hipLaunchKernelGGL(kern, grid, dim3(1024), lds_chase, stream(c), int(d), A, lda, w_dev, log, tol, max_sweeps,
-                           im->d_flag + 2, sync, Vrows, ldv);
+                           im->d_flag.get() + 2, sync, Vrows, ldv);
       };
       if (nblk <= 1024) launch2(&k_syev_chase<1>);
       else if (nblk <= 2048) launch2(&k_syev_chase<2>);
       else launch2(&k_syev_chase<4>);
       CCZ_LAUNCH_CHECK();
       int st[2] = {0, 0};
-      d2h(c, st, im->d_flag + 2, sizeof(st));
+      d2h(c, st, im->d_flag.get() + 2, sizeof(st));
       sw = st[0];
       if (sw == -3) fail(CCZ_EHIP, "syev: the replaying workgroups lost the solving one");
       if (sw == -2) fail(CCZ_EINVAL, "syev: matrix has non-finite entries");
@@ -2186,7 +2177,7 @@ int syev_small(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_de
     else launch(&k_syev_packed4);
     CCZ_LAUNCH_CHECK();
     int st[2] = {0, 0};
-    d2h(c, st, im->d_flag + 2, sizeof(st));
+    d2h(c, st, im->d_flag.get() + 2, sizeof(st));
     sw = st[0];
     if (sw >= 1 && Vrows) {
       // the last sweep of a converged run rotated nothing: the log's first (sweeps - 1) * m1 rounds are all of V
@@ -2200,14 +2191,14 @@ int syev_small(ccz_ctx* c, const double* A, int64_t d, int64_t lda, double* w_de
     if (d <= 80) {
       CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_syev_small), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_need)));
       hipLaunchKernelGGL(k_syev_small, dim3(1), dim3(1024), lds_need, stream(c), int(d), A, lda, w_dev, Vrows, ldv,
-                         tol, max_sweeps, im->d_flag + 1);
+                         tol, max_sweeps, im->d_flag.get() + 1);
     } else {
       CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_syev_small_wide), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_need)));
       hipLaunchKernelGGL(k_syev_small_wide, dim3(1), dim3(1024), lds_need, stream(c), int(d), A, lda, w_dev, Vrows, ldv,
-                         tol, max_sweeps, im->d_flag + 1);
+                         tol, max_sweeps, im->d_flag.get() + 1);
     }
     CCZ_LAUNCH_CHECK();
-    d2h(c, &sw, im->d_flag + 1, sizeof(int));
+    d2h(c, &sw, im->d_flag.get() + 1, sizeof(int));
   }
   if (sw == -2) fail(CCZ_EINVAL, "syev: matrix has non-finite entries");
   if (sw < 0) fail(CCZ_ENOCONV, "Jacobi did not converge in %d sweeps (d=%lld)", max_sweeps, (long long)d);

@@ -228,28 +228,25 @@ void project_split(ccz_ctx* c, const float* X, int64_t n, int64_t d, int64_t ld,
   const int64_t nsteps = d / 16;
   // two planes / three products by default (4.07 ms, 4.5e-6); CCZ_PROJECT_PLANES=3: three planes / five products (4.63 ms, 2.9e-6)
   const int nplanes = env::live(env::PROJECT_PLANES) == 3 ? 3 : 2;
-  char* planes = static_cast<char*>(dev_alloc(c, size_t(nsteps) * size_t(nplanes) * 2048));
-  float* pilot = static_cast<float*>(dev_alloc(c, size_t(d) * 4));
-  double* corr = static_cast<double*>(dev_alloc(c, 64 * 8));
-  try {
-    zero(c, corr, 64 * 8);
-    hipLaunchKernelGGL(k_project_prep, dim3((unsigned)nsteps), dim3(128), 0, st, W, d, int(k), k, mean, planes, pilot, corr, nplanes);
-    const int64_t wgs = (n + 4 * 32 * PJ_MT - 1) / (4 * 32 * PJ_MT);
-    if (nplanes == 2) {
-      const size_t lds = size_t(4) * PJ<2>::R * PJ<2>::SLOT + size_t(d) * 4;
-      sp_allow_lds(reinterpret_cast<const void*>(&k_project_split<2>), c->device, int(lds));
-      hipLaunchKernelGGL(k_project_split<2>, dim3((unsigned)wgs), dim3(256), lds, st, X, n, d, ld, pilot, planes, mean ? corr : nullptr, out, ldo, int(k));
-    } else {
-      const size_t lds = size_t(4) * PJ<3>::R * PJ<3>::SLOT + size_t(d) * 4;
-      sp_allow_lds(reinterpret_cast<const void*>(&k_project_split<3>), c->device, int(lds));
-      hipLaunchKernelGGL(k_project_split<3>, dim3((unsigned)wgs), dim3(256), lds, st, X, n, d, ld, pilot, planes, mean ? corr : nullptr, out, ldo, int(k));
-    }
-    CCZ_LAUNCH_CHECK();
-  } catch (...) {
-    dev_free(c, corr); dev_free(c, pilot); dev_free(c, planes);
-    throw;
+  PoolBuf<char> planes_own(c, nsteps * nplanes * 2048);
+  PoolBuf<float> pilot_own(c, d);
+  DBuf corr_own(c, 64);
+  char* planes = planes_own;
+  float* pilot = pilot_own;
+  double* corr = corr_own;
+  zero(c, corr, 64 * 8);
+  hipLaunchKernelGGL(k_project_prep, dim3((unsigned)nsteps), dim3(128), 0, st, W, d, int(k), k, mean, planes, pilot, corr, nplanes);
+  const int64_t wgs = (n + 4 * 32 * PJ_MT - 1) / (4 * 32 * PJ_MT);
+  if (nplanes == 2) {
+    const size_t lds = size_t(4) * PJ<2>::R * PJ<2>::SLOT + size_t(d) * 4;
+    sp_allow_lds(reinterpret_cast<const void*>(&k_project_split<2>), c->device, int(lds));
+    hipLaunchKernelGGL(k_project_split<2>, dim3((unsigned)wgs), dim3(256), lds, st, X, n, d, ld, pilot, planes, mean ? corr : nullptr, out, ldo, int(k));
+  } else {
+    const size_t lds = size_t(4) * PJ<3>::R * PJ<3>::SLOT + size_t(d) * 4;
+    sp_allow_lds(reinterpret_cast<const void*>(&k_project_split<3>), c->device, int(lds));
+    hipLaunchKernelGGL(k_project_split<3>, dim3((unsigned)wgs), dim3(256), lds, st, X, n, d, ld, pilot, planes, mean ? corr : nullptr, out, ldo, int(k));
   }
-  dev_free(c, corr); dev_free(c, pilot); dev_free(c, planes);
+  CCZ_LAUNCH_CHECK();
 }
 
 }  // namespace ccz
