@@ -149,6 +149,8 @@ SIGNATURES = {
     "ccz_gfa_peek": (_int, [_vp, _vp, _int, _int, _pdbl]),
     "ccz_gfa_get_result": (_int, [_vp, _vp, _pint, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
     "ccz_gfa_sumsq": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
+    "ccz_kr_moment": (_int, [_vp, C.POINTER(View), _int, _i64, _dbl, _vp]),
+    "ccz_kr_apply": (_int, [_vp, C.POINTER(View), _int, _i64, _vp, _int, _dbl, _vp, _i64]),
 }
 
 

@@ -29,6 +29,10 @@ void pair_loss_moments_impl(ccz_ctx* c, const double* mom, int64_t n, const int6
 void loss_status_take(ccz_ctx* c, bool synchronise, int* view, int* pivot);
 void randn_fill_impl(ccz_ctx* c, int dtype, void* out, int64_t rows, int64_t cols, int64_t ld, uint64_t seed,
                      int64_t row0, int64_t row_stride, double scale, bool accumulate);
+// krmoment.hip
+void kr_moment_impl(ccz_ctx* c, const ccz_view* H, int n_views, int64_t n, double scale, double* M);
+void kr_apply_impl(ccz_ctx* c, const ccz_view* H, int n_views, int64_t n, const double* T, int mode, double scale, double* out,
+                   int64_t ldo);
 }  // namespace ccz
 
 
@@ -427,6 +431,15 @@ int ccz_transform(ccz_handle h, int dtype, const void* X_dev, int64_t n, int64_t
   CCZ_GUARD(h, {
     transform_impl(h, dtype, X_dev, n, d, ld, mean_dev, W_dev, k, out_dev, ldo);
   })
+}
+
+int ccz_kr_moment(ccz_handle h, const ccz_view* H_dev, int n_views, int64_t n, double scale, double* M_dev) {
+  CCZ_GUARD(h, ccz::kr_moment_impl(h, H_dev, n_views, n, scale, M_dev));
+}
+
+int ccz_kr_apply(ccz_handle h, const ccz_view* H_dev, int n_views, int64_t n, const double* T_dev, int mode, double scale,
+                 double* out_dev, int64_t ldo) {
+  CCZ_GUARD(h, ccz::kr_apply_impl(h, H_dev, n_views, n, T_dev, mode, scale, out_dev, ldo));
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 """Differentiable CCA objectives on the MI355X solver core."""
 
 from cca_zoo_amd.deep._score import score_representations
-from cca_zoo_amd.deep.objectives import CCALoss, GCCALoss, MCCALoss
+from cca_zoo_amd.deep.objectives import CCALoss, GCCALoss, MCCALoss, TCCALoss
 
-__all__ = ["CCALoss", "GCCALoss", "MCCALoss", "score_representations"]
+__all__ = ["CCALoss", "GCCALoss", "MCCALoss", "TCCALoss", "score_representations"]

@@ -1,7 +1,7 @@
 """DCCA correlation losses as ``nn.Module`` callables backed by libccz.
 
 Reference: cca_zoo/deep/objectives.py:9-21 (``_inv_sqrtm``), :24-102 (``CCALoss``),
-:105-153 (``MCCALoss``).  Contract kept: ``forward(list[Tensor (batch x d_i)]) ->
+:105-153 (``MCCALoss``), :155-220 (``GCCALoss``), :256-289 (``TCCALoss``).  Contract kept: ``forward(list[Tensor (batch x d_i)]) ->
 0-dim Tensor`` on the inputs' device/dtype, differentiable w.r.t. every input,
 ``ValueError`` matching "exactly 2" for a wrong number of views, stateless modules.
 
@@ -199,6 +199,36 @@ def _views_of(vs):
     return views
 
 
+def _daleckii_krein(w: torch.Tensor, Vr: torch.Tensor, f: torch.Tensor, eps: float, g64: torch.Tensor) -> torch.Tensor:
+    """``dA = V ((V' sym(G) V) o K) V'`` for ``F = V diag(f(lam)) V'``, ``f = max(., eps)^-1/2`` (rows of ``Vr`` = eigenvectors,
+    ``w`` = eigenvalues): ``K_ij = (f_i - f_j) / (lam_i - lam_j)``, ``f'(lam_i)`` on the diagonal and between equal eigenvalues,
+    ``f' = 0`` where the clamp is active.  The backward of :class:`_InvSqrtmFn` and the whitening step of :class:`_TCCALossFn`."""
+    d = int(w.shape[0])
+    h = _backend.handle_for([Vr])
+    g64 = (0.5 * (g64 + g64.t())).contiguous()                   # F is symmetric: only the symmetric part of G acts
+    fp = torch.where(w > eps, -0.5 * f ** 3, torch.zeros_like(f))     # f'(lam); 0 where the clamp is active
+    dl = w[:, None] - w[None, :]
+    close = dl.abs() <= 1e-12 * torch.clamp(w.abs().max(), min=1e-300)
+    K = torch.where(close, (0.5 * (fp[:, None] + fp[None, :])).expand(d, d), (f[:, None] - f[None, :]) / torch.where(close, torch.ones_like(dl), dl))
+    t1 = torch.empty((d, d), dtype=torch.float64, device=Vr.device)
+    M = torch.empty((d, d), dtype=torch.float64, device=Vr.device)
+    sp = _stream_ptr(Vr)
+    h.acquire(sp)
+    try:
+        h.gemm(False, False, d, d, d, 1.0, Vr.data_ptr(), d, g64.data_ptr(), d, 0.0, t1.data_ptr(), d)      # V' G   (rows of Vr = eigenvectors)
+        h.gemm(False, True, d, d, d, 1.0, t1.data_ptr(), d, Vr.data_ptr(), d, 0.0, M.data_ptr(), d)        # V' G V
+    finally:
+        h.release(sp)
+    MK = (M * K).contiguous()
+    h.acquire(sp)
+    try:
+        h.gemm(True, False, d, d, d, 1.0, Vr.data_ptr(), d, MK.data_ptr(), d, 0.0, t1.data_ptr(), d)       # V (M o K)
+        h.gemm(False, False, d, d, d, 1.0, t1.data_ptr(), d, Vr.data_ptr(), d, 0.0, M.data_ptr(), d)       # ... V'
+    finally:
+        h.release(sp)
+    return M
+
+
 class _InvSqrtmFn(torch.autograd.Function):
     """``A^-1/2`` with eigenvalues clamped at ``eps`` as a differentiable node (the reference's ``_inv_sqrtm`` sits inside
     the autograd graph of ``CCALoss.forward``, cca_zoo/deep/objectives.py:9-21, :94-97): ``A = V diag(lam) V'`` by the device
@@ -235,31 +265,7 @@ class _InvSqrtmFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, G):
         w, Vr, f = ctx.saved_tensors
-        d = int(w.shape[0])
-        h = _backend.handle_for([Vr])
-        g64 = G.detach().to(torch.float64)
-        g64 = (0.5 * (g64 + g64.t())).contiguous()                   # F is symmetric: only the symmetric part of G acts
-        fp = torch.where(w > ctx.eps, -0.5 * f ** 3, torch.zeros_like(f))     # f'(lam); 0 where the clamp is active
-        dl = w[:, None] - w[None, :]
-        close = dl.abs() <= 1e-12 * torch.clamp(w.abs().max(), min=1e-300)
-        K = torch.where(close, (0.5 * (fp[:, None] + fp[None, :])).expand(d, d), (f[:, None] - f[None, :]) / torch.where(close, torch.ones_like(dl), dl))
-        t1 = torch.empty((d, d), dtype=torch.float64, device=Vr.device)
-        M = torch.empty((d, d), dtype=torch.float64, device=Vr.device)
-        sp = _stream_ptr(Vr)
-        h.acquire(sp)
-        try:
-            h.gemm(False, False, d, d, d, 1.0, Vr.data_ptr(), d, g64.data_ptr(), d, 0.0, t1.data_ptr(), d)      # V' G   (rows of Vr = eigenvectors)
-            h.gemm(False, True, d, d, d, 1.0, t1.data_ptr(), d, Vr.data_ptr(), d, 0.0, M.data_ptr(), d)        # V' G V
-        finally:
-            h.release(sp)
-        MK = (M * K).contiguous()
-        h.acquire(sp)
-        try:
-            h.gemm(True, False, d, d, d, 1.0, Vr.data_ptr(), d, MK.data_ptr(), d, 0.0, t1.data_ptr(), d)       # V (M o K)
-            h.gemm(False, False, d, d, d, 1.0, t1.data_ptr(), d, Vr.data_ptr(), d, 0.0, M.data_ptr(), d)       # ... V'
-        finally:
-            h.release(sp)
-        return M.to(ctx.dtype), None
+        return _daleckii_krein(w, Vr, f, ctx.eps, G.detach().to(torch.float64)).to(ctx.dtype), None
 
 
 def _inv_sqrtm(A: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
@@ -473,3 +479,143 @@ class GCCALoss(nn.Module):
 
     def forward(self, representations: list[torch.Tensor]) -> torch.Tensor:
         return _GCCALossFn.apply(self.eps, *representations)
+
+
+class _TCCALossFn(torch.autograd.Function):
+    """Tensor CCA loss ``-||M||_F``, ``M = (1 / n) sum_s H_1[s] (x) .. (x) H_V[s]`` (reference:
+    cca_zoo/deep/objectives.py:260-289) as one node.  Per view: K1 moments, ``S = Z_c'Z_c / (n - 1) + eps I``, the device
+    Jacobi EVD, ``F = V diag(max(lam, eps)^-1/2) V'``, ``H = Z_c F``; then ``ccz_kr_moment`` -- the reference's
+    ``n x d_1 x .. x d_V`` tensor is never formed.  Backward, in closed form: ``T = -M / ||M||`` (zero where ``M`` is),
+    ``GH_j = ccz_kr_apply(T, mode j) / n``, ``dS`` by the Daleckii-Krein step of :class:`_InvSqrtmFn` applied to ``Z_c' GH_j``,
+    ``dZ_j = (GH_j - mean) F + 2 Z_c dS / (n - 1)``.  Everything is float64, whatever the inputs' dtype."""
+
+    @staticmethod
+    def forward(ctx, eps: float, *zs: torch.Tensor) -> torch.Tensor:
+        dev, dt, n = zs[0].device, zs[0].dtype, int(zs[0].shape[0])
+        h = _backend.handle_for(zs)
+        sp = _stream_ptr(zs[0])
+        per_view = []
+        for z in zs:
+            d = int(z.shape[1])
+            z64 = _view_of(z.detach().to(torch.float64))
+            mom = torch.empty(d * d + d, dtype=torch.float64, device=dev)
+            h.acquire(sp)
+            try:
+                h.moments([(z64.data_ptr(), d, z64.stride(0))], n, _backend.F64, True, mom.data_ptr(), pilot=False, timed=False)
+                h.moments_symmetrize(mom.data_ptr(), d)
+            finally:
+                h.release(sp)
+            s = mom[d * d:]
+            mean = s / n
+            S = (mom[:d * d].view(d, d) - s[:, None] * mean[None, :]) / (n - 1) + eps * torch.eye(d, dtype=torch.float64, device=dev)
+            zc = (z64 - mean).contiguous()
+            if d == 1:
+                w, Vr = S.reshape(1).clone(), torch.ones((1, 1), dtype=torch.float64, device=dev)
+            else:
+                a64 = S.contiguous()                                    # ccz_syevj overwrites its input
+                w = torch.empty(d, dtype=torch.float64, device=dev)
+                Vr = torch.empty((d, d), dtype=torch.float64, device=dev)   # row i = eigenvector i
+                h.acquire(sp)
+                try:
+                    h.check(h.lib.ccz_syevj(h.raw, C.c_void_p(a64.data_ptr()), d, C.c_void_p(w.data_ptr()), C.c_void_p(Vr.data_ptr()), None))
+                finally:
+                    h.release(sp)
+            f = torch.clamp(w, min=eps).rsqrt()
+            scaled = (Vr * f[:, None]).contiguous()                     # diag(f) V'
+            F = torch.empty((d, d), dtype=torch.float64, device=dev)
+            H = torch.empty((n, d), dtype=torch.float64, device=dev)
+            h.acquire(sp)
+            try:
+                h.gemm(True, False, d, d, d, 1.0, Vr.data_ptr(), d, scaled.data_ptr(), d, 0.0, F.data_ptr(), d)     # V diag(f) V'
+                h.gemm(False, False, n, d, d, 1.0, zc.data_ptr(), d, F.data_ptr(), d, 0.0, H.data_ptr(), d)         # Z_c F
+            finally:
+                h.release(sp)
+            per_view.append((zc, H, F, w, Vr, f))
+        M = torch.empty([int(z.shape[1]) for z in zs], dtype=torch.float64, device=dev)
+        views = _views_of([pv[1] for pv in per_view])
+        h.acquire(sp)
+        try:
+            h.check(h.lib.ccz_kr_moment(h.raw, views, len(zs), n, 1.0 / n, C.c_void_p(M.data_ptr())))
+        finally:
+            h.release(sp)
+        norm = (M * M).sum().sqrt()
+        if any(ctx.needs_input_grad[1:]):
+            ctx.save_for_backward(M, norm, *[t for pv in per_view for t in pv])
+            ctx.eps = float(eps)
+            ctx.dtypes = [z.dtype for z in zs]
+            ctx.wanted = list(ctx.needs_input_grad[1:])
+        return (-norm).to(dt)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        M, norm, *flat = ctx.saved_tensors
+        per_view = [flat[6 * i:6 * i + 6] for i in range(len(flat) // 6)]
+        n, dev = int(per_view[0][0].shape[0]), M.device
+        h = _backend.handle_for([M])
+        sp = _stream_ptr(M)
+        T = (-M / torch.where(norm > 0, norm, torch.ones_like(norm))).contiguous()      # ||M|| = 0: the zero subgradient
+        go = grad_out.detach().to(device=dev, dtype=torch.float64)
+        views = _views_of([pv[1] for pv in per_view])
+        grads = []
+        for j, ((zc, H, F, w, Vr, f), want, dt) in enumerate(zip(per_view, ctx.wanted, ctx.dtypes)):
+            if not want:
+                grads.append(None)
+                continue
+            d = int(H.shape[1])
+            GH = torch.empty((n, d), dtype=torch.float64, device=dev)
+            dF = torch.empty((d, d), dtype=torch.float64, device=dev)
+            h.acquire(sp)
+            try:
+                h.check(h.lib.ccz_kr_apply(h.raw, views, len(per_view), n, C.c_void_p(T.data_ptr()), j, 1.0 / n,
+                                           C.c_void_p(GH.data_ptr()), d))
+                h.gemm(True, False, d, d, n, 1.0, zc.data_ptr(), d, GH.data_ptr(), d, 0.0, dF.data_ptr(), d)        # Z_c' GH
+            finally:
+                h.release(sp)
+            dS2 = (_daleckii_krein(w, Vr, f, ctx.eps, dF) * (2.0 / (n - 1))).contiguous()
+            g = _project(GH, GH.mean(dim=0), F)                         # (GH - column mean) F; Z_c dS is centred already
+            h.acquire(sp)
+            try:
+                h.gemm(False, False, n, d, d, 1.0, zc.data_ptr(), d, dS2.data_ptr(), d, 1.0, g.data_ptr(), d)       # + 2 Z_c dS / (n - 1)
+            finally:
+                h.release(sp)
+            grads.append((go * g).to(dt))
+        return (None, *grads)
+
+
+class TCCALoss(nn.Module):
+    r"""Tensor CCA loss: ``-||M||_F`` with ``M = (1 / n) sum_s H_1[s] (x) .. (x) H_V[s]`` the cross-moment tensor of the
+    centred, ridge-whitened representations ``H_i = Z_c (Z_c'Z_c / (n - 1) + eps I)^-1/2`` (eigenvalues clamped at ``eps``).
+    2 to 8 views, ``prod d_i <= 2^24``; float32 batches are computed in float64.
+
+    Args:
+        eps: ridge added to the within-view batch covariances (default 1e-5).
+    """
+
+    _MAX_VIEWS = 8
+    _MAX_ENTRIES = 1 << 24
+
+    def __init__(self, eps: float = 1e-5) -> None:
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, representations: list[torch.Tensor]) -> torch.Tensor:
+        zs = list(representations)
+        if not 2 <= len(zs) <= self._MAX_VIEWS:
+            raise ValueError(f"TCCALoss expects 2 to {self._MAX_VIEWS} representations, got {len(zs)}.")
+        entries = 1
+        for z in zs:
+            if not isinstance(z, torch.Tensor) or z.dim() != 2:
+                raise ValueError("TCCALoss expects (batch, d_i) tensors")
+            if z.shape[0] != zs[0].shape[0]:
+                raise ValueError("TCCALoss expects (batch, d_i) tensors with equal batch size")
+            entries *= int(z.shape[1])
+        if entries < 1 or entries > self._MAX_ENTRIES:
+            raise ValueError(f"TCCALoss: the cross-moment tensor has {entries} entries; 1 to 2^24 are supported")
+        for z in zs:
+            _require_cuda(z, "TCCALoss")
+        from cca_zoo_amd import _dist
+
+        if _dist.is_sharded():
+            raise RuntimeError("TCCALoss under row_sharded() is not supported: whitening needs the global moments of every view")
+        return _TCCALossFn.apply(self.eps, *zs)

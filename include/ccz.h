@@ -612,6 +612,22 @@ CCZ_API int ccz_gfa_get_result(ccz_handle h, void* state, int* k_active, double*
  * noise variance that is constant within a view).  Synchronises. */
 CCZ_API int ccz_gfa_sumsq(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev, double* sumsq_host);
 
+/* ---- Khatri-Rao moment and its adjoint (tensor CCA) -------------------------------------------------------------------
+ * Views are float64 DEVICE matrices H_i (n x d_i), 2..8 of them, prod d_i <= 2^24.  Tensors are row-major, the last view's
+ * index fastest.  Both run on the handle's stream without a host wait and use no floating-point atomics: two calls give the
+ * same bits.  CCZ_EINVAL: n_views outside 2..8, prod d_i > 2^24, mode out of range, a bad view. */
+
+/* M[r_1 .. r_V] = scale * sum_s prod_i H_i[s, r_i]: the cross-moment tensor, as the product (H_1 (.) .. (.) H_{V-1})' H_V
+ * whose Khatri-Rao operand is formed in registers.  Replaces the n x d_1 x .. x d_V outer-product tensor and its mean over
+ * the batch: cca_zoo/deep/objectives.py:279-288, cca_zoo/linear/_tcca.py:99-109 */
+CCZ_API int ccz_kr_moment(ccz_handle h, const ccz_view* H_dev, int n_views, int64_t n, double scale, double* M_dev);
+
+/* out[s, a] = scale * sum_{r : r_mode = a} T[r] * prod_{i != mode} H_i[s, r_i]   (n x d_mode, row stride ldo): the adjoint of
+ * ccz_kr_moment with respect to view `mode` -- what autograd computes through the broadcast products of
+ * cca_zoo/deep/objectives.py:280-288 by keeping the n x prod d tensor alive. */
+CCZ_API int ccz_kr_apply(ccz_handle h, const ccz_view* H_dev, int n_views, int64_t n, const double* T_dev, int mode, double scale,
+                         double* out_dev, int64_t ldo);
+
 #ifdef __cplusplus
 }
 #endif
