@@ -49,10 +49,7 @@ using STR = const char*;
   X(SPLIT_SCRATCH_GB, REAL, 48.0, LIVE, "GiB of scratch of a split-route launch (at most 0.4 of the device, at least 8 MiB) -- gram_split.hip split_scratch_budget: knob; tests shrink it to force several row super-chunks") \
   X(SPLIT_ROWS, I64, 16384, LIVE, "rows a split-route workgroup accumulates in fp32 -- gram_split.hip gram_split_f32: A/B; tests shorten it") \
   X(SPLIT_ORDER, INT, 1, LIVE, "0: row blocks fastest in the split pass's grid (the first form), else panels fastest -- gram_split.hip launch_split_pass: A/B") \
-  X(SPLIT_XCH, INT, 1, LIVE, "0: direct 16-byte stores at a stride of 64 bytes (the first form), else whole-line stores -- gram_split.hip launch_split_pass: A/B") \
   X(SPLIT_WALK, INT, 0, LIVE, "1: every XCD walks the SAME row chunk also when ksplit % 8 == 0 -- gram_split.hip split_row_plan: A/B")       \
-  X(SPLIT_PIPE, STR, nullptr, LIVE, "f0,f1,..: leading row pieces as fractions in (0, 1) whose split pass runs on a side stream; unset / 0: one piece -- gram_split.hip split_pieces: A/B") \
-  X(SPLIT_PIPE_CUS, INT, 64, LIVE, "CUs of that side stream (0: no mask) -- gram_split.hip split_side_stream: A/B; a new width makes a new stream") \
   X(LOSS_K1_SPLIT, INT, 1, LIVE, "0 never, 1 split-route partial sums from 32768 rows on, 2 and above from 4096 -- gram_split.hip gram_partials_split_f32: knob") \
   /* ---- loss, projection, fp32 products (loss.hip, gemm_split.hip, project_split.hip, gemm_big.hip) ---- */                                 \
   X(LOSS_FUSED, INT, 1, ONCE, "0: every shape takes the wide route (super-blocked factorization, 128-tile GEMMs) -- loss.hip narrow_ok: test") \

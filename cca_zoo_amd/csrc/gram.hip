@@ -1161,6 +1161,75 @@ RowPlan plan_rows(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, int
   return rp;
 }
 
+// The K1 launch of fp32 views on the fp32 matrix pipe (pilot: null = unshifted), with the reduce over the partial tiles where the
+// staged kernel runs on a small grid.
+void launch_gram_f32(ccz_ctx* c, const TileTable& tt, const RowPlan& rp, int64_t n, double* G, int64_t D, const float* pilot) {
+  hipStream_t st = stream(c);
+  GramTile* d_tiles = tt.dev;
+  const int ntiles = tt.ntiles, per_xcd = rp.per_xcd;
+  const int64_t rows_per_wg = rp.rows_per_wg, ksplit = rp.ksplit, nblocks = rp.nblocks;
+  const bool fast = rp.fast, use_pilot = pilot != nullptr;
+  const size_t lds_bytes = size_t(2) * 2 * BK * T32 * sizeof(float);   // 64 KiB
+  const size_t fifo_bytes = size_t(4) * FR * FSLOT;                    // 128 KiB: four wave-private rings
+  const int impl_sel = env::once(env::GRAM_IMPL);
+  // pilot-shifted data on a chip-filling grid: the FIFO kernel with the subtraction at the fragment read, on the rows
+  // that form whole ring periods; the (< 32) rows left over go through the staged kernel, same pilot
+  const int fifo_pilot_env = env::once(env::GRAM_FIFO_PILOT);
+  const int64_t n_main = n / (FB * FR) * (FB * FR);
+  const bool fifo_pilot = fast && impl_sel != 0 && use_pilot && fifo_pilot_env != 0 && rp.sliced && n_main >= rows_per_wg;
+  // staged fp32 kernel on a small grid: per-(chunk, tile) partial sums + one reduce instead of contended atomics
+  PoolBuf<float> partial_own;
+  float* partial = nullptr;
+  const bool staged32 = !(fast && impl_sel != 0 && !use_pilot) && !fifo_pilot;
+  if (staged32 && ksplit >= 2 && !rp.sliced) {
+    const int64_t bytes = ksplit * int64_t(ntiles) * T32 * T32 * 4;
+    if (bytes <= env::gram_partial_cap()) partial = partial_own = PoolBuf<float>(c, bytes / 4);
+  }
+  if (fifo_pilot) {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32_fifo<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
+    hipLaunchKernelGGL(k_gram_f32_fifo<true>, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n_main,
+                       rows_per_wg, G, D, pilot);
+    if (n_main < n) {
+      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+      hipLaunchKernelGGL(k_gram_f32<true>, dim3((unsigned)ntiles), dim3(256), lds_bytes, st, d_tiles, ntiles, 0, int64_t(1), n, int64_t(FB * FR), G, D,
+                         pilot, static_cast<float*>(nullptr), n_main);
+    }
+  } else if (fast && impl_sel != 0 && !use_pilot) {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32_fifo<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
+    hipLaunchKernelGGL(k_gram_f32_fifo<false>, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D,
+                       static_cast<const float*>(nullptr));
+  } else if (fast) {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    hipLaunchKernelGGL(k_gram_f32<true>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D, pilot, partial, int64_t(0));
+  } else {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    hipLaunchKernelGGL(k_gram_f32<false>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D, pilot, partial, int64_t(0));
+  }
+  CCZ_LAUNCH_CHECK();
+  if (partial) {
+    hipLaunchKernelGGL(k_gram_reduce, dim3(256, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, ksplit, G, D);
+    CCZ_LAUNCH_CHECK();
+  }
+}
+
+// The K1 launch of fp64 views.
+void launch_gram_f64(ccz_ctx* c, const TileTable& tt, const RowPlan& rp, int64_t n, double* G, int64_t D) {
+  hipStream_t st = stream(c);
+  const dim3 grid((unsigned)rp.nblocks);
+  const size_t lds_bytes = size_t(2) * 2 * BK * T64 * sizeof(double);  // 64 KiB
+  if (rp.fast && env::once(env::GRAM64_IMPL) != 0) {
+    const size_t fifo_bytes = size_t(4) * FR * FSLOT;
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64_fifo), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
+    hipLaunchKernelGGL(k_gram_f64_fifo, grid, dim3(256), fifo_bytes, st, tt.dev, tt.ntiles, rp.per_xcd, rp.ksplit, n, rp.rows_per_wg, G, D);
+  } else if (rp.fast) {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    hipLaunchKernelGGL(k_gram_f64<true>, grid, dim3(256), lds_bytes, st, tt.dev, tt.ntiles, rp.per_xcd, rp.ksplit, n, rp.rows_per_wg, G, D);
+  } else {
+    CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    hipLaunchKernelGGL(k_gram_f64<false>, grid, dim3(256), lds_bytes, st, tt.dev, tt.ntiles, rp.per_xcd, rp.ksplit, n, rp.rows_per_wg, G, D);
+  }
+}
+
 // pilot_mode (fp32 only): 0 = never, 1 = automatic (column sums and sums of squares are inspected on the host: one small
 // read-back), 2 = always (device-side only, no host synchronisation).  Returns whether the pilot path ran.
 template <typename T>
@@ -1169,21 +1238,8 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   Impl* im = impl(c);
   hipStream_t st = stream(c);
   constexpr bool is32 = sizeof(T) == 4;
-  const int tile = is32 ? T32 : T64;
-  const TileTable tt = build_tile_table<T>(c, views, n_views, tile_cache);
-  GramTile* d_tiles = tt.dev;
-  const int ntiles = tt.ntiles;
-  const RowPlan rp = plan_rows<T>(c, views, n_views, n, ntiles, tt.fast);
-  const bool fast = rp.fast;
-  const int64_t rows_per_wg = rp.rows_per_wg, ksplit = rp.ksplit, nblocks = rp.nblocks;
-  const int per_xcd = rp.per_xcd;
-  const bool sliced = rp.sliced;
   const int ncu = std::max(1, im->props.multiProcessorCount);
-  const size_t lds_bytes = size_t(2) * 2 * BK * tile * sizeof(T);  // 64 KiB either way
-  // ---- column sums first: they are the means, and for fp32 views they decide (and define) the pilot shift ----
-  // (Round 3 tried to hide this 5.4 ms HBM-bound pass under the MFMA-bound K1 on a second stream, with the pilot decided
-  // from a strided sample: K1 then ran 7 ms LONGER -- the column-sum workgroups share the CUs' issue slots with K1's one
-  // wave per SIMD -- so the pass stays in front.)
+  // ---- the pilot mode and the arithmetic route first: they decide what the launch needs at all ----
   const int pilot_env = env::once(env::GRAM_PILOT);
   if (pilot_env == 0 || pilot_env == 1) pilot_mode = pilot_env == 1 ? 2 : 0;
   if (!is32) pilot_mode = 0;                                  // fp64 views accumulate in fp64: nothing to protect
@@ -1198,6 +1254,20 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
     if (split) pilot_mode = 2;
   }
   c->last_route = !is32 ? CCZ_K1_FP64 : (split ? CCZ_K1_BF16X2 : CCZ_K1_FP32);
+  // (k_pilot_fixup runs one grid row per column of G; checked before anything is enqueued where the pilot is already certain)
+  if (pilot_mode == 2 && D > 65535) fail(CCZ_EUNSUP, "gram: pilot fix-up supports D <= 65535");
+  // the fp32 and fp64 kernels walk a tile table over the views' pointers by a row plan; the split route keeps tables of its own
+  // (gram_split.hip) and uses neither
+  TileTable tt;
+  RowPlan rp;
+  if (!split) {
+    tt = build_tile_table<T>(c, views, n_views, tile_cache);
+    rp = plan_rows<T>(c, views, n_views, n, tt.ntiles, tt.fast);
+  }
+  // ---- column sums first: they are the means, and for fp32 views they decide (and define) the pilot shift ----
+  // (Round 3 tried to hide this 5.4 ms HBM-bound pass under the MFMA-bound K1 on a second stream, with the pilot decided
+  // from a strided sample: K1 then ran 7 ms LONGER -- the column-sum workgroups share the CUs' issue slots with K1's one
+  // wave per SIMD -- so the pass stays in front.)
   const double pilot_thr = env::once(env::GRAM_PILOT_RATIO);
   double* s_launch = s;            // column sums of THIS launch's rows (separate from the running sums in pilot modes)
   double* sq = nullptr;
@@ -1263,6 +1333,8 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
       if (ratio > worst) worst = ratio;
     }
     use_pilot = worst > pilot_thr;
+    // (only now certain; so far only this launch's own sums have been written, nothing has been added to G or s)
+    if (use_pilot && D > 65535) fail(CCZ_EUNSUP, "gram: pilot fix-up supports D <= 65535");
   }
   if (use_pilot && !split) {
     pilot = pilot_own = PoolBuf<float>(c, D);
@@ -1270,69 +1342,12 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   }
 
   if (time_it) CCZ_HIP(hipEventRecord(im->ev[0].get(), st));
-  const int impl_sel = env::once(env::GRAM_IMPL);
-  // pilot-shifted data on a chip-filling grid: the FIFO kernel with the subtraction at the fragment read, on the rows
-  // that form whole ring periods; the (< 32) rows left over go through the staged kernel, same pilot
-  const int fifo_pilot_env = env::once(env::GRAM_FIFO_PILOT);
-  const int64_t n_main = n / (FB * FR) * (FB * FR);
-  const bool fifo_pilot = is32 && fast && impl_sel != 0 && use_pilot && fifo_pilot_env != 0 && sliced && n_main >= rows_per_wg;
-  // staged fp32 kernel on a small grid: per-(chunk, tile) partial sums + one reduce instead of contended atomics
-  PoolBuf<float> partial_own;
-  float* partial = nullptr;
-  const bool staged32 = is32 && !(fast && impl_sel != 0 && !use_pilot) && !fifo_pilot;
-  if (staged32 && ksplit >= 2 && !sliced && !split) {
-    const int64_t bytes = ksplit * int64_t(ntiles) * T32 * T32 * 4;
-    if (bytes <= env::gram_partial_cap()) partial = partial_own = PoolBuf<float>(c, bytes / 4);
-  }
-  if (split) {
-    gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it);
-  } else if (is32) {
-    if (fifo_pilot) {
-      const size_t fifo_bytes = size_t(4) * FR * FSLOT;
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32_fifo<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
-      hipLaunchKernelGGL(k_gram_f32_fifo<true>, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n_main,
-                         rows_per_wg, G, D, pilot);
-      if (n_main < n) {
-        CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-        hipLaunchKernelGGL(k_gram_f32<true>, dim3((unsigned)ntiles), dim3(256), lds_bytes, st, d_tiles, ntiles, 0, int64_t(1), n, int64_t(FB * FR), G, D,
-                           pilot, static_cast<float*>(nullptr), n_main);
-      }
-    } else if (fast && impl_sel != 0 && !use_pilot) {
-      const size_t fifo_bytes = size_t(4) * FR * FSLOT;   // 128 KiB: four wave-private rings
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32_fifo<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
-      hipLaunchKernelGGL(k_gram_f32_fifo<false>, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D,
-                         static_cast<const float*>(nullptr));
-    } else if (fast) {
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-      hipLaunchKernelGGL(k_gram_f32<true>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D, pilot, partial, int64_t(0));
-    } else {
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f32<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-      hipLaunchKernelGGL(k_gram_f32<false>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D, pilot, partial, int64_t(0));
-    }
-  } else {
-    if (fast && env::once(env::GRAM64_IMPL) != 0) {
-      const size_t fifo_bytes = size_t(4) * FR * FSLOT;
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64_fifo), hipFuncAttributeMaxDynamicSharedMemorySize, int(fifo_bytes)));
-      hipLaunchKernelGGL(k_gram_f64_fifo, dim3((unsigned)nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D);
-    } else if (fast) {
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-      hipLaunchKernelGGL(k_gram_f64<true>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D);
-    } else {
-      CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_f64<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-      hipLaunchKernelGGL(k_gram_f64<false>, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, d_tiles, ntiles, per_xcd, ksplit, n, rows_per_wg, G, D);
-    }
-  }
+  if (split) gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it);
+  else if (is32) launch_gram_f32(c, tt, rp, n, G, D, pilot);
+  else launch_gram_f64(c, tt, rp, n, G, D);
   CCZ_LAUNCH_CHECK();
-  if (partial) {
-    hipLaunchKernelGGL(k_gram_reduce, dim3(256, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, ksplit, G, D);
-    CCZ_LAUNCH_CHECK();
-    partial_own.reset();
-  }
   if (time_it) CCZ_HIP(hipEventRecord(im->ev[1].get(), st));
-  if (use_pilot) {
-    if (D > 65535) fail(CCZ_EUNSUP, "gram: pilot fix-up supports D <= 65535");
-    hipLaunchKernelGGL(k_pilot_fixup, dim3((unsigned)((D + 255) / 256), (unsigned)D), dim3(256), 0, st, G, D, s_launch, double(n), pilot);
-  }
+  if (use_pilot) hipLaunchKernelGGL(k_pilot_fixup, dim3((unsigned)((D + 255) / 256), (unsigned)D), dim3(256), 0, st, G, D, s_launch, double(n), pilot);
   if (s_launch != s) hipLaunchKernelGGL(k_vec_add, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, s, s_launch, D);
   CCZ_LAUNCH_CHECK();
   if (time_it) {

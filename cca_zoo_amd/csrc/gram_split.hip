@@ -34,9 +34,6 @@
 //
 // Roofline: executed flops = 3 x n Dp (Dp + 256) on the bf16 pipe (2.5 PF dense peak); algorithmic F = n D (D + 1).
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "hip_common.h"
@@ -79,18 +76,19 @@ __device__ __forceinline__ void sp_wave_lds_sync() {    // lanes of ONE wave exc
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// XCH (default; CCZ_SPLIT_XCH=0 restores the direct stores): the 64 bytes a thread produces per plane are FOUR 16-byte pieces of a
-// 512-byte run, so a wave-level store of one piece per lane is 64 separate 16-byte writes at a stride of 64 bytes -- the PMC pass
+// The piece exchange: the 64 bytes a thread produces per plane are FOUR 16-byte pieces of a 512-byte run, so storing them as they
+// are makes every wave-level store 64 separate 16-byte writes at a stride of 64 bytes -- the PMC pass over that first form
 // (profiles/r06_split_pass_pmc_raw.md) counts 6.05e8 L2 requests per 262144 rows, 5.4e8 of them these partial writes, i.e. 80
-// requests per clock on 128 L2 channels.  With XCH the eight lanes of a column tile swap pieces through a wave-private 4 KB of LDS
-// (no workgroup barrier) so that store e of lane j is piece 8 e + j: every wave-level store is eight whole 128-byte lines.
-template <bool ALIGNED, bool XCH>
+// requests per clock on 128 L2 channels.  So the eight lanes of a column tile swap pieces through a wave-private 4 KB of LDS
+// (no workgroup barrier) until store e of lane j is piece 8 e + j: every wave-level store is eight whole 128-byte lines
+// (2.03e8 L2 requests per 262144 rows; the pass at the metric shape 14.0 -> 12.4 ms).
+template <bool ALIGNED>
 __global__ __launch_bounds__(256) void k_split_bf16x2(const SplitPanel* __restrict__ panels, SplitViews vws, int64_t r0, int64_t nrows, int64_t ksteps,
                                                       const float* __restrict__ pilot, char* __restrict__ planes,
                                                       double* __restrict__ msq, double* __restrict__ csum, int rb, int panel_fast) {
   __shared__ float red[4][256];
   __shared__ double redc[4][256];
-  __shared__ sp_v4u32 xch[XCH ? 4 : 1][XCH ? 256 : 1];      // per wave: 8 column tiles x 32 pieces of 16 bytes (one plane, one k half)
+  __shared__ sp_v4u32 xch[4][256];                          // per wave: 8 column tiles x 32 pieces of 16 bytes (one plane, one k half)
   // panel_fast: consecutive workgroups take the panels of ONE row block (together they read whole rows) instead of the row blocks
   // of one panel (a 1 KiB stripe of every 16 KiB row: the same few HBM channels for everybody) -- CCZ_SPLIT_ORDER
   const unsigned pidx = panel_fast ? blockIdx.x : blockIdx.y, ridx = panel_fast ? blockIdx.y : blockIdx.x;
@@ -151,38 +149,30 @@ __global__ __launch_bounds__(256) void k_split_bf16x2(const SplitPanel* __restri
       }
     }
     char* dst = out + (row >> 4) * SP_PSTEP + ((row >> 3) & 1) * 512;
-    if constexpr (XCH) {
-      // piece (tile t, column c) sits at xw[32 t + (c ^ ((c >> 3) & 3) ^ ((t & 1) << 3))]: the 8 lanes of a ds_write_b128 group
-      // (c = 4 j + e) then cover all eight 16-byte bank quads, and the 16 lanes of a ds_read_b128 group (c = 8 e + j over four
-      // tiles) all sixteen of a 256-byte row (MI355X_MICROARCH.md, LDS service groups) -- plain [32 t + c] is 4-way / 2-way
-      sp_v4u32* xw = xch[rg];
-      char* dst2 = dst - (cg & 7) * 48;                                // tile base + (cg & 7) * 16
-      const int t8 = ((cg >> 3) & 1) << 3, j = cg & 7;
-      const int wr = (cg >> 3) * 32 + ((4 * j) ^ t8), wx = j >> 1;     // + (e ^ wx)
-      const int rd = (cg >> 3) * 32;                                   // + ((8 e) ^ t8) + (j ^ e)
-      sp_wave_lds_sync();                                              // the previous pass's reads are done
+    // piece (tile t, column c) sits at xw[32 t + (c ^ ((c >> 3) & 3) ^ ((t & 1) << 3))]: the 8 lanes of a ds_write_b128 group
+    // (c = 4 j + e) then cover all eight 16-byte bank quads, and the 16 lanes of a ds_read_b128 group (c = 8 e + j over four
+    // tiles) all sixteen of a 256-byte row (MI355X_MICROARCH.md, LDS service groups) -- plain [32 t + c] is 4-way / 2-way
+    sp_v4u32* xw = xch[rg];
+    char* dst2 = dst - (cg & 7) * 48;                                // tile base + (cg & 7) * 16
+    const int t8 = ((cg >> 3) & 1) << 3, j = cg & 7;
+    const int wr = (cg >> 3) * 32 + ((4 * j) ^ t8), wx = j >> 1;     // + (e ^ wx)
+    const int rd = (cg >> 3) * 32;                                   // + ((8 e) ^ t8) + (j ^ e)
+    sp_wave_lds_sync();                                              // the previous pass's reads are done
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xw[wr + (e ^ wx)] = hw[e];
-      sp_wave_lds_sync();
+    for (int e = 0; e < 4; ++e) xw[wr + (e ^ wx)] = hw[e];
+    sp_wave_lds_sync();
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hw[e] = xw[rd + ((8 * e) ^ t8) + (j ^ e)];
-      sp_wave_lds_sync();
+    for (int e = 0; e < 4; ++e) hw[e] = xw[rd + ((8 * e) ^ t8) + (j ^ e)];
+    sp_wave_lds_sync();
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xw[wr + (e ^ wx)] = mw[e];
-      sp_wave_lds_sync();
+    for (int e = 0; e < 4; ++e) xw[wr + (e ^ wx)] = mw[e];
+    sp_wave_lds_sync();
 #pragma unroll
-      for (int e = 0; e < 4; ++e) mw[e] = xw[rd + ((8 * e) ^ t8) + (j ^ e)];
+    for (int e = 0; e < 4; ++e) mw[e] = xw[rd + ((8 * e) ^ t8) + (j ^ e)];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        *reinterpret_cast<sp_v4u32*>(dst2 + e * 128) = hw[e];
-        *reinterpret_cast<sp_v4u32*>(dst2 + SP_PLANE + e * 128) = mw[e];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        *reinterpret_cast<sp_v4u32*>(dst + e * 16) = hw[e];              // (plain stores: non-temporal ones made this pass 3.5x slower)
-        *reinterpret_cast<sp_v4u32*>(dst + SP_PLANE + e * 16) = mw[e];
-      }
+    for (int e = 0; e < 4; ++e) {
+      *reinterpret_cast<sp_v4u32*>(dst2 + e * 128) = hw[e];            // (plain stores: non-temporal ones made this pass 3.5x slower)
+      *reinterpret_cast<sp_v4u32*>(dst2 + SP_PLANE + e * 128) = mw[e];
     }
   }
   // msq: the four row groups of the workgroup -> one fp64 atomic per column
@@ -410,18 +400,14 @@ static bool split_views_arg(const ccz_view* views, int n_views, SplitViews* vws)
 }
 
 static void launch_split_pass(ccz_ctx* c, const SplitTables& tb, const SplitViews& vws, bool aligned, int64_t r0, int64_t rows, int64_t ksteps,
-                              const float* pilot, char* planes, double* msq, double* colsum, hipStream_t st = nullptr) {
-  if (!st) st = stream(c);
+                              const float* pilot, char* planes, double* msq, double* colsum) {
   const int rb = split_rows_per_block(ksteps * SP_K, tb.np, std::max(1, impl(c)->props.multiProcessorCount));
   const unsigned nrb = (unsigned)((ksteps * SP_K + rb - 1) / rb);
   // panels fastest in the grid (CCZ_SPLIT_ORDER=0: row blocks fastest, the first form).  Measured at the
   // metric shape, alternating runs (tools/r6_split_order.sh): 12.1 / 10.7 / 10.6 ms against 12.6 / 12.3 / 11.9 -- never slower.
   const int panel_fast = (env::live(env::SPLIT_ORDER) != 0 && nrb <= 65535u) ? 1 : 0;
   const dim3 grid = panel_fast ? dim3((unsigned)tb.np, nrb) : dim3(nrb, (unsigned)tb.np);
-  const bool xch = env::live(env::SPLIT_XCH) != 0;
-  auto kern = aligned ? (xch ? &k_split_bf16x2<true, true> : &k_split_bf16x2<true, false>)
-                      : (xch ? &k_split_bf16x2<false, true> : &k_split_bf16x2<false, false>);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, tb.panels, vws, r0, rows, ksteps, pilot, planes, msq, colsum, rb, panel_fast);
+  hipLaunchKernelGGL(aligned ? &k_split_bf16x2<true> : &k_split_bf16x2<false>, grid, dim3(256), 0, stream(c), tb.panels, vws, r0, rows, ksteps, pilot, planes, msq, colsum, rb, panel_fast);
 }
 
 // The K1-layout planes of ONE fp32 matrix X (rows x cols, ld): panels of 256 columns, `ksteps` k-steps of 16 rows each (rows past
@@ -528,75 +514,12 @@ bool gram_split_worthwhile(int64_t n, int64_t D) {
   return n >= 32768 && D >= 256 && double(n) * double(D) * double(D + 1) >= min_flop;
 }
 
-// Row pieces of one launch (in rows; whole units of a workgroup's row chunk except the last) -- an A/B switch, OFF by default.
-// The split pass is an HBM pass (13 ms of a 160 ms K1 at the metric shape) in front of a power-bound MFMA kernel, so round 6 tried to
-// hide it: cut the launch into a short leading piece and the rest, and run the split pass of piece p + 1 on a side stream under the
-// MFMA kernel of piece p.  Measured at n = 1e6, 2 x 4096 (profiles/r06_split_pipe_sweep.log): one piece 156.6 - 157.6 ms; piped with
-// the side stream on 32 / 64 / 128 CUs 199.5 / 180.0 / 168.4 ms, unmasked 159.1 ms (the pass's small workgroups fill every CU that
-// frees up and the two kernels serialise).  The MFMA kernel loses MORE than the pass's duration whenever the two really overlap: it
-// scales with the CUs it holds even at the power limit, and the pass's 4.7 TB/s stream evicts the panels it shares through L2.
-// CCZ_SPLIT_PIPE: unset / "0" = one piece; "f0,f1,.." = the leading pieces as fractions of the launch's rows (launches below 8 units =
-// 131072 rows stay whole).
-static std::vector<int64_t> split_pieces(int64_t rows, int64_t unit) {
-  std::vector<double> fr;
-  if (const char* e = env::live(env::SPLIT_PIPE)) {
-    fr.clear();
-    for (const char* q = e; *q;) {
-      char* end = nullptr;
-      const double f = strtod(q, &end);
-      if (end == q) break;
-      if (f > 0.0 && f < 1.0) fr.push_back(f);
-      q = *end == ',' ? end + 1 : end;
-      if (end && *end != ',' ) break;
-    }
-  }
-  std::vector<int64_t> out;
-  const int64_t T = (rows + unit - 1) / unit;
-  int64_t used = 0;
-  if (T >= 8 && fr.size() <= 6) {
-    for (double f : fr) {
-      const int64_t u = std::max<int64_t>(1, int64_t(f * double(T) + 0.5));
-      if (used + u >= T) break;
-      out.push_back(u * unit);
-      used += u;
-    }
-  }
-  out.push_back(rows - used * unit);
-  return out;
-}
-
-// The side stream of the piped launch (CCZ_SPLIT_PIPE), confined to a few CUs of every XCD when the runtime takes a CU mask: the
-// MFMA kernel's workgroups take whole CUs (512 VGPRs per lane, 128 KiB of LDS), so without the mask the small workgroups of the pass
-// fill every CU that frees up and the two kernels run one after the other.
-// CCZ_SPLIT_PIPE_CUS: CUs of the side stream (default 64 = 8 per XCD; 0: no mask).  nullptr: no second stream (one piece then).
-static hipStream_t split_side_stream(ccz_ctx* c) {
-  Impl* im = impl(c);
-  const int ncu = std::max(1, im->props.multiProcessorCount);
-  const int cus = env::live(env::SPLIT_PIPE_CUS);
-  if (im->split_side && cus == im->split_side->req) return im->split_side->st.get();
-  if (im->split_side && im->split_side->st) (void)hipStreamSynchronize(im->split_side->st.get());
-  Impl::SplitSide side;
-  side.req = cus;
-  if (cus > 0 && cus < ncu && ncu % 8 == 0) {
-    // bit i set iff (i / 8) % stride == 0: 8-bit groups, every stride-th one -- uniform over the XCDs whether the runtime deals the
-    // mask's bits round-robin over the XCDs (bit i -> XCD i % 8) or XCD by XCD
-    const int stride = std::max(1, ncu / cus);
-    std::vector<uint32_t> mask(size_t((ncu + 31) / 32), 0u);
-    int set = 0;
-    for (int i = 0; i < ncu; ++i)
-      if ((i / 8) % stride == 0) { mask[size_t(i >> 5)] |= 1u << (i & 31); ++set; }
-    if (hipExtStreamCreateWithCUMask(side.st.out(), uint32_t(mask.size()), mask.data()) == hipSuccess) side.cus = set;
-    else { (void)hipGetLastError(); side.st.reset(); }
-  }
-  if (!side.st && hipStreamCreateWithFlags(side.st.out(), hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); side.st.reset(); }
-  im->split_side = std::move(side);     // (an earlier side stream, drained above, is destroyed here)
-  return im->split_side->st.get();
-}
-
 // G (upper tiles) += sum over rows of d d' for d = x - pilot (pilot may be null: d = x), through the split-bf16 route;
 // colsum (may be null) += the exact fp64 column sums of x, gathered by the split pass on its way over the rows.
-// Everything is enqueued on the handle's stream; with time_it the three stages are timed with HIP events (one host wait per
-// row super-chunk) into c->last_split_ms / last_mfma_ms / last_reduce_ms.
+// Per row super-chunk one straight chain on the handle's stream: zero msq, split pass, MFMA kernel, reduce.  With time_it four HIP
+// events bracket the three stages (one host wait per row super-chunk) into c->last_split_ms / last_mfma_ms / last_reduce_ms.
+// (Round 6 also built a piped form, the split pass of the next row piece on a CU-masked side stream under the MFMA kernel of the
+// current one: slower in every setting, profiles/r06_split_pipe_sweep.log and DESIGN.md section 7 item 2, and removed.)
 void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, double* G, int64_t D, const float* pilot, double* colsum,
                     bool time_it) {
   Impl* im = impl(c);
@@ -610,133 +533,69 @@ void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   SplitViews vws{};
   const bool aligned = split_views_arg(views, n_views, &vws);
   const int np = tb.np, ntiles = tb.ntiles;
-  const SplitTile* d_tiles = tb.tiles;
-  PoolBuf<double> msq_own(c, D);
-  PoolBuf<char> planes_own;
-  PoolBuf<float> partial_own;
-  double* msq = msq_own;
-  char* planes = nullptr;
-  float* partial = nullptr;
-  // unwinding between the side stream's launches and the main stream's waits: the pool recycles in the order of the MAIN stream, so
-  // the side stream is drained before the buffers above go back (this is declared after them, hence unwinds before them)
-  struct Drain {
-    hipStream_t side = nullptr;            // set while split passes on the side stream have not been waited for by the main stream
-    ~Drain() { if (side) (void)hipStreamSynchronize(side); }
-  } drain;
+  PoolBuf<double> msq(c, D);
   // ---- rows per launch (scratch budget) and per workgroup ----
   const int ncu = std::max(1, im->props.multiProcessorCount);
   const int64_t max_steps = std::max<int64_t>(1, env::live(env::SPLIT_ROWS) / SP_K);
-  const double per_row = double(np) * SP_PSTEP / SP_K + double(ntiles) * (SP_T * SP_T * 4) / double(max_steps * SP_K);
+  const int64_t unit = max_steps * SP_K;
+  const double per_row = double(np) * SP_PSTEP / SP_K + double(ntiles) * (SP_T * SP_T * 4) / double(unit);
   const size_t budget = split_scratch_budget(c);
-  int64_t launch_rows = int64_t(double(budget) / per_row) / (max_steps * SP_K) * (max_steps * SP_K);
-  launch_rows = std::max<int64_t>(launch_rows, max_steps * SP_K);
+  int64_t launch_rows = std::max<int64_t>(int64_t(double(budget) / per_row) / unit * unit, unit);
   const int64_t n_launch = (n + launch_rows - 1) / launch_rows;
   launch_rows = ((n + n_launch - 1) / n_launch + SP_K - 1) / SP_K * SP_K;       // equal super-chunks
   const size_t fifo_bytes = size_t(SP_NST) * SP_STAGE;
   sp_allow_lds(reinterpret_cast<const void*>(&k_gram_bf16x2), c->device, int(fifo_bytes));
   c->last_split_ms = c->last_mfma_ms = c->last_reduce_ms = 0.0;
-  size_t planes_cap = 0, partial_cap = 0;
-  bool launched = false;
- retry_smaller:
-  try {
+  // ---- plan, allocate, and only then enqueue: every super-chunk but the last has launch_rows rows, and the scratch is sized for the
+  // larger of the two plans (split_row_plan is a cost search: the shorter last super-chunk may come out with MORE row chunks), so
+  // an allocation that fails does so before anything has been added to G ----
+  PoolBuf<char> planes;
+  PoolBuf<float> partial;
+  SplitRowPlan rp_full, rp_last;
+  for (;;) {
+    const int64_t full_steps = (std::min(launch_rows, n) + SP_K - 1) / SP_K;
+    const int64_t last_steps = (n - (n - 1) / launch_rows * launch_rows + SP_K - 1) / SP_K;
+    rp_full = split_row_plan(full_steps, ntiles, max_steps, ncu);
+    rp_last = split_row_plan(last_steps, ntiles, max_steps, ncu);
+    try {
+      planes = PoolBuf<char>(c, int64_t(np) * full_steps * SP_PSTEP);
+      partial = PoolBuf<float>(c, std::max(rp_full.ksplit, rp_last.ksplit) * int64_t(ntiles) * (SP_T * SP_T));
+      break;
+    } catch (const Error& e) {
+      // the scratch did not fit (another library holds most of HBM): halve the row super-chunk and plan again
+      if (e.code != CCZ_ENOMEM || launch_rows <= unit) throw;
+      planes.reset();
+      launch_rows = std::max<int64_t>(unit, launch_rows / 2 / unit * unit);
+    }
+  }
+  hipEvent_t ev[4] = {};               // before the split pass, after it, after the MFMA kernel, after the reduce
+  for (int q = 0; time_it && q < 4; ++q) {
+    if (!im->sp_ev[q]) CCZ_HIP(hipEventCreate(im->sp_ev[q].out()));
+    ev[q] = im->sp_ev[q].get();
+  }
   for (int64_t r0 = 0; r0 < n; r0 += launch_rows) {
-    const int64_t rows = std::min(launch_rows, n - r0);
-    // row pieces of this super-chunk: the split pass of piece p + 1 runs on the side stream under the MFMA kernel of piece p
-    std::vector<int64_t> piece_rows = split_pieces(rows, max_steps * SP_K);
-    hipStream_t side = piece_rows.size() > 1 ? split_side_stream(c) : nullptr;
-    if (!side) piece_rows.assign(1, rows);
-    const int npc = int(piece_rows.size());
-    struct Piece { int64_t r0, rows, ksteps, slice0; size_t planes_off; SplitRowPlan rp; };
-    std::vector<Piece> pcs;
-    pcs.resize(size_t(npc));
-    size_t planes_bytes = 0;
-    int64_t slices = 0;
-    {
-      int64_t off = 0;
-      for (int p = 0; p < npc; ++p) {
-        Piece& pc = pcs[size_t(p)];
-        pc.r0 = r0 + off;
-        pc.rows = piece_rows[size_t(p)];
-        pc.ksteps = (pc.rows + SP_K - 1) / SP_K;
-        pc.rp = split_row_plan(pc.ksteps, ntiles, max_steps, ncu);
-        pc.planes_off = planes_bytes;
-        pc.slice0 = slices;
-        planes_bytes += size_t(np) * size_t(pc.ksteps) * SP_PSTEP;
-        slices += pc.rp.ksplit;
-        off += pc.rows;
-      }
-    }
-    const size_t partial_bytes = size_t(slices) * size_t(ntiles) * (SP_T * SP_T * 4);
-    // (the old block goes back BEFORE the larger one is asked for: the pool may hand the same block out again)
-    if (planes_bytes > planes_cap) { planes_own.reset(); planes = planes_own = PoolBuf<char>(c, int64_t(planes_bytes)); planes_cap = planes_bytes; }
-    if (partial_bytes > partial_cap) { partial_own.reset(); partial = partial_own = PoolBuf<float>(c, int64_t(partial_bytes / 4)); partial_cap = partial_bytes; }
-    // events: [0] before split 0, [1] after it (the side stream's go-ahead), [4p + 2] after the MFMA kernel of piece p; per piece
-    // p >= 1: [4p - 1] / [4p] before / after its split (side stream), [4p + 1] after the main stream's wait; [4 npc - 1] after the reduce
-    const size_t nev = size_t(4 * npc);
-    while (im->sp_ev.size() < nev) {
-      Event e;
-      CCZ_HIP(hipEventCreate(e.out()));
-      im->sp_ev.push_back(std::move(e));
-    }
-    hipEvent_t ev[4 * 7];                  // (split_pieces gives at most 7 pieces)
-    for (size_t q = 0; q < nev; ++q) ev[q] = im->sp_ev[q].get();
-    launched = true;                     // (from here on the super-chunks are no larger than this one: no further allocation)
-    drain.side = side;
+    const int64_t rows = std::min(launch_rows, n - r0), ksteps = (rows + SP_K - 1) / SP_K;
+    const SplitRowPlan& rp = r0 + launch_rows < n ? rp_full : rp_last;
     zero(c, msq, size_t(D) * 8);
     if (time_it) CCZ_HIP(hipEventRecord(ev[0], st));
-    launch_split_pass(c, tb, vws, aligned, pcs[0].r0, pcs[0].rows, pcs[0].ksteps, pilot, planes, msq, colsum, st);
-    if (time_it || side) CCZ_HIP(hipEventRecord(ev[1], st));
-    if (side) {
-      // (the go-ahead also orders the side stream behind the zeroing of msq, the pilot and the previous super-chunk's readers of `planes`)
-      CCZ_HIP(hipStreamWaitEvent(side, ev[1], 0));
-      for (int p = 1; p < npc; ++p) {
-        const Piece& pc = pcs[size_t(p)];
-        if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p - 1], side));
-        launch_split_pass(c, tb, vws, aligned, pc.r0, pc.rows, pc.ksteps, pilot, planes + pc.planes_off, msq, colsum, side);
-        CCZ_HIP(hipEventRecord(ev[4 * p], side));
-      }
-    }
-    for (int p = 0; p < npc; ++p) {
-      const Piece& pc = pcs[size_t(p)];
-      if (p > 0) {
-        CCZ_HIP(hipStreamWaitEvent(st, ev[4 * p], 0));
-        if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 1], st));
-      }
-      hipLaunchKernelGGL(k_gram_bf16x2, dim3((unsigned)pc.rp.nblocks), dim3(256), fifo_bytes, st, d_tiles, ntiles, pc.rp.per_xcd, pc.rp.ksplit,
-                         planes + pc.planes_off, pc.ksteps, pc.rp.steps_per_wg, partial + pc.slice0 * int64_t(ntiles) * (SP_T * SP_T));
-      if (time_it) CCZ_HIP(hipEventRecord(ev[4 * p + 2], st));
-    }
-    drain.side = nullptr;                 // (the main stream has waited for every split pass of the side stream)
-    hipLaunchKernelGGL(k_split_reduce, dim3(64, (unsigned)ntiles), dim3(256), 0, st, partial, d_tiles, ntiles, slices, G, D, msq);
+    launch_split_pass(c, tb, vws, aligned, r0, rows, ksteps, pilot, planes, msq, colsum);
+    if (time_it) CCZ_HIP(hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(k_gram_bf16x2, dim3((unsigned)rp.nblocks), dim3(256), fifo_bytes, st, tb.tiles, ntiles, rp.per_xcd, rp.ksplit, planes.get(), ksteps,
+                       rp.steps_per_wg, partial.get());
+    if (time_it) CCZ_HIP(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(k_split_reduce, dim3(64, (unsigned)ntiles), dim3(256), 0, st, partial.get(), tb.tiles, ntiles, rp.ksplit, G, D, msq.get());
     CCZ_LAUNCH_CHECK();
     if (time_it) {
-      hipEvent_t last = ev[4 * npc - 1];
-      CCZ_HIP(hipEventRecord(last, st));
-      CCZ_HIP(hipEventSynchronize(last));
+      CCZ_HIP(hipEventRecord(ev[3], st));
+      CCZ_HIP(hipEventSynchronize(ev[3]));
       float a = 0.f;
       CCZ_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
       c->last_split_ms += a;
       CCZ_HIP(hipEventElapsedTime(&a, ev[1], ev[2]));
       c->last_mfma_ms += a;
-      for (int p = 1; p < npc; ++p) {
-        CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p - 1], ev[4 * p]));
-        c->last_split_ms += a;             // (under the previous piece's MFMA kernel: the stage times of a piped launch overlap)
-        CCZ_HIP(hipEventElapsedTime(&a, ev[4 * p + 1], ev[4 * p + 2]));
-        c->last_mfma_ms += a;
-      }
-      CCZ_HIP(hipEventElapsedTime(&a, ev[4 * (npc - 1) + 2], last));
+      CCZ_HIP(hipEventElapsedTime(&a, ev[2], ev[3]));
       c->last_reduce_ms += a;
     }
-  }
-  } catch (const Error& e) {
-    // the scratch did not fit (another library holds most of HBM): halve the row super-chunk and start over -- nothing has
-    // been enqueued yet when the FIRST super-chunk's buffers cannot be allocated
-    if (e.code != CCZ_ENOMEM || launched || launch_rows <= max_steps * SP_K) throw;
-    planes_own.reset(); planes = nullptr;
-    partial_own.reset(); partial = nullptr;
-    planes_cap = partial_cap = 0;
-    launch_rows = std::max<int64_t>(max_steps * SP_K, launch_rows / 2 / (max_steps * SP_K) * (max_steps * SP_K));
-    goto retry_smaller;
   }
 }
 

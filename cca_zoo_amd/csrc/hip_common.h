@@ -138,16 +138,9 @@ struct Impl {
                                     // (ccz_solve_defer, or the handle's own event behind an unpack on a foreign stream)
   Event defer_own_ev;
   bool adopted = false;             // c->stream is a caller's stream (ccz_stream_adopt) until the next acquire
-  // gram_split.hip: stage boundaries and hand-overs of a split-route launch (timing events, grown on demand), and the side stream the
-  // split pass of the NEXT row piece runs on under the MFMA kernel of the current one.  split_side is empty until the first piped
-  // launch asks; then it says what was asked for and holds the stream, or none when the runtime refused (one piece then)
-  std::vector<Event> sp_ev;
-  struct SplitSide {
-    Stream st;                      // CU-masked when the runtime allows
-    int req = 0;                    // CCZ_SPLIT_PIPE_CUS the side stream was made for
-    int cus = 0;                    // CUs the side stream is confined to (0: no mask)
-  };
-  std::optional<SplitSide> split_side;
+  // gram_split.hip: timing events at the stage boundaries of a split-route launch (before the split pass, after it, after the MFMA
+  // kernel, after the reduce), created by the first timed launch
+  Event sp_ev[4];
   // comm.hip: ccz_moments_exchange -- the packed blocks buffer the handle keeps between fits (grown on demand), the stream its
   // collectives run on and the events that tie it to the handle's stream: packed (main -> exchange), head reduced, tail unpacked
   DevMem<> xchg_buf;
