@@ -151,6 +151,13 @@ SIGNATURES = {
     "ccz_gfa_sumsq": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
     "ccz_kr_moment": (_int, [_vp, C.POINTER(View), _int, _i64, _dbl, _vp]),
     "ccz_kr_apply": (_int, [_vp, C.POINTER(View), _int, _i64, _vp, _int, _dbl, _vp, _i64]),
+    "ccz_cp_create": (_int, [_vp, _int, _pi64, _i64, _dbl, _i64, _i64, C.POINTER(_vp)]),
+    "ccz_cp_destroy": (_int, [_vp, _vp]),
+    "ccz_cp_setup": (_int, [_vp, _vp, _vp]),
+    "ccz_cp_set_init": (_int, [_vp, _vp, _pdbl]),
+    "ccz_cp_iterations": (_int, [_vp, _vp, _i64, _pi64, _pint]),
+    "ccz_cp_status": (_int, [_vp, _vp, _pi64, _pint, _pint, _pdbl, _pdbl]),
+    "ccz_cp_get_result": (_int, [_vp, _vp, _pdbl, _pdbl, _pi64]),
 }
 
 

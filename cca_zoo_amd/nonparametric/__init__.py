@@ -2,5 +2,6 @@
 
 from cca_zoo_amd.nonparametric._kcca import KCCA
 from cca_zoo_amd.nonparametric._kgcca import KGCCA
+from cca_zoo_amd.nonparametric._ktcca import KTCCA
 
-__all__ = ["KCCA", "KGCCA"]
+__all__ = ["KCCA", "KGCCA", "KTCCA"]

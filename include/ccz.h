@@ -628,6 +628,56 @@ CCZ_API int ccz_kr_moment(ccz_handle h, const ccz_view* H_dev, int n_views, int6
 CCZ_API int ccz_kr_apply(ccz_handle h, const ccz_view* H_dev, int n_views, int64_t n, const double* T_dev, int mode, double scale,
                          double* out_dev, int64_t ldo);
 
+/* ---- CP-ALS of a dense float64 tensor (csrc/cp_als.hip): the factor step of TCCA / KTCCA ------------------------------------
+ * The tensor M lies in DEVICE memory in ccz_kr_moment's layout (row-major, the last mode's index fastest): order V = 2..8,
+ * prod d_i <= 2^24, rank k = 1..32, k <= min d_i.  The algorithm is tensorly's documented parafac with the defaults the
+ * reference calls it with (init="svd", n_iter_max=100, tol=1e-8, no normalisation, stop on the absolute change of the
+ * reconstruction error), written out:
+ *   unfold(T, m) = moveaxis(T, m, 0).reshape(d_m, -1)
+ *   init: A_m = the k leading left singular vectors of unfold(M, m), every column's entry of largest magnitude positive
+ *   iteration t, for m = 0 .. V-1 in turn: P = Hadamard product over i != m of A_i'A_i, G = unfold(M, m) khatri_rao(A_i, i != m),
+ *     A_m = G P^-1; then F2 = sum of the Hadamard product of all A_i'A_i, ip = sum G o A_m of the last mode,
+ *     e_t = sqrt|normM^2 + F2 - 2 ip| / normM; the fit stops after iteration t when t >= 1 and |e_{t-1} - e_t| < tol, after
+ *     max_iter iterations, or when a pivot of P is zero or not finite ("singular").
+ * Whole iterations run on the device behind a status word, in chunks without a host wait; every sum has a fixed order (two fits
+ * give the same bits, whatever the chunk length).  k > min d_i is refused (tensorly would pad the init with random columns).
+ * cca_zoo/linear/_tcca.py:111-117, cca_zoo/nonparametric/_ktcca.py:130-136 */
+#define CCZ_CP_RUNNING 0
+#define CCZ_CP_TOL 1
+#define CCZ_CP_MAXITER 2
+#define CCZ_CP_SINGULAR 3
+
+/* Create a fit state for tensors of `order` modes of widths dims[i], rank k, up to chunk_iters iterations per
+ * ccz_cp_iterations call.  CCZ_EUNSUP: order outside 2..8, k outside 1..32, prod dims > 2^24.  CCZ_EINVAL: k > min dims, an
+ * empty mode, tol < 0 or NaN, max_iter or chunk_iters < 1.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_create(ccz_handle h, int order, const int64_t* dims, int64_t k, double tol, int64_t max_iter,
+                          int64_t chunk_iters, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_destroy(ccz_handle h, void* state);
+
+/* A new fit of the tensor at M_dev: its unfoldings (made once), ||M||_F, the SVD init, the status word.  M_dev is read by
+ * every later ccz_cp_iterations of this fit and must stay unchanged until they have run.  May wait for the device (the
+ * symmetric EVD behind the init reads its eigenvalues on the host).  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_setup(ccz_handle h, void* state, const double* M_dev);
+
+/* Restart the fit of the tensor of the last ccz_cp_setup from the given factors (host, float64, A_m as d_m x k row-major,
+ * modes back to back) instead of the SVD init.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_set_init(ccz_handle h, void* state, const double* factors_host);
+
+/* Enqueue n_iters (<= chunk_iters) iterations.  Returns without waiting for the device; the only host wait is for the chunk
+ * that used the same status slot two calls earlier, whose state is returned in iters_known / stopped_known (-1 / 0 when
+ * there is none yet).  Iterations after the stop are no-ops.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_iterations(ccz_handle h, void* state, int64_t n_iters, int64_t* iters_known, int* stopped_known);
+
+/* Iterations done, whether the fit has stopped and why (CCZ_CP_*), the last error e_t and the last |e_{t-1} - e_t|.
+ * Synchronises.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_status(ccz_handle h, void* state, int64_t* iters, int* stopped, int* reason, double* err, double* decrease);
+
+/* The factors (layout of ccz_cp_set_init) and the error trace e_0 .. e_{iters-1} (size it for max_iter) to the host; NULL
+ * outputs are skipped.  Synchronises.  (_tcca.py:111-117, _ktcca.py:130-136) */
+CCZ_API int ccz_cp_get_result(ccz_handle h, void* state, double* factors_host, double* trace_host, int64_t* n_trace);
+
 #ifdef __cplusplus
 }
 #endif
