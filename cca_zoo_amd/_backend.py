@@ -112,6 +112,8 @@ SIGNATURES = {
     "ccz_pair_loss_forward": (_int, [_vp, _int, C.POINTER(View), _int, _i64, _dbl, _vp, _vp]),
     "ccz_pair_loss_backward": (_int, [_vp, _int, C.POINTER(View), _int, _i64, _vp, _vp, C.POINTER(_vp), _pi64]),
     "ccz_cca_loss_moments": (_int, [_vp, _vp, _i64, _i64, _i64, _dbl, C.POINTER(_dbl), _vp, _vp]),
+    "ccz_moment_loss_state_bytes": (_i64, [_int, _i64, _int]),
+    "ccz_moment_loss_forward": (_int, [_vp, _int, _int, _pdbl, C.POINTER(View), _int, _i64, C.POINTER(View), _i64, _vp, _vp, _vp, _vp]),
     "ccz_pair_loss_moments": (_int, [_vp, _vp, _i64, _pi64, _int, _dbl, C.POINTER(_dbl), _vp, _vp]),
     "ccz_cholinv": (_int, [_vp, _int, C.POINTER(_vp), _pi64, C.POINTER(_vp), C.POINTER(_vp)]),
     "ccz_randn_fill": (_int, [_vp, _int, _vp, _i64, _i64, _i64, C.c_uint64, _i64, _i64, _dbl, _int]),

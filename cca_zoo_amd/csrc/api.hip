@@ -29,6 +29,10 @@ void pair_loss_moments_impl(ccz_ctx* c, const double* mom, int64_t n, const int6
 void loss_status_take(ccz_ctx* c, bool synchronise, int* view, int* pivot);
 void randn_fill_impl(ccz_ctx* c, int dtype, void* out, int64_t rows, int64_t cols, int64_t ld, uint64_t seed,
                      int64_t row0, int64_t row_stride, double scale, bool accumulate);
+// ssl_loss.hip
+int64_t moment_loss_state_bytes_impl(int dtype, int64_t d, int m);
+void moment_loss_forward_impl(ccz_ctx* c, int dtype, int kind, const double* params, const ccz_view* z, int m, int64_t n, const ccz_view* zi,
+                              int64_t n_ind, void* loss_dev, double* terms_dev, void* state, void* state_ind);
 // krmoment.hip
 void kr_moment_impl(ccz_ctx* c, const ccz_view* H, int n_views, int64_t n, double scale, double* M);
 void kr_apply_impl(ccz_ctx* c, const ccz_view* H, int n_views, int64_t n, const double* T, int mode, double scale, double* out,
@@ -389,6 +393,14 @@ int ccz_pair_loss_forward(ccz_handle h, int dtype, const ccz_view* z_dev, int n_
 int ccz_pair_loss_backward(ccz_handle h, int dtype, const ccz_view* z_dev, int n_views, int64_t n, const void* state_dev,
                            const void* grad_out_dev, void* const* g_dev, const int64_t* ldg) {
   CCZ_GUARD(h, ccz::pair_loss_backward_impl(h, dtype, z_dev, n_views, n, state_dev, grad_out_dev, g_dev, ldg));
+}
+
+int64_t ccz_moment_loss_state_bytes(int dtype, int64_t d, int n_views) { return ccz::moment_loss_state_bytes_impl(dtype, d, n_views); }
+
+int ccz_moment_loss_forward(ccz_handle h, int dtype, int kind, const double* params, const ccz_view* z_dev, int n_views, int64_t n,
+                            const ccz_view* ind_dev, int64_t n_ind, void* loss_dev, double* terms_dev, void* state_dev, void* state_ind_dev) {
+  CCZ_GUARD(h, ccz::moment_loss_forward_impl(h, dtype, kind, params, z_dev, n_views, n, ind_dev, n_ind, loss_dev, terms_dev, state_dev,
+                                             state_ind_dev));
 }
 
 int ccz_cca_loss_moments(ccz_handle h, const double* moments_dev, int64_t n_rows, int64_t d1, int64_t d2, double eps,

@@ -302,6 +302,26 @@ CCZ_API int ccz_pair_loss_forward(ccz_handle h, int dtype, const ccz_view* z_dev
                           void* loss_dev, void* state_dev);
 CCZ_API int ccz_pair_loss_backward(ccz_handle h, int dtype, const ccz_view* z_dev, int n_views, int64_t n,
                            const void* state_dev, const void* grad_out_dev, void* const* g_dev, const int64_t* ldg);
+/* Moment-map losses of the reference's self-supervised models (cca_zoo/deep/_dcca_ey.py:10-111, _barlowtwins.py:83-112,
+ * _vicreg.py:12-67 and :142-169, _dcca_sdl.py:12-26 and :100-121) for n_views views of ONE width d: the value and the terms from one K1
+ * pass over [z_1 .. z_m], a map on the D x D moments and, for VICReg / SDL, a streaming pass for mean((z_1 - z_2)^2).
+ *   kind            params                              views    terms_dev (3 doubles, may be NULL)
+ *   CCZ_MOMENT_EY      --  (params may be NULL)            2 .. 8   rewards, penalties, 0
+ *   CCZ_MOMENT_BARLOW  lam                                 2        invariance, redundancy, 0
+ *   CCZ_MOMENT_VICREG  sim_coeff, std_coeff, cov_coeff     2        sim_loss, var_loss, cov_loss
+ *   CCZ_MOMENT_SDL     lam                                 2 .. 8   l2, sdl, 0        (d >= 2)
+ * loss_dev: ONE element of `dtype`, the objective.  state_dev (NULL: forward only): ccz_moment_loss_state_bytes(dtype, d, n_views)
+ * bytes in the layout of ccz_pair_loss_forward's state -- the gradients are ccz_pair_loss_backward on the same views and that state.
+ * EY takes an optional independent batch (ind_dev: n_views views of width d, n_ind rows; the penalty becomes tr(V V_ind)); its own
+ * gradient is ccz_pair_loss_backward on ind_dev, n_ind and state_ind_dev (NULL: not wanted).  Enqueue-only, no host synchronisation. */
+#define CCZ_MOMENT_EY 0
+#define CCZ_MOMENT_BARLOW 1
+#define CCZ_MOMENT_VICREG 2
+#define CCZ_MOMENT_SDL 3
+CCZ_API int64_t ccz_moment_loss_state_bytes(int dtype, int64_t d, int n_views);
+CCZ_API int ccz_moment_loss_forward(ccz_handle h, int dtype, int kind, const double* params, const ccz_view* z_dev, int n_views, int64_t n,
+                                    const ccz_view* ind_dev, int64_t n_ind, void* loss_dev, double* terms_dev, void* state_dev,
+                                    void* state_ind_dev);
 /* ccz_cca_loss / ccz_pair_loss never read the factorization's pivot flags back (no host synchronisation between the encoders' forward
  * and backward).  If S_aa + eps I was not positive definite the loss written to loss_dev is NaN and the handle keeps a
  * sticky record: *view = 1 + index of the failing view (0: none since the last query), *pivot = the failing pivot;
