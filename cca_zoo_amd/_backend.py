@@ -160,6 +160,14 @@ SIGNATURES = {
     "ccz_cp_iterations": (_int, [_vp, _vp, _i64, _pi64, _pint]),
     "ccz_cp_status": (_int, [_vp, _vp, _pi64, _pint, _pint, _pdbl, _pdbl]),
     "ccz_cp_get_result": (_int, [_vp, _vp, _pdbl, _pdbl, _pi64]),
+    "ccz_rrr_create": (_int, [_vp, _i64, _i64, _dbl, _dbl, _dbl, _i64, _i64, C.POINTER(_vp)]),
+    "ccz_rrr_destroy": (_int, [_vp, _vp]),
+    "ccz_rrr_setup": (_int, [_vp, _vp, _vp, _vp]),
+    "ccz_rrr_iterations": (_int, [_vp, _vp, _i64, _pi64, _pint]),
+    "ccz_rrr_status": (_int, [_vp, _vp, _pi64, _pint, _pint, _pdbl, _pdbl]),
+    "ccz_rrr_get_result": (_int, [_vp, _vp, _pdbl, _vp]),
+    "ccz_rownorm4": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
+    "ccz_moments_block": (_int, [_vp, _vp, _i64, _i64, _int, _i64, _i64, _i64, _i64, _dbl, _vp, _i64]),
 }
 
 

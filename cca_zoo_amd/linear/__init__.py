@@ -1,5 +1,6 @@
 """Closed-form linear CCA family on the MI355X solver core."""
 
+from cca_zoo_amd.linear._ccar3 import CCAR3
 from cca_zoo_amd.linear._gcca import GCCA
 from cca_zoo_amd.linear._grcca import GRCCA
 from cca_zoo_amd.linear._iterative import PLS_ALS, SCCA_ADMM, SCCA_PMD, ParkhomenkoCCA, SCCA_Span
@@ -10,4 +11,4 @@ from cca_zoo_amd.linear._tcca import TCCA
 from cca_zoo_amd.linear.gradient import CCA_EY, MCCA_EY, PLS_EY
 
 __all__ = ["CCA", "GCCA", "GRCCA", "MCCA", "PLS", "PartialCCA", "rCCA", "CCA_EY", "PLS_EY", "MCCA_EY",
-           "PLS_ALS", "SCCA_PMD", "ParkhomenkoCCA", "SCCA_Span", "SCCA_ADMM", "TCCA"]
+           "PLS_ALS", "SCCA_PMD", "ParkhomenkoCCA", "SCCA_Span", "SCCA_ADMM", "TCCA", "CCAR3"]

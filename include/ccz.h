@@ -698,6 +698,59 @@ CCZ_API int ccz_cp_status(ccz_handle h, void* state, int64_t* iters, int* stoppe
  * outputs are skipped.  Synchronises.  (_tcca.py:111-117, _ktcca.py:130-136) */
 CCZ_API int ccz_cp_get_result(ccz_handle h, void* state, double* factors_host, double* trace_host, int64_t* n_trace);
 
+/* ---- Row-sparse reduced-rank regression by ADMM (csrc/rrr.hip): the coefficient step of CCAR3 ------------------------------
+ * With M = (Sxx + (rho + eps) I)^-1 (p x p) and P = Sxy Sy^-1/2 (p x q), both float64 in DEVICE memory, from Z = U = 0:
+ *   B = M (P + rho (Z - U));  Z_old = Z;  Z = B + U, every row scaled by max(0, 1 - (lambda_ / rho) / |row|) (a zero row stays
+ *   zero);  U += B - Z;  the fit stops after the iteration whose max(|Z - B|_F, |Z_old - Z|_F) / sqrt(p) < tol, or after
+ *   max_iter.  The result is Z, which has exact zero rows.
+ * The reference solves with the Cholesky factor every iteration; M is the explicit inverse (condition number at most
+ * (lambda_max + rho) / rho).  Whole iterations run on the device behind a status word, two launches each, in chunks without
+ * a host wait; every sum has a fixed order (two fits give the same bits, whatever the chunk length).
+ * cca_zoo/linear/_ccar3.py:37-80 (_admm_row_sparse_rrr) */
+#define CCZ_RRR_RUNNING 0
+#define CCZ_RRR_TOL 1
+#define CCZ_RRR_MAXITER 2
+
+/* Create a fit state for a p x q coefficient matrix, up to chunk_iters iterations per ccz_rrr_iterations call.  CCZ_EUNSUP:
+ * p + q > 16384, q > 1024.  CCZ_EINVAL: p or q < 1, lambda_ < 0, rho <= 0, tol < 0, a NaN, max_iter or chunk_iters < 1.
+ * (_ccar3.py:37-54) */
+CCZ_API int ccz_rrr_create(ccz_handle h, int64_t p, int64_t q, double lambda_, double rho, double tol, int64_t max_iter,
+                           int64_t chunk_iters, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op.  (_ccar3.py:37-80) */
+CCZ_API int ccz_rrr_destroy(ccz_handle h, void* state);
+
+/* A new fit on M (Minv_dev, p x p) and P (P_dev, p x q): Z = U = 0, the status word.  Both matrices are read by every later
+ * ccz_rrr_iterations of this fit and must stay unchanged until they have run.  Does not wait for the device.
+ * (_ccar3.py:48-54) */
+CCZ_API int ccz_rrr_setup(ccz_handle h, void* state, const double* Minv_dev, const double* P_dev);
+
+/* Enqueue n_iters (<= chunk_iters) iterations.  Returns without waiting for the device; the only host wait is for the chunk
+ * that used the same status slot two calls earlier, whose state is returned in iters_known / stopped_known (-1 / 0 when
+ * there is none yet).  Iterations after the stop are no-ops.  (_ccar3.py:55-70) */
+CCZ_API int ccz_rrr_iterations(ccz_handle h, void* state, int64_t n_iters, int64_t* iters_known, int* stopped_known);
+
+/* Iterations done, whether the fit has stopped and why (CCZ_RRR_*), and the two residuals of the last iteration.
+ * Synchronises.  (_ccar3.py:67-70) */
+CCZ_API int ccz_rrr_status(ccz_handle h, void* state, int64_t* iters, int* stopped, int* reason, double* primal, double* dual);
+
+/* Z (p x q row-major) to the host and / or to another device buffer; NULL outputs are skipped.  Synchronises when Z_host is
+ * given.  (_ccar3.py:71-80: Z, not B, is returned) */
+CCZ_API int ccz_rrr_get_result(ccz_handle h, void* state, double* Z_host, double* Z_dev);
+
+/* *out_host = sum over the rows of (sum_j (y_ij - mean_j)^2)^2 of one view of DEVICE rows: rows read in `dtype`, arithmetic in
+ * float64, per-workgroup partials folded in index order (two calls give the same bits).  mean_dev: float64, NULL for none.
+ * The one quantity of sklearn's Ledoit-Wolf shrinkage that the second moments do not hold (beta_ = sum (X^2)'(X^2)).
+ * Synchronises.  cca_zoo/linear/_ccar3.py:258 (LedoitWolf().fit(Y)) */
+CCZ_API int ccz_rownorm4(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const double* mean_dev, double* out_host);
+
+/* out (rows x cols, row stride ldo) = (G[r0 + i][c0 + j] - (center ? s[r0 + i] s[c0 + j] / n_rows : 0)) / n_rows, plus `shift`
+ * on the diagonal (a diagonal block only), from the moments [G | s] of ccz_moments (upper triangle authoritative): X'X / n,
+ * X'Y / n and Y'Y / n of the centred views as dense matrices, without a pass over the data.
+ * cca_zoo/linear/_ccar3.py:48-50, 273-274 */
+CCZ_API int ccz_moments_block(ccz_handle h, const double* moments_dev, int64_t D, int64_t n_rows, int center, int64_t r0,
+                              int64_t rows, int64_t c0, int64_t cols, double shift, double* out_dev, int64_t ldo);
+
 #ifdef __cplusplus
 }
 #endif
