@@ -137,6 +137,9 @@ SIGNATURES = {
     "ccz_als_destroy": (_int, [_vp, _vp]),
     "ccz_als_set_init": (_int, [_vp, _vp, _pdbl]),
     "ccz_als_admm_setup": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _dbl]),
+    "ccz_als_enet_setup": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _pdbl, _pdbl, _pint, _int, _int]),
+    "ccz_als_enet_solve": (_int, [_vp, _vp, _int, _pdbl, _pdbl, _pdbl, _dbl, _i64]),
+    "ccz_als_enet_status": (_int, [_vp, _vp, _pi64, _pi64]),
     "ccz_als_sweeps": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pint]),
     "ccz_als_status": (_int, [_vp, _vp, _pint, _pint, _pi64, _pdbl]),
     "ccz_als_colmeans": (_int, [_vp, _int, C.POINTER(View), _i64, _vp]),

@@ -42,6 +42,24 @@
 // z_i and w_i coincide between iterations (the reference starts from z = w and ends every iteration with w = z), so w_i - z_i
 // in its gradient is exactly zero and z has no buffer of its own; eta_i counts as zero at a dimension's first iteration.
 //
+// SCCA_IPLS and ElasticCCA (cca_zoo/linear/_iterative.py:522-623, :730-831, :938-982) regress the target on the deflated view
+// with an elastic-net penalty.  The reference's solver visits the coordinates in random order; whenever the minimiser is
+// unique the outer update does not depend on that order, so here the solve is cyclic coordinate descent on the Gram matrix
+// G_i of the deflated view (formed once on the p side, deflated in place by G_i -= a a', a = (X_i - mu_i)' q~_d).  Its length
+// depends on the data, so the sweep is cut into UNITS of a fixed kernel sequence and the status word carries where the
+// sweep stands (view, phase); every kernel of a unit returns at once unless the status names its view and phase:
+//   per view i:
+//     phase 0  k_als_enet_prologue (t, t't, t~), k_als_xt, k_als_enet_rinit (q = X_d' t into raw; r = q - G c from the
+//              view's previous coefficients c, c = 0 at a dimension's first solve), then phase 1
+//     phase 1  up to ENET_CD_CHUNK (16) x [ per block of 64 coordinates: k_als_enet_block (one wave: the 64 sequential steps on the
+//              diagonal tile in LDS), k_als_enet_update (r -= G[:, block] delta for the rest of r; returns at once when
+//              delta = 0);  k_als_enet_check (scikit-learn's stop rule in Gram form; phase 2 when it holds) ]
+//     phase 2  k_als_score of c, k_als_enet_std (SCCA_IPLS: the population standard deviation of the corrected score),
+//              k_als_enet_apply (w_i = c or c / std, partial |w_i - w_i_old|^2), then phase 0 of view i + 1
+//   k_als_finish (once every view is done), k_als_advance; at the end of a dimension k_als_admm_xtq / _afold and
+//   k_als_enet_deflate bring every G_i up to date
+// A solve that needs more sweeps than its unit holds goes on in the next unit: all other kernels of the units between pass.
+//
 // Precision: x - mu is rounded in the views' precision (the reference's own `v - v.mean(0)`), then widened; every product
 // and sum is fp64 (the reference's fp64 initial w promotes every product, cca_zoo/linear/_iterative.py:88-89).
 #include <algorithm>
@@ -74,7 +92,17 @@ constexpr int ALS_GT = 64;           // k_als_gram: tile edge
 constexpr int ALS_GKC = 32;          // k_als_gram: contraction indices per LDS stage
 constexpr int ALS_GLD = ALS_GKC + 1; // LDS row stride (doubles)
 
-enum { RULE_NORMALISE = 0, RULE_SOFT_FIXED = 1, RULE_SOFT_L1 = 2, RULE_TOP_S = 3, RULE_ADMM = 4 };
+// Elastic-net solve.  ENET_BW coordinates per block: one wavefront, so the 64 dependent steps of a block run without a
+// workgroup barrier (a shuffle hands delta_j to the other lanes) and the diagonal tile, 64 x 64 doubles = 32 KiB, fits the
+// LDS one workgroup gets by default; a wider block would pay a barrier per coordinate, which costs more than the launch
+// it saves.
+constexpr int ENET_BW = 64;
+constexpr int ENET_MAXP = ALS_ADMM_MAXSIDE;   // widest view: G_i is p_i x p_i
+constexpr int ENET_CAP = 1000;       // CD sweeps per solve (scikit-learn's max_iter)
+constexpr int ENET_CD_CHUNK = 16;    // CD sweeps enqueued per view and unit, at most ...
+constexpr int ENET_CD_BLOCKS = 64;   // ... and as many as keep it near this many block steps (at least one sweep)
+
+enum { RULE_NORMALISE = 0, RULE_SOFT_FIXED = 1, RULE_SOFT_L1 = 2, RULE_TOP_S = 3, RULE_ADMM = 4, RULE_ENET = 5 };
 
 struct AlsStatus {
   double last_delta[ALS_MAXK];     // delta of the last sweep of each dimension
@@ -84,6 +112,11 @@ struct AlsStatus {
   int sweep;                       // sweeps done in the current dimension
   int stopped;
   int advance;                     // the last finish ended a dimension (read by k_als_advance)
+  // elastic net only (zero otherwise)
+  long long inner[ALS_MAXK];       // CD sweeps per dimension
+  int view, phase;                 // where the current sweep stands: the view being updated and its phase (0, 1, 2)
+  int isweep;                      // CD sweeps done in the current solve
+  int capped;                      // solves that ended on ENET_CAP without meeting the stop rule
 };
 
 struct AlsViews {
@@ -127,6 +160,12 @@ struct AlsBuf {
   double* tt2;      // SCCA_ADMM, n: the view's own corrected score while the prologue forms s_i - t_i
   double* lip;      // SCCA_ADMM, M: L_i of the current dimension
   double* gpart;    // SCCA_ADMM, ALS_LG: partial sums of squares of a deflated Gram
+  double* coef;     // elastic net, ptot: the coefficients of every view's last solve
+  double* res;      // elastic net, pmax: r = q - G c of the running solve
+  double* dl;       // elastic net, ENET_BW: the block's coordinate changes
+  double* bstat;    // elastic net, nbmax x 2: per block max |delta|, max |c|
+  double* scal;     // elastic net, M x 4: t't, the gap, the score's standard deviation, the sweeps of the last solve
+  int enet;         // elastic net: the status carries (view, phase)
   int n, M, k, csmax, nchunk, rc;
   int64_t ptot, pmax;
 };
@@ -139,12 +178,14 @@ __device__ __forceinline__ double als_soft(double x, double t) {
 // ---- score: column-split partial sums of s = (X - mu) w ----------------------------------------------------------------
 // grid (ceil(n / 4), cs), 256 threads: 4 rows x one column range per workgroup, 4 consecutive columns per thread and step.
 // first_only: the scores of a dimension's initial vectors -- runs only while no sweep of the dimension is done.
+// gate >= 0 (elastic net): runs only in phase 2 of that view.
 template <typename T>
 __global__ void __launch_bounds__(256) k_als_score(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
                                                   const double* __restrict__ w, double* __restrict__ spart, int first_only,
-                                                  const AlsStatus* st) {
+                                                  int gate, const AlsStatus* st) {
   if (fit_stopped(st)) return;
-  if (first_only && st->sweep != 0) return;
+  if (first_only && (st->sweep != 0 || st->view != 0 || st->phase != 0)) return;
+  if (gate >= 0 && (st->view != gate || st->phase != 2)) return;
   __shared__ double sh[4];
   const int r0 = blockIdx.x * ALS_SROWS;
   int64_t c0, c1;
@@ -217,7 +258,7 @@ __device__ void als_target(const AlsBuf& B, const AlsViews& vw, int i, int d, do
   const int n = B.n;
   bool first = true;
   for (int j = 0; j < B.M; ++j) {
-    if (j == i) continue;
+    if (j == i) continue;                // i = -1 (ElasticCCA): every view
     als_corrected_score(B, vw, j, d, B.tt, !first, coef, sh);
     first = false;
   }
@@ -275,7 +316,7 @@ __global__ void __launch_bounds__(ALS_PT) k_als_admm_prologue(AlsBuf B, AlsViews
 
 // once per sweep: delta, the stop test, the end of a dimension (cca_zoo/linear/_iterative.py:109-117, :91-93, _linalg.py:108-116)
 __global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, double tol, int max_iter, AlsStatus* st) {
-  if (fit_stopped(st)) {
+  if (fit_stopped(st) || (B.enet && st->view != B.M)) {     // elastic net: a view's solve is still running
     if (threadIdx.x == 0) st->advance = 0;
     return;
   }
@@ -298,6 +339,8 @@ __global__ void __launch_bounds__(ALS_PT) k_als_finish(AlsBuf B, AlsViews vw, do
     end_dim = (delta < tol || sweep >= max_iter) ? 1 : 0;
     st->sweep = end_dim ? 0 : sweep;
     st->advance = end_dim;
+    st->view = 0;
+    st->phase = 0;
   }
   __syncthreads();
   if (!end_dim) return;
@@ -332,8 +375,9 @@ __global__ void __launch_bounds__(256) k_als_advance(AlsBuf B, const AlsStatus* 
 // grid (ceil(p / 1024), nchunk), 256 threads: thread t owns columns 1024 bx + 4 t .. + 3 over rows [rc by, rc (by + 1))
 template <typename T>
 __global__ void __launch_bounds__(256) k_als_xt(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n, int rc,
-                                               const double* __restrict__ tt, double* __restrict__ xpart, const AlsStatus* st) {
+                                               const double* __restrict__ tt, double* __restrict__ xpart, int gate, const AlsStatus* st) {
   if (fit_stopped(st)) return;
+  if (gate >= 0 && (st->view != gate || st->phase != 0)) return;     // elastic net: phase 0 of that view only
   const int64_t f0 = int64_t(blockIdx.x) * ALS_STRIP + 4 * threadIdx.x;
   if (f0 >= p) return;
   const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
@@ -640,6 +684,10 @@ __global__ void __launch_bounds__(256) k_als_admm_apply(const double* __restrict
 // the kernels below bring K Q / A up to date with the newest column of Q and sum the squares of the deflated entries.  They
 // return at once on every other iteration.
 __device__ __forceinline__ bool admm_not_first(const AlsStatus* st) { return fit_stopped(st) || st->sweep != 0; }
+// elastic net: the newest column of A is taken right after the finish that ended a dimension
+__device__ __forceinline__ bool acol_off(const AlsStatus* st, int enet) {
+  return enet ? (fit_stopped(st) || !st->advance) : (admm_not_first(st) || st->dim == 0);
+}
 
 // n side: column d - 1 of K Q, one wave per row of K
 __global__ void __launch_bounds__(256) k_als_admm_kq(const double* __restrict__ K, int n, const double* __restrict__ Q,
@@ -681,8 +729,8 @@ __global__ void __launch_bounds__(ALS_PT) k_als_admm_h(int n, const double* __re
 template <typename T>
 __global__ void __launch_bounds__(256) k_als_admm_xtq(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
                                                      int rc, const double* __restrict__ Q, double* __restrict__ xpart,
-                                                     const AlsStatus* st) {
-  if (admm_not_first(st) || st->dim == 0) return;
+                                                     int enet, const AlsStatus* st) {
+  if (acol_off(st, enet)) return;
   const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (f >= p) return;
   const double* q = Q + int64_t(st->dim - 1) * n;
@@ -695,8 +743,8 @@ __global__ void __launch_bounds__(256) k_als_admm_xtq(const T* __restrict__ X, c
 
 // p side: column d - 1 of A = the chunk partials summed in chunk order
 __global__ void __launch_bounds__(256) k_als_admm_afold(const double* __restrict__ xpart, int nchunk, int64_t p,
-                                                       double* __restrict__ A, const AlsStatus* st) {
-  if (admm_not_first(st) || st->dim == 0) return;
+                                                       double* __restrict__ A, int enet, const AlsStatus* st) {
+  if (acol_off(st, enet)) return;
   const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (f >= p) return;
   double v = 0.0;
@@ -818,6 +866,220 @@ __global__ void __launch_bounds__(256) k_als_gram(const T* __restrict__ X, const
   }
 }
 
+// ---- SCCA_IPLS / ElasticCCA: the elastic-net solve in Gram form -------------------------------------------------------------
+// argmin_c 1/2 |X_d c - t|^2 + a |c|_1 + b/2 |c|^2 (a = n alpha l1, b = n alpha (1 - l1); the reference's Ridge: a = 0,
+// b = alpha) from G = X_d' X_d, q = X_d' t and t't alone.  r = q - G c is carried along.
+__device__ __forceinline__ bool enet_off(const AlsStatus* st, int view, int phase) {
+  return fit_stopped(st) || st->view != view || st->phase != phase;
+}
+
+// t of view i (every view's score when all != 0, cca_zoo/linear/_iterative.py:824-828), t't into scal[0], t~ into B.tt
+__global__ void __launch_bounds__(ALS_PT) k_als_enet_prologue(AlsBuf B, AlsViews vw, int i, int all, const AlsStatus* st) {
+  if (enet_off(st, i, 0)) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  const int d = st->dim;
+  als_target(B, vw, all ? -1 : i, d, coef, sh);
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < B.n; r += ALS_PT) acc += B.tt[r] * B.tt[r];      // own rows
+  const double tn = block_sum<ALS_PT / 64>(acc, sh);
+  if (threadIdx.x == 0) B.scal[4 * i] = tn;
+  als_correct_target(B, i, d, coef, sh);
+}
+
+// q = the chunk partials of X' t~ summed in chunk order, into raw; r = q - G c with c the view's previous coefficients, or
+// c = 0 and r = q at the first solve of a dimension (the reference builds fresh regressors per dimension).  One wave per row.
+__global__ void __launch_bounds__(256) k_als_enet_rinit(const double* __restrict__ xpart, int nchunk, int64_t p,
+                                                       const double* __restrict__ G, double* __restrict__ c,
+                                                       double* __restrict__ raw, double* __restrict__ res, int view,
+                                                       const AlsStatus* st) {
+  if (enet_off(st, view, 0)) return;
+  const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (row >= p) return;
+  const int lane = threadIdx.x & 63;
+  double q = 0.0;
+  for (int ch = 0; ch < nchunk; ++ch) q += xpart[int64_t(ch) * p + row];
+  if (st->sweep == 0) {                  // no thread reads c in this branch
+    if (lane == 0) { raw[row] = q; res[row] = q; c[row] = 0.0; }
+    return;
+  }
+  double s = 0.0;
+  for (int64_t f = lane; f < p; f += 64) s += G[row * p + f] * c[f];
+  s = wave_sum(s);
+  if (lane == 0) { raw[row] = q; res[row] = q - s; }
+}
+
+// (view, phase) -> (to_view, to_phase), one thread; a solve starts with its sweep count at zero
+__global__ void k_als_enet_step(AlsStatus* st, int view, int phase, int to_view, int to_phase) {
+  if (enet_off(st, view, phase)) return;
+  st->view = to_view;
+  st->phase = to_phase;
+  if (to_phase == 1) st->isweep = 0;
+}
+
+// The ENET_BW sequential coordinate steps of block `blk`, one wave: lane l owns coordinate j0 + l, the diagonal tile of G
+// lies in LDS by rows (G is symmetric: row j is column j, read without bank conflicts).  Step j:
+//   z = r_j + G_jj c_j;  c_j' = sign(z) max(|z| - a, 0) / (G_jj + b);  r -= (c_j' - c_j) G[:, j]  on the block's slice of r
+// (G_jj = 0: the coordinate is skipped, as scikit-learn skips zero columns).  The block's changes go to dl for
+// k_als_enet_update, max |delta| and max |c| to bstat.
+__global__ void __launch_bounds__(ENET_BW) k_als_enet_block(const double* __restrict__ G, int64_t p, double* __restrict__ res,
+                                                           double* __restrict__ c, double a, double b, int blk,
+                                                           double* __restrict__ dl, double* __restrict__ bstat, int view,
+                                                           const AlsStatus* st) {
+  if (enet_off(st, view, 1)) return;
+  __shared__ double T[ENET_BW * ENET_BW];
+  const int lane = threadIdx.x;
+  const int64_t j0 = int64_t(blk) * ENET_BW;
+  const int bw = int(min(int64_t(ENET_BW), p - j0));
+  const bool live = lane < bw;
+  for (int j = 0; j < ENET_BW; ++j) T[j * ENET_BW + lane] = (j < bw && live) ? G[(j0 + j) * p + j0 + lane] : 0.0;
+  __syncthreads();
+  double rl = live ? res[j0 + lane] : 0.0, cl = live ? c[j0 + lane] : 0.0, dmine = 0.0;
+  const double g = T[lane * ENET_BW + lane];
+  for (int j = 0; j < bw; ++j) {
+    const double z = rl + g * cl;
+    const double nw = g == 0.0 ? cl : als_soft(z, a) / (g + b);
+    const double d = __shfl(nw - cl, j, 64);
+    if (lane == j) { cl = nw; dmine = d; }
+    if (d != 0.0) rl -= d * T[j * ENET_BW + lane];      // uniform over the wave
+  }
+  if (live) { res[j0 + lane] = rl; c[j0 + lane] = cl; }
+  dl[lane] = dmine;
+  const double dmax = wave_max(fabs(dmine)), cmax = wave_max(fabs(cl));
+  if (lane == 0) { bstat[2 * blk] = dmax; bstat[2 * blk + 1] = cmax; }
+}
+
+// r_f -= sum_j delta_j G[j0 + j][f] for every f outside the block, j in order (the same sums as one coordinate at a time);
+// returns at once when the block changed nothing.  One thread per f, 64 per workgroup: p / 64 workgroups fill the device
+// at the widths where this kernel's time matters.
+__global__ void __launch_bounds__(ENET_BW) k_als_enet_update(const double* __restrict__ G, int64_t p, double* __restrict__ res,
+                                                            const double* __restrict__ dl, const double* __restrict__ bstat,
+                                                            int blk, int view, const AlsStatus* st) {
+  if (enet_off(st, view, 1)) return;
+  if (bstat[2 * blk] == 0.0) return;
+  __shared__ double dsh[ENET_BW];
+  dsh[threadIdx.x] = dl[threadIdx.x];
+  __syncthreads();
+  const int64_t j0 = int64_t(blk) * ENET_BW, f = int64_t(blockIdx.x) * ENET_BW + threadIdx.x;
+  const int bw = int(min(int64_t(ENET_BW), p - j0));
+  if (f >= p || (f >= j0 && f < j0 + ENET_BW)) return;
+  double acc = res[f];
+  for (int j = 0; j < bw; ++j) {
+    const double d = dsh[j];
+    if (d != 0.0) acc -= d * G[(j0 + j) * p + f];
+  }
+  res[f] = acc;
+}
+
+// After a CD sweep: scikit-learn's stop rule.  With max |delta| / max |c| < tol (or max |c| = 0, or at the cap) the duality
+// gap from R'R = t't - c'q - c'r, R't = t't - c'q, X'R = r; the solve ends (phase 2) when gap < tol t't or at the cap.
+// ridge: ends on the coordinate change alone.
+__global__ void __launch_bounds__(ALS_PT) k_als_enet_check(int64_t p, const double* __restrict__ q, const double* __restrict__ res,
+                                                          const double* __restrict__ c, const double* __restrict__ bstat, int nb,
+                                                          double a, double b, int ridge, double tol, double* __restrict__ scal,
+                                                          int view, AlsStatus* st) {
+  if (enet_off(st, view, 1)) return;
+  __shared__ double sh[ALS_PT / 64];
+  const int t = threadIdx.x;
+  const double dmax = block_max<ALS_PT / 64>(t < nb ? bstat[2 * t] : 0.0, sh);
+  const double cmax = block_max<ALS_PT / 64>(t < nb ? bstat[2 * t + 1] : 0.0, sh);
+  const int isweep = st->isweep + 1;
+  const bool crit = cmax == 0.0 || dmax / cmax < tol, cap = isweep >= ENET_CAP;
+  bool done = ridge ? (crit || cap) : false, met = crit;
+  double gap = 0.0;
+  if (!ridge && (crit || cap)) {         // uniform over the workgroup
+    double cq = 0.0, cr = 0.0, l1 = 0.0, cc = 0.0, dual = 0.0;
+    for (int64_t f = t; f < p; f += ALS_PT) {
+      const double v = c[f], rf = res[f];
+      cq += v * q[f];
+      cr += v * rf;
+      l1 += fabs(v);
+      cc += v * v;
+      dual = fmax(dual, fabs(rf - b * v));
+    }
+    cq = block_sum<ALS_PT / 64>(cq, sh);
+    cr = block_sum<ALS_PT / 64>(cr, sh);
+    l1 = block_sum<ALS_PT / 64>(l1, sh);
+    cc = block_sum<ALS_PT / 64>(cc, sh);
+    dual = block_max<ALS_PT / 64>(dual, sh);
+    const double tn = scal[0], rr = tn - cq - cr, rt = tn - cq;
+    double cst = 1.0;
+    if (dual > a) {
+      cst = a / dual;
+      gap = 0.5 * (rr + rr * cst * cst);
+    } else {
+      gap = rr;
+    }
+    gap += a * l1 - cst * rt + 0.5 * b * (1.0 + cst * cst) * cc;
+    met = gap < tol * tn;
+    done = met || cap;
+  }
+  __syncthreads();                       // every thread has read the status
+  if (t == 0) {
+    st->isweep = isweep;
+    st->inner[st->dim] += 1;
+    scal[3] = double(isweep);
+    if (!ridge && (crit || cap)) scal[1] = gap;
+    if (done) {
+      st->phase = 2;
+      if (!met) st->capped += 1;
+    }
+  }
+}
+
+// SCCA_IPLS: the population standard deviation of the corrected score of the coefficients (numpy.std: the mean subtracted,
+// ddof 0; cca_zoo/linear/_iterative.py:619-622) into scal[2]; when it exceeds 1e-12 the score partials are divided by it,
+// so that they are those of w_i = c / std
+__global__ void __launch_bounds__(ALS_PT) k_als_enet_std(AlsBuf B, AlsViews vw, int i, const AlsStatus* st) {
+  if (enet_off(st, i, 2)) return;
+  __shared__ double sh[ALS_PT / 64];
+  __shared__ double coef[ALS_MAXK];
+  const int n = B.n;
+  als_corrected_score(B, vw, i, st->dim, B.tt2, false, coef, sh);
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < n; r += ALS_PT) acc += B.tt2[r];
+  const double mean = block_sum<ALS_PT / 64>(acc, sh) / double(n);
+  acc = 0.0;
+  for (int r = threadIdx.x; r < n; r += ALS_PT) acc += (B.tt2[r] - mean) * (B.tt2[r] - mean);
+  const double sd = sqrt(block_sum<ALS_PT / 64>(acc, sh) / double(n));
+  if (threadIdx.x == 0) B.scal[4 * i + 2] = sd;
+  if (!(sd > 1e-12)) return;
+  double* sp = B.spart + int64_t(i) * B.csmax * n;
+  for (int cidx = 0; cidx < vw.cs[i]; ++cidx)
+    for (int r = threadIdx.x; r < n; r += ALS_PT) sp[int64_t(cidx) * n + r] /= sd;
+}
+
+// w = c (ElasticCCA) or c / std when std > 1e-12 (SCCA_IPLS); per-workgroup partial |w - w_old|^2
+__global__ void __launch_bounds__(256) k_als_enet_apply(const double* __restrict__ c, int64_t p, int post, const double* __restrict__ scal,
+                                                       double* __restrict__ w, double* __restrict__ dpart, int view,
+                                                       const AlsStatus* st) {
+  if (enet_off(st, view, 2)) return;
+  __shared__ double sh[4];
+  const double sd = post ? scal[2] : 1.0;
+  const bool divide = post && sd > 1e-12;
+  double dd = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < p; f += int64_t(gridDim.x) * 256) {
+    const double u = divide ? c[f] / sd : c[f];
+    const double diff = u - w[f];
+    dd += diff * diff;
+    w[f] = u;
+  }
+  dd = block_sum<4>(dd, sh);
+  if (threadIdx.x == 0) dpart[blockIdx.x] = dd;
+}
+
+// at the end of a dimension: G -= a a' with a the newest column of A = (X - mu)' Q (exact: the Q columns are orthonormal; a
+// view that was not deflated has a zero column).  grid (ceil(p / 256), rows strided by gridDim.y)
+__global__ void __launch_bounds__(256) k_als_enet_deflate(double* __restrict__ G, int64_t p, const double* __restrict__ A,
+                                                         const AlsStatus* st) {
+  if (acol_off(st, 1)) return;
+  const double* a = A + int64_t(st->dim - 1) * p;
+  const int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (f >= p) return;
+  const double af = a[f];
+  for (int64_t r = blockIdx.y; r < p; r += gridDim.y) G[r * p + f] -= a[r] * af;
+}
+
 // ---- column means as the reference forms them ----------------------------------------------------------------------------
 // NumPy's v.mean(axis=0) of a row-major array adds the rows in order in the array's own precision and divides by n
 // (cca_zoo/_base.py:97-99); one thread per column does exactly that, so the means of device rows equal the reference's bit for bit.
@@ -843,6 +1105,11 @@ struct AlsState : FitState<AlsStatus> {
   bool admm_ready = false;
   AdmmView admm[ALS_MAXV] = {};
   int last_cs[ALS_MAXV] = {};
+  bool enet_used = false;          // units have run since the setup: G_i is deflated
+  bool enet_ready = false;         // elastic net: what ccz_als_enet_setup left per view (admm[i].G = G_i, .U = A_i)
+  double ea[ALS_MAXV] = {}, eb[ALS_MAXV] = {};
+  int eridge[ALS_MAXV] = {};
+  int enet_all = 0, enet_post = 0;
 };
 
 AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const* means) {
@@ -862,22 +1129,24 @@ AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const*
   return vw;
 }
 
-void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
+// vec: the p-vectors scored (B.w unless given); gate: see k_als_score
+void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only, const double* vec = nullptr, int gate = -1) {
   const dim3 grid(unsigned((S.n + ALS_SROWS - 1) / ALS_SROWS), unsigned(vw.cs[i]));
   by_dtype(S.dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL((k_als_score<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                       vw.ld[i], vw.p[i], int(S.n), S.B.w + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.drv.dev);
+                       vw.ld[i], vw.p[i], int(S.n), (vec ? vec : S.B.w) + vw.off[i], S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only,
+                       gate, S.drv.dev);
   });
   CCZ_LAUNCH_CHECK();
 }
 
-void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int gate = -1) {
   const dim3 grid(unsigned((vw.p[i] + ALS_STRIP - 1) / ALS_STRIP), unsigned(S.B.nchunk));
   by_dtype(S.dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL((k_als_xt<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]), static_cast<const T*>(vw.mu[i]),
-                       vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, S.drv.dev);
+                       vw.ld[i], vw.p[i], int(S.n), S.B.rc, S.B.tt, S.B.xpart, gate, S.drv.dev);
   });
   CCZ_LAUNCH_CHECK();
 }
@@ -911,6 +1180,22 @@ void launch_prologue(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   CCZ_LAUNCH_CHECK();
 }
 
+// p side: the newest column of A_i = (X_i - mu_i)' Q_i (enet: gated on the end of a dimension, else on a dimension's first
+// iteration)
+void launch_acol(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int enet) {
+  const AlsBuf& B = S.B;
+  const double* Q = B.Q + int64_t(i) * B.k * S.n;
+  const dim3 grid(unsigned((vw.p[i] + 255) / 256), unsigned(B.nchunk));
+  by_dtype(S.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_admm_xtq<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]),
+                       static_cast<const T*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, enet, S.drv.dev);
+  });
+  CCZ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_als_admm_afold, dim3(grid.x), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], S.admm[i].U, enet, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+}
+
 // SCCA_ADMM: L_i at the first iteration of a dimension (the four kernels return at once otherwise)
 void launch_admm_lipschitz(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const AlsBuf& B = S.B;
@@ -922,15 +1207,7 @@ void launch_admm_lipschitz(ccz_ctx* c, const AlsState& S, const AlsViews& vw, in
     hipLaunchKernelGGL(k_als_admm_h, dim3(1), dim3(ALS_PT), 0, stream(c), int(S.n), Q, a.KQ, a.U, S.drv.dev);
     CCZ_LAUNCH_CHECK();
   } else if (S.k > 1) {
-    const dim3 grid(unsigned((vw.p[i] + 255) / 256), unsigned(B.nchunk));
-    by_dtype(S.dtype, [&](auto t) {
-      using T = decltype(t);
-      hipLaunchKernelGGL((k_als_admm_xtq<T>), grid, dim3(256), 0, stream(c), static_cast<const T*>(vw.X[i]),
-                         static_cast<const T*>(vw.mu[i]), vw.ld[i], vw.p[i], int(S.n), B.rc, Q, B.xpart, S.drv.dev);
-    });
-    CCZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_als_admm_afold, dim3(grid.x), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], a.U, S.drv.dev);
-    CCZ_LAUNCH_CHECK();
+    launch_acol(c, S, vw, i, 0);
   }
   const int lg = int(std::min<int64_t>(ALS_LG, a.side));
   hipLaunchKernelGGL(k_als_admm_gnorm, dim3(lg), dim3(256), 0, stream(c), a.G, a.side, a.U, Q, a.nside, B.gpart, S.drv.dev);
@@ -971,8 +1248,77 @@ void enqueue_admm_iteration(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
   finish_sweep(c, S, vw);
 }
 
+// elastic net: `sweeps` CD sweeps of view i's running solve (every kernel passes unless the status says view i, phase 1)
+void enqueue_cd(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int64_t sweeps) {
+  const AlsBuf& B = S.B;
+  const int64_t p = vw.p[i];
+  const int nb = int((p + ENET_BW - 1) / ENET_BW);
+  const double* G = S.admm[i].G;
+  double* coef = B.coef + vw.off[i];
+  for (int64_t s = 0; s < sweeps; ++s) {
+    for (int b = 0; b < nb; ++b) {
+      hipLaunchKernelGGL(k_als_enet_block, dim3(1), dim3(ENET_BW), 0, stream(c), G, p, B.res, coef, S.ea[i], S.eb[i], b, B.dl, B.bstat, i,
+                         S.drv.dev);
+      CCZ_LAUNCH_CHECK();
+      if (nb == 1) continue;             // no r outside the block
+      hipLaunchKernelGGL(k_als_enet_update, dim3(nb), dim3(ENET_BW), 0, stream(c), G, p, B.res, B.dl, B.bstat, b, i, S.drv.dev);
+      CCZ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_als_enet_check, dim3(1), dim3(ALS_PT), 0, stream(c), p, B.raw + vw.off[i], B.res, coef, B.bstat, nb, S.ea[i], S.eb[i],
+                       S.eridge[i], S.tol, B.scal + 4 * i, i, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+}
+
+void launch_enet_step(ccz_ctx* c, const AlsState& S, int view, int phase, int to_view, int to_phase) {
+  hipLaunchKernelGGL(k_als_enet_step, dim3(1), dim3(1), 0, stream(c), S.drv.dev, view, phase, to_view, to_phase);
+  CCZ_LAUNCH_CHECK();
+}
+
+// r = q - G c of view i from the chunk partials in xpart, then phase 1
+void launch_enet_rinit(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const AlsBuf& B = S.B;
+  hipLaunchKernelGGL(k_als_enet_rinit, dim3(unsigned((vw.p[i] + 3) / 4)), dim3(256), 0, stream(c), B.xpart, B.nchunk, vw.p[i], S.admm[i].G,
+                     B.coef + vw.off[i], B.raw + vw.off[i], B.res, i, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+  launch_enet_step(c, S, i, 0, i, 1);
+}
+
+// one unit of an elastic-net fit (see the head of the file)
+void enqueue_enet_unit(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
+  const AlsBuf& B = S.B;
+  for (int i = 0; i < S.M; ++i) launch_score(c, S, vw, i, 1);
+  for (int i = 0; i < S.M; ++i) {
+    hipLaunchKernelGGL(k_als_enet_prologue, dim3(1), dim3(ALS_PT), 0, stream(c), B, vw, i, S.enet_all, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    launch_xt(c, S, vw, i, i);
+    launch_enet_rinit(c, S, vw, i);
+    const int64_t nb = (vw.p[i] + ENET_BW - 1) / ENET_BW;
+    enqueue_cd(c, S, vw, i, std::max<int64_t>(1, std::min<int64_t>(ENET_CD_CHUNK, ENET_CD_BLOCKS / nb)));
+    launch_score(c, S, vw, i, 0, B.coef, i);
+    if (S.enet_post) {
+      hipLaunchKernelGGL(k_als_enet_std, dim3(1), dim3(ALS_PT), 0, stream(c), B, vw, i, S.drv.dev);
+      CCZ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_als_enet_apply, dim3(vw.ng[i]), dim3(256), 0, stream(c), B.coef + vw.off[i], vw.p[i], S.enet_post, B.scal + 4 * i,
+                       B.w + vw.off[i], B.dpart + size_t(i) * ALS_MAXG, i, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+    launch_enet_step(c, S, i, 2, i + 1, 0);
+  }
+  finish_sweep(c, S, vw);
+  if (S.k == 1) return;
+  for (int i = 0; i < S.M; ++i) {
+    launch_acol(c, S, vw, i, 1);
+    const int64_t p = vw.p[i];
+    hipLaunchKernelGGL(k_als_enet_deflate, dim3(unsigned((p + 255) / 256), unsigned(std::min<int64_t>(p, 256))), dim3(256), 0, stream(c),
+                       S.admm[i].G, p, S.admm[i].U, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+}
+
 void enqueue_sweep(ccz_ctx* c, const AlsState& S, const AlsViews& vw) {
   if (S.rule == RULE_ADMM) return enqueue_admm_iteration(c, S, vw);
+  if (S.rule == RULE_ENET) return enqueue_enet_unit(c, S, vw);
   for (int i = 0; i < S.M; ++i) launch_score(c, S, vw, i, 1);
   for (int i = 0; i < S.M; ++i) {
     launch_prologue(c, S, vw, i);
@@ -990,7 +1336,7 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
   if (k < 1 || k > ALS_MAXK) fail(CCZ_EUNSUP, "als: 1 to %d latent dimensions are supported, got %lld", ALS_MAXK, (long long)k);
   if (!p || n < 1 || n > (int64_t(1) << 30) || max_iter < 1 || max_iter > (int64_t(1) << 30) || chunk < 1 || !(tol >= 0.0))
     fail(CCZ_EINVAL, "als: bad argument");
-  if (rule < RULE_NORMALISE || rule > RULE_ADMM) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
+  if (rule < RULE_NORMALISE || rule > RULE_ENET) fail(CCZ_EINVAL, "als: unknown rule %d", rule);
   if (rule != RULE_NORMALISE && !par) fail(CCZ_EINVAL, "als: the rule needs one parameter per view");
   check_no_empty_view("als", M, p);
   return new_state<AlsState>(c, [&](AlsState& S) {
@@ -1003,6 +1349,8 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
       if (rule == RULE_ADMM && std::min(n, p[i]) > ALS_ADMM_MAXSIDE)
         fail(CCZ_EUNSUP, "als: ADMM keeps a min(n, p) x min(n, p) Gram per view; view %d has min(n, p) = %lld > %d", i,
              (long long)std::min(n, p[i]), ALS_ADMM_MAXSIDE);
+      if (rule == RULE_ENET && p[i] > ENET_MAXP)
+        fail(CCZ_EUNSUP, "als: the elastic-net models keep a p x p Gram per view; view %d has p = %lld > %d", i, (long long)p[i], ENET_MAXP);
       const double q = par ? par[i] : 0.0;
       if (rule == RULE_TOP_S && !(q >= 1.0)) fail(CCZ_EINVAL, "als: top-s needs s >= 1 (view %d)", i);
       if (rule != RULE_NORMALISE && !(q == q)) fail(CCZ_EINVAL, "als: the parameter of view %d is NaN", i);
@@ -1041,6 +1389,23 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
         a.KQ = a.nside ? S.get(c, size_t(k) * n) : nullptr;
       }
     }
+    if (rule == RULE_ENET) {
+      B.enet = 1;
+      B.tt2 = S.get(c, size_t(n));
+      B.coef = S.get(c, size_t(B.ptot));
+      B.res = S.get(c, size_t(B.pmax));
+      B.dl = S.get(c, ENET_BW);
+      B.bstat = S.get(c, size_t(2) * ((B.pmax + ENET_BW - 1) / ENET_BW));
+      B.scal = S.get(c, size_t(M) * 4);
+      for (int i = 0; i < M; ++i) {
+        AdmmView& a = S.admm[i];
+        a.nside = 0;                       // on the p side whatever n is
+        a.side = p[i];
+        a.G = S.get(c, size_t(p[i]) * p[i]);
+        a.U = S.get(c, size_t(k) * p[i]);
+        a.KQ = nullptr;
+      }
+    }
     S.drv.create(c);
   });
 }
@@ -1069,6 +1434,58 @@ void als_admm_setup(ccz_ctx* c, AlsState& S, const ccz_view* views, const void* 
   S.admm_ready = true;
 }
 
+// SCCA_IPLS / ElasticCCA: the penalties, the two outer rules, and G_i = fl(X_i - mu_i)' fl(X_i - mu_i) of every view.  The fit
+// deflates G_i in place, so every fit needs a setup of its own.
+void als_enet_setup(ccz_ctx* c, AlsState& S, const ccz_view* views, const void* const* means, const double* a, const double* b,
+                    const int* ridge, int target_all, int post_std) {
+  if (S.rule != RULE_ENET) fail(CCZ_EINVAL, "als: the fit state was not created with CCZ_ALS_ENET");
+  if (!a || !b || !ridge) fail(CCZ_EINVAL, "als: null argument");
+  for (int i = 0; i < S.M; ++i) {
+    if (!(a[i] >= 0.0) || !(b[i] >= 0.0) || !std::isfinite(a[i]) || !std::isfinite(b[i]))
+      fail(CCZ_EINVAL, "als: the penalties of view %d must be finite and not negative", i);
+    if (ridge[i] && a[i] != 0.0) fail(CCZ_EINVAL, "als: the ridge solve of view %d takes no L1 penalty", i);
+    S.ea[i] = a[i]; S.eb[i] = b[i]; S.eridge[i] = ridge[i] ? 1 : 0;
+  }
+  S.enet_all = target_all ? 1 : 0;
+  S.enet_post = post_std ? 1 : 0;
+  const AlsViews vw = make_views(S, views, means);
+  for (int i = 0; i < S.M; ++i) by_dtype(S.dtype, [&](auto t) { launch_gram<decltype(t)>(c, S, vw, i); });
+  zero(c, S.B.coef, size_t(S.B.ptot) * 8);
+  zero(c, S.B.scal, size_t(S.M) * 32);
+  S.enet_ready = true;
+  S.enet_used = false;
+}
+
+// One solve of view `view` outside a fit (what the kernel tests drive): G (p x p, null keeps the view's own), q and the
+// starting coefficients from the host, t't = tt; r = q - G c, then n_sweeps CD sweeps under the stop rule.  The status is
+// left at (view, phase 1 or 2), so a fit must begin with ccz_als_set_init.
+void als_enet_solve(ccz_ctx* c, AlsState& S, int view, const double* G, const double* q, const double* c0, double tt, int64_t n_sweeps) {
+  const AlsBuf& B = S.B;
+  AlsViews vw;
+  memset(&vw, 0, sizeof(vw));
+  int64_t off = 0;
+  for (int i = 0; i < S.M; ++i) { vw.p[i] = S.p[i]; vw.off[i] = off; off += S.p[i]; }
+  const int64_t p = S.p[view];
+  sync(c);
+  if (G) h2d(c, S.admm[view].G, G, size_t(p) * p * 8);
+  h2d(c, B.coef + vw.off[view], c0, size_t(p) * 8);
+  // q as the single chunk partial of k_als_enet_rinit
+  h2d(c, B.xpart, q, size_t(p) * 8);
+  h2d(c, B.scal + 4 * view, &tt, 8);
+  AlsStatus st0;
+  memset(&st0, 0, sizeof(st0));
+  st0.view = view;
+  st0.sweep = 1;                         // not a dimension's first solve: start from c0
+  h2d(c, S.drv.dev, &st0, sizeof(st0));
+  hipLaunchKernelGGL(k_als_enet_rinit, dim3(unsigned((p + 3) / 4)), dim3(256), 0, stream(c), B.xpart, 1, p, S.admm[view].G,
+                     B.coef + vw.off[view], B.raw + vw.off[view], B.res, view, S.drv.dev);
+  CCZ_LAUNCH_CHECK();
+  launch_enet_step(c, S, view, 0, view, 1);
+  enqueue_cd(c, S, vw, view, n_sweeps);
+  S.has_init = false;
+  S.enet_used = true;
+}
+
 void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
   if (!w0) fail(CCZ_EINVAL, "als: null initial vectors");
   const AlsBuf& B = S.B;
@@ -1077,6 +1494,7 @@ void als_set_init(ccz_ctx* c, AlsState& S, const double* w0) {
   zero(c, B.Wout, size_t(B.ptot) * S.k * 8);
   zero(c, B.Q, size_t(S.M) * S.k * S.n * 8);
   zero(c, B.thr, size_t(S.M) * 16);
+  if (S.rule == RULE_ENET && S.enet_used) fail(CCZ_EINVAL, "als: ccz_als_enet_setup must precede every elastic-net fit (the last one deflated G)");
   AlsStatus st0;
   memset(&st0, 0, sizeof(st0));
   h2d(c, S.drv.dev, &st0, sizeof(st0));
@@ -1118,12 +1536,45 @@ int ccz_als_admm_setup(ccz_handle h, void* state, const ccz_view* views, const v
   })
 }
 
+int ccz_als_enet_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, const double* a,
+                       const double* b, const int* ridge, int target_all, int post_std) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
+    ccz::als_enet_setup(h, S, views, means_dev, a, b, ridge, target_all, post_std);
+  })
+}
+
+int ccz_als_enet_solve(ccz_handle h, void* state, int view, const double* G_host, const double* q_host, const double* c0_host,
+                       double tt, int64_t n_sweeps) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
+    if (S.rule != ccz::RULE_ENET || !S.enet_ready) ccz::fail(CCZ_EINVAL, "als: ccz_als_enet_setup has not been called");
+    if (view < 0 || view >= S.M || !q_host || !c0_host || n_sweeps < 0 || n_sweeps > ccz::ENET_CAP) ccz::fail(CCZ_EINVAL, "als: bad argument");
+    ccz::als_enet_solve(h, S, view, G_host, q_host, c0_host, tt, n_sweeps);
+  })
+}
+
+int ccz_als_enet_status(ccz_handle h, void* state, int64_t* cd_sweeps_per_dim, int64_t* capped) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
+    ccz::AlsStatus st;
+    ccz::d2h(h, &st, S.drv.dev, sizeof(st));
+    for (int64_t d = 0; d < S.k; ++d)
+      if (cd_sweeps_per_dim) cd_sweeps_per_dim[d] = st.inner[d];
+    if (capped) *capped = st.capped;
+  })
+}
+
 int ccz_als_sweeps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_sweeps,
                    int64_t* sweeps_known, int* stopped_known) {
   CCZ_GUARD(h, {
     ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
     if (!S.has_init) ccz::fail(CCZ_EINVAL, "als: ccz_als_set_init has not been called");
     if (S.rule == ccz::RULE_ADMM && !S.admm_ready) ccz::fail(CCZ_EINVAL, "als: ccz_als_admm_setup has not been called");
+    if (S.rule == ccz::RULE_ENET) {
+      if (!S.enet_ready) ccz::fail(CCZ_EINVAL, "als: ccz_als_enet_setup has not been called");
+      S.enet_used = true;
+    }
     ccz::run_chunk(h, "als", "n_sweeps", S, n_sweeps, sweeps_known, stopped_known, &ccz::AlsStatus::total,
                    [&] {
                      const ccz::AlsViews vw = ccz::make_views(S, views, means_dev);
@@ -1182,6 +1633,16 @@ int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host
         if (S.rule != ccz::RULE_ADMM) ccz::fail(CCZ_EINVAL, "als: buffer %d exists for CCZ_ALS_ADMM only", what);
         if (what == CCZ_ALS_PEEK_ETA) ccz::d2h(h, out_host, B.eta + off, size_t(p) * 8);
         else ccz::d2h(h, out_host, B.lip + view, 8);
+        break;
+      case CCZ_ALS_PEEK_GRAM:
+      case CCZ_ALS_PEEK_RESIDUAL:
+      case CCZ_ALS_PEEK_COEF:
+      case CCZ_ALS_PEEK_ENET:
+        if (S.rule != ccz::RULE_ENET) ccz::fail(CCZ_EINVAL, "als: buffer %d exists for CCZ_ALS_ENET only", what);
+        if (what == CCZ_ALS_PEEK_GRAM) ccz::d2h(h, out_host, S.admm[view].G, size_t(p) * p * 8);
+        else if (what == CCZ_ALS_PEEK_RESIDUAL) ccz::d2h(h, out_host, B.res, size_t(p) * 8);
+        else if (what == CCZ_ALS_PEEK_COEF) ccz::d2h(h, out_host, B.coef + off, size_t(p) * 8);
+        else ccz::d2h(h, out_host, B.scal + 4 * view, 32);
         break;
       case CCZ_ALS_PEEK_SCORE: {
         // the column-split partial sums, added in split order as the device adds them; the split count is that of the

@@ -1,9 +1,11 @@
-"""ALS models with deflation, run on the device: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span, SCCA_ADMM.
+"""ALS models with deflation, run on the device: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span, SCCA_ADMM, SCCA_IPLS,
+ElasticCCA.
 
 Reference: ``cca_zoo/linear/_iterative.py:38-158`` (the loop and the target score), ``:166-223`` (PLS_ALS),
 ``:231-380`` (SCCA_PMD and its bisection), ``:631-722`` (SCCA_Span), ``:839-930`` (ParkhomenkoCCA) and
 ``cca_zoo/_utils/_linalg.py:76-116`` (soft threshold, deflation); ``:388-514`` (SCCA_ADMM, whose iteration is described
-at the class).  The first four models share one sweep: for every view,
+at the class), ``:522-623`` and ``:730-831`` (SCCA_IPLS and ElasticCCA, whose update is an elastic-net regression solved
+on the device; see :class:`_BaseElasticNet`).  The first four models share one sweep: for every view,
 ``t = normalise(sum_{j != i} X_j w_j)``, ``raw = X_i' t``, then the model's rule turns ``raw`` into ``w_i``.  Every sweep
 runs in libccz (``csrc/als.hip``); the host draws the initial vectors of all dimensions up front (they do not depend on
 results), uploads them and enqueues sweeps in chunks behind a device stop word.
@@ -16,6 +18,7 @@ precision and corrects the two n-vectors of an update instead (DESIGN.md "ALS mo
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from numbers import Integral, Real
 from typing import Any, ClassVar
 
@@ -32,9 +35,12 @@ CHUNK_SWEEPS = 8
 #: limits of the device path (``csrc/als.hip``)
 MAX_DIMS, MAX_VIEWS = 32, 8
 #: rule codes of ``ccz_als_create`` (``include/ccz.h``)
-RULE_NORMALISE, RULE_SOFT_FIXED, RULE_SOFT_L1, RULE_TOP_S, RULE_ADMM = 0, 1, 2, 3, 4
+RULE_NORMALISE, RULE_SOFT_FIXED, RULE_SOFT_L1, RULE_TOP_S, RULE_ADMM, RULE_ENET = 0, 1, 2, 3, 4, 5
 #: SCCA_ADMM: the largest ``min(n, p_i)`` (the side of the Gram ``csrc/als.hip`` keeps per view)
 ADMM_MAX_SIDE = 16384
+#: SCCA_IPLS / ElasticCCA: the widest view (``csrc/als.hip`` keeps a ``p_i x p_i`` Gram per view), the CD sweeps one solve
+#: may take (scikit-learn's ``max_iter``)
+ENET_MAX_P, ENET_CAP = 16384, 1000
 
 
 def initial_vectors(random_state, p, k):
@@ -99,6 +105,13 @@ class _BaseIterative(BaseModel):
     def _setup_state(self, h, state, res) -> None:
         """Model-specific calls between ``ccz_als_create`` and the first sweep."""
 
+    def _total_units(self, k, m) -> int:
+        """The most ``ccz_als_sweeps`` units a fit can need: one per sweep."""
+        return k * int(self.max_iter)
+
+    def _after_fit(self, h, state, k) -> None:
+        """Model-specific read-backs once the fit has stopped."""
+
     def fit(self, views, y=None):
         refuse_row_sharded(f"{type(self).__name__} alternates over whole feature vectors, which this build does not shard "
                            "by rows")
@@ -114,7 +127,7 @@ class _BaseIterative(BaseModel):
         self._check_shapes(n, p)
         self.n_views_, self.n_features_in_, self.n_samples_ = m, p, n
         par = self._rule_parameters(p)
-        total = k * int(self.max_iter)
+        total = self._total_units(k, m)
         chunk = max(1, min(CHUNK_SWEEPS, total))
         with res:
             h = res.handle
@@ -138,6 +151,7 @@ class _BaseIterative(BaseModel):
                     raise RuntimeError(f"ALS fit ended after {dims.value} of {k} dimensions")   # cannot happen: k * max_iter sweeps
                 wflat = np.empty(sum(p) * k)
                 h.check(h.lib.ccz_als_get_weights(h.raw, state, wflat.ctypes.data_as(C.POINTER(C.c_double))))
+                self._after_fit(h, state, k)
         self.n_iter_ = [int(x) for x in iters]
         self.last_delta_ = [float(x) for x in deltas]
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
@@ -352,3 +366,177 @@ class SCCA_ADMM(_BaseIterative):
 
     def _setup_state(self, h, state, res):
         h.check(h.lib.ccz_als_admm_setup(h.raw, state, res.varr, res.marr, float(self.mu)))
+
+
+class _BaseElasticNet(_BaseIterative):
+    r"""SCCA_IPLS and ElasticCCA: every view update is an elastic-net regression of a target on the deflated view,
+
+    $$
+    \hat c_i = \arg\min_c \frac{1}{2n} \|X_i c - t\|_2^2 + \alpha_i \bigl(l_1 \|c\|_1 + \tfrac{1 - l_1}{2} \|c\|_2^2\bigr),
+    $$
+
+    which the reference hands to scikit-learn's ``Lasso`` / ``ElasticNet`` with ``selection="random"`` (``Ridge`` when
+    ``l1_ratio == 0``; ``cca_zoo/linear/_iterative.py:938-982``).  The contract here is the reference's *update map*, not
+    its trajectory of coordinate visits: the minimiser is unique whenever ``l1_ratio < 1`` with ``alpha > 0`` or the
+    deflated view has full column rank, and then it depends neither on the visiting order nor on the warm start.  The
+    device solves it by blocked cyclic coordinate descent on the float64 Gram matrix of the view (``csrc/als.hip``),
+    formed once per fit and deflated in place, under scikit-learn's own stop rule: after a sweep whose largest coordinate
+    change is below ``tol`` times the largest coefficient, the duality gap is compared with ``tol * t't``; a solve takes at
+    most 1000 sweeps.  Within a dimension a solve starts from the view's previous coefficients, the first from zero.
+
+    ``tol`` is also the solver's tolerance, as in the reference.  The gap is formed from ``t't - c'q - c'r`` in float64,
+    which cancels: a ``tol`` below about 1e-13 cannot be reached except by an accident of rounding, and such a fit runs its
+    solves to the cap.
+
+    A solve that ends on the cap without meeting the stop rule is counted, and ``fit`` then emits one ``RuntimeWarning``
+    (scikit-learn's ``ConvergenceWarning`` in the reference), never silently.
+
+    Outside the contract (nothing is claimed there beyond finite weights of the right shape and determinism):
+
+    - ``l1_ratio = 1`` with ``p_i >= n``: the lasso objective is not strongly convex and its minimiser need not be unique;
+    - any fit in which scikit-learn's own solver would not converge: the reference's result is then an unfinished random
+      walk that nothing can match.
+
+    Differences from the reference, on purpose (besides those of the family):
+
+    - ``p_i <= 16384`` for every view (the Gram matrix is ``p_i x p_i``); wider views raise ``ValueError``.
+    - ``l1_ratio = 0`` with ``alpha = 0`` and ``p_i >= n`` raises ``ValueError``: the unpenalised least-squares problem has
+      no unique solution there (the reference returns whichever one its factorisation yields).
+    - float32 views: in the first dimension the reference's solver runs in float32 (``ElasticNet.fit`` casts the target
+      to the dtype of ``X``); here everything after centring is float64.
+
+    ``n_inner_iter_`` (not in the reference) lists the coordinate-descent sweeps taken per latent dimension, over all
+    solves.
+    """
+
+    _parameter_constraints: ClassVar[dict[str, list[Any]]] = {
+        **_BaseIterative._parameter_constraints,
+        "alpha": [Interval(Real, 0, None, closed="left"), list],
+        "l1_ratio": [Interval(Real, 0, 1, closed="both"), list],
+    }
+    _rule = RULE_ENET
+    _l1_default = 1.0
+    _target_all = False
+    _post_std = False
+
+    def _penalties(self, m):
+        alpha = [float(a) for a in perview_parameter("alpha", self.alpha, 0.0, m)]
+        l1 = [float(x) for x in perview_parameter("l1_ratio", self.l1_ratio, self._l1_default, m)]
+        if any(not (a >= 0.0 and np.isfinite(a)) for a in alpha):
+            raise ValueError("alpha must be finite and not negative")
+        if any(not 0.0 <= x <= 1.0 for x in l1):
+            raise ValueError("l1_ratio must lie in [0, 1]")
+        return alpha, l1
+
+    def _rule_parameters(self, p):
+        self._penalties(len(p))
+        return [0.0] * len(p)
+
+    def _check_shapes(self, n, p):
+        alpha, l1 = self._penalties(len(p))
+        for i, pi in enumerate(p):
+            if pi > ENET_MAX_P:
+                raise ValueError(f"view {i} has {pi} columns: {type(self).__name__} keeps a p x p Gram per view and supports at "
+                                 f"most {ENET_MAX_P}")
+            if l1[i] == 0.0 and alpha[i] == 0.0 and pi >= n:
+                raise ValueError(f"view {i}: l1_ratio = 0 with alpha = 0 and p >= n is a least-squares problem without a unique "
+                                 "solution")
+
+    def _setup_state(self, h, state, res):
+        m, n = len(res.p), res.n
+        alpha, l1 = self._penalties(m)
+        ridge = [1 if x == 0.0 else 0 for x in l1]
+        # scikit-learn's ElasticNet scales its penalties by n; its Ridge does not
+        a = [0.0 if r else n * al * x for al, x, r in zip(alpha, l1, ridge)]
+        b = [al if r else n * al * (1.0 - x) for al, x, r in zip(alpha, l1, ridge)]
+        h.check(h.lib.ccz_als_enet_setup(h.raw, state, res.varr, res.marr, (C.c_double * m)(*a), (C.c_double * m)(*b),
+                                         (C.c_int * m)(*ridge), int(self._target_all), int(self._post_std)))
+
+    def _total_units(self, k, m):
+        # a unit advances a sweep by at least one CD sweep of one solve, or ends it
+        return k * int(self.max_iter) * (m * ENET_CAP + 1)
+
+    def _after_fit(self, h, state, k):
+        inner = (C.c_int64 * k)()
+        capped = C.c_int64(0)
+        h.check(h.lib.ccz_als_enet_status(h.raw, state, inner, C.byref(capped)))
+        self.n_inner_iter_ = [int(x) for x in inner]
+        if capped.value:
+            warnings.warn(f"{type(self).__name__}: {capped.value} coordinate-descent solve(s) ended on the cap of {ENET_CAP} sweeps "
+                          "without reaching the duality-gap tolerance; consider a larger alpha or tol", RuntimeWarning,
+                          stacklevel=3)
+
+
+class SCCA_IPLS(_BaseElasticNet):
+    r"""Sparse CCA by iterative penalised least squares (Mai & Zhang 2019), every solve on the device.
+
+    For view $i$ the target is $\bar s_{\neg i}$, the normalised sum of the other views' scores; the elastic-net
+    coefficients $\hat c_i$ (see :class:`_BaseElasticNet`) are divided by the population standard deviation of their score
+    $X_i \hat c_i$ when that exceeds 1e-12, so that the score has unit variance (reference:
+    ``cca_zoo/linear/_iterative.py:522-623``).
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        alpha: Elastic-net penalty strength(s), per view. Default is 0.
+        l1_ratio: Share(s) of the L1 penalty, per view: 1 is the lasso, 0 ridge regression. Default is 1.
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance of the sweeps and of every solve. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _l1_default = 1.0
+    _target_all = False
+    _post_std = True
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        alpha: float | list[float] = 0.0,
+        l1_ratio: float | list[float] = 1.0,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.alpha = alpha
+        self.l1_ratio = l1_ratio
+
+
+class ElasticCCA(_BaseElasticNet):
+    r"""Elastic-net CCA (Waaijenborg 2008), every solve on the device.
+
+    For every view the target is the normalised sum of ALL views' scores, view $i$'s own included, and $w_i$ is the
+    elastic-net coefficient vector as it comes (see :class:`_BaseElasticNet`; reference:
+    ``cca_zoo/linear/_iterative.py:730-831``).
+
+    Args:
+        latent_dimensions: Number of latent dimensions. Default is 1.
+        center: Whether to subtract column means. Default True.
+        alpha: Elastic-net penalty strength(s), per view. Default is 0.
+        l1_ratio: Share(s) of the L1 penalty, per view. Default is 0.5.
+        max_iter: Maximum sweeps per dimension. Default is 500.
+        tol: Convergence tolerance of the sweeps and of every solve. Default is 1e-6.
+        random_state: Seed of the initial vectors.
+    """
+
+    _l1_default = 0.5
+    _target_all = True
+    _post_std = False
+
+    def __init__(
+        self,
+        latent_dimensions: int = 1,
+        center: bool = True,
+        alpha: float | list[float] = 0.0,
+        l1_ratio: float | list[float] = 0.5,
+        max_iter: int = 500,
+        tol: float = 1e-6,
+        random_state: int | None = None,
+    ) -> None:
+        super().__init__(latent_dimensions=latent_dimensions, center=center, max_iter=max_iter, tol=tol,
+                         random_state=random_state)
+        self.alpha = alpha
+        self.l1_ratio = l1_ratio

@@ -504,6 +504,14 @@ CCZ_API int ccz_ey_get_weights(ccz_handle h, void* state, double* W_host);
  * L_i = |X_d' X_d|_F / n + mu taken at the first iteration of each dimension from the Gram of the centred view on its
  * smaller side.  min(n_rows, p[i]) <= 16384 for every view; ccz_als_admm_setup must precede the first ccz_als_sweeps. */
 #define CCZ_ALS_ADMM 4
+/* SCCA_IPLS and ElasticCCA (cca_zoo/linear/_iterative.py:522-623, :730-831, :938-982): each update is the elastic-net
+ * regression argmin_c 1/2 |X_d c - t|^2 + a_i |c|_1 + b_i/2 |c|^2 of the target on the deflated view, solved by blocked
+ * cyclic coordinate descent on G_i = X_d' X_d (formed once on the p side, deflated in place) under scikit-learn's stop rule
+ * (coordinate change, then duality gap < tol t't; at most 1000 CD sweeps).  rule_param is ignored.  p[i] <= 16384 for every
+ * view; ccz_als_enet_setup must precede ccz_als_set_init of every fit.  What ccz_als_sweeps enqueues for this rule is not a
+ * sweep but a UNIT, a fixed kernel sequence that advances the sweep as far as up to 16 CD sweeps per view take it (csrc/als.hip);
+ * a sweep needs one unit or more, so the caller enqueues units until the stop is reported. */
+#define CCZ_ALS_ENET 5
 
 /* Create a fit state: n_views (1..8) views of widths p[i] and n_rows rows, k (1..32) latent dimensions, the rule and its
  * per-view parameter (NULL for CCZ_ALS_NORMALISE), tol and max_iter per dimension as in the reference
@@ -522,6 +530,26 @@ CCZ_API int ccz_als_set_init(ccz_handle h, void* state, const double* w0_host);
  * side ((X - mu)(X - mu)' when n_rows <= p[i], else (X - mu)'(X - mu)) in the state.  views / means_dev as for
  * ccz_als_sweeps, and the same rows must be passed there.  Asynchronous on the handle's stream. */
 CCZ_API int ccz_als_admm_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, double mu);
+
+/* CCZ_ALS_ENET only.  Per view: a[i] = n alpha l1_ratio, b[i] = n alpha (1 - l1_ratio); ridge[i] != 0 (the reference's
+ * Ridge, l1_ratio = 0): a[i] = 0, b[i] = alpha, and the solve stops on the coordinate change alone.  target_all: the target
+ * is the normalised sum of EVERY view's score (ElasticCCA), else of the other views' (SCCA_IPLS).  post_std: w_i is the
+ * coefficient vector over the population standard deviation of its score when that exceeds 1e-12 (SCCA_IPLS), else the
+ * coefficient vector (ElasticCCA).  Forms G_i = fl(X_i - mu_i)' fl(X_i - mu_i) in float64 for every view.  The fit deflates
+ * G_i, so every fit needs its own setup.  Asynchronous on the handle's stream. */
+CCZ_API int ccz_als_enet_setup(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, const double* a,
+                               const double* b, const int* ridge, int target_all, int post_std);
+
+/* CCZ_ALS_ENET only, after the setup: one solve of view `view` outside a fit, for tests of the kernels.  G_host (p x p
+ * row-major symmetric float64; NULL keeps the view's G), q_host and the starting coefficients c0_host (p each), tt = t't.
+ * Enqueues r = q - G c0 and n_sweeps (<= 1000) CD sweeps under the stop rule of the state's tol; read the result with
+ * ccz_als_peek.  A fit on the state must begin again with ccz_als_enet_setup and ccz_als_set_init. */
+CCZ_API int ccz_als_enet_solve(ccz_handle h, void* state, int view, const double* G_host, const double* q_host,
+                               const double* c0_host, double tt, int64_t n_sweeps);
+
+/* CCZ_ALS_ENET only: CD sweeps taken per dimension (k entries) and the number of solves that ended on the cap of 1000
+ * sweeps without meeting the stop rule.  Synchronises. */
+CCZ_API int ccz_als_enet_status(ccz_handle h, void* state, int64_t* cd_sweeps_per_dim, int64_t* capped);
 
 /* Enqueue n_sweeps (<= chunk_sweeps) sweeps (cca_zoo/linear/_iterative.py:86-117).  Returns without waiting for the
  * device; the only host wait is for the chunk that used the same status slot two calls earlier, whose state is returned
@@ -558,6 +586,13 @@ CCZ_API int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int6
 #define CCZ_ALS_PEEK_Z 6
 #define CCZ_ALS_PEEK_ETA 7
 #define CCZ_ALS_PEEK_LIPSCHITZ 8
+/* CCZ_ALS_ENET: RAW holds q = X_d' t of the view's last solve; GRAM is G_i (p_i x p_i, deflated by the finished dimensions),
+ * RESIDUAL r = q - G c of the LAST solve of any view (p_i), COEF the view's coefficients (p_i), ENET four numbers: t't, the
+ * last duality gap computed, the score's standard deviation, the CD sweeps of the view's last solve. */
+#define CCZ_ALS_PEEK_GRAM 9
+#define CCZ_ALS_PEEK_RESIDUAL 10
+#define CCZ_ALS_PEEK_COEF 11
+#define CCZ_ALS_PEEK_ENET 12
 CCZ_API int ccz_als_peek(ccz_handle h, void* state, int what, int view, double* out_host);
 
 /* Copy the finished columns (W blocks as in ccz_ey_get_weights: view i's p_i x k row-major float64 weights, views back

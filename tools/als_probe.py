@@ -3,6 +3,7 @@
 
     python tools/als_probe.py [--out profiles/als_probe.json] [--only device|cpu] [--model PLS_ALS|SCCA_PMD|SCCA_ADMM]
                               [--sweeps 20]
+    python tools/als_probe.py --model SCCA_IPLS|ElasticCCA [--out profiles/als_probe.json] [--only device|cpu]
 
 device: PLS_ALS, SCCA_PMD and SCCA_ADMM sweeps through the C ABI on n = 4096, 2 x 262144 float32 features drawn on the device
         (ccz_randn_fill), k = 1, tol = 0, a fixed number of sweeps: ms per sweep between two stream synchronisations
@@ -15,6 +16,13 @@ device: PLS_ALS, SCCA_PMD and SCCA_ADMM sweeps through the C ABI on n = 4096, 2 
         ``rocprofv3 --kernel-trace --stats`` run of ``--only device --model SCCA_PMD`` and one of ``--model PLS_ALS``,
         summarised by tools/rocpd_stats.py (profiles/als_kernel_stats.md); ``--kernel-stats MODEL=TABLE.md`` reads such a
         table back and adds the split of the sweep's kernel time (rule kernels, one-workgroup kernels) to the JSON.
+enet:   ``--model SCCA_IPLS`` / ``ElasticCCA``: the estimator itself (k = 1, alpha = 0.05, l1_ratio = 0.5, tol = 1e-6, at most 20
+        sweeps) on float32 CUDA tensors at a tall shape (n = 4096, p = 1024 + 768) and a wide one (n = 256, p = 4096 + 2048):
+        ms per outer sweep (fit wall time over ``n_iter_``, warm), CD sweeps per solve, the one-off Gram time
+        (ccz_als_enet_setup between two synchronisations, best of three), and PLS_ALS on the same tensors for the same
+        number of sweeps -- the two streaming passes without a solve -- from which the share of the CD kernels is
+        estimated.  Beside them the same fit by a scikit-learn-structured CPU restatement (float64 copies deflated
+        explicitly, ``ElasticNet(selection="random", warm_start=True)`` per view) on the host cores.
 cpu:    the reference-structured float64 NumPy sweep (float64 copies of the views, two matrix-vector products per
         view) on the host cores at n = 512 with the same widths, scaled by 8 to n = 4096 (labelled as scaled).
 """
@@ -136,6 +144,106 @@ def cpu(out, sweeps=2):
     }
 
 
+ENET_SHAPES = {"tall": (4096, (1024, 768)), "wide": (256, (4096, 2048))}
+ENET_PAR = dict(latent_dimensions=1, alpha=0.05, l1_ratio=0.5, tol=1e-6, max_iter=20, random_state=0)
+
+
+def _enet_views(n, dims):
+    rng = np.random.default_rng(n)
+    z = rng.standard_normal((n, 2))
+    return [(z @ rng.standard_normal((2, d)) + rng.standard_normal((n, d))).astype(np.float32) for d in dims]
+
+
+def enet_device(out, model):
+    import torch
+
+    import cca_zoo_amd.linear as lin
+    from cca_zoo_amd import _backend
+
+    h = _backend.default_handle()
+    res = {}
+    for tag, (n, dims) in ENET_SHAPES.items():
+        tens = [torch.as_tensor(v, device="cuda") for v in _enet_views(n, dims)]
+        times = []
+        for _ in range(3):                       # the first fit loads the code objects
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            est = getattr(lin, model)(**ENET_PAR).fit(tens)
+            times.append(time.perf_counter() - t0)
+        sweeps = est.n_iter_[0]
+        pls = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lin.PLS_ALS(latent_dimensions=1, tol=0.0, max_iter=sweeps, random_state=0).fit(tens)
+            pls.append(time.perf_counter() - t0)
+        # the one-off Gram through the C ABI
+        m = len(dims)
+        varr = (_backend.View * m)()
+        for i, v in enumerate(tens):
+            varr[i].data, varr[i].cols, varr[i].ld = v.data_ptr(), dims[i], v.stride(0)
+        mus = [v.mean(dim=0) for v in tens]
+        marr = (C.c_void_p * m)(*[mu.data_ptr() for mu in mus])
+        state = C.c_void_p()
+        zeros = (C.c_double * m)(*([0.0] * m))
+        h.check(h.lib.ccz_als_create(h.raw, _backend.F32, m, (C.c_int64 * m)(*dims), n, 1, 5, zeros, 1e-6, 20, 8, C.byref(state)))
+        setup = []
+        try:
+            for _ in range(3):
+                h.sync()
+                t0 = time.perf_counter()
+                h.check(h.lib.ccz_als_enet_setup(h.raw, state, varr, marr, zeros, zeros, (C.c_int * m)(*([0] * m)), 0, 0))
+                h.sync()
+                setup.append(time.perf_counter() - t0)
+        finally:
+            h.check(h.lib.ccz_als_destroy(h.raw, state))
+        fit_ms, pls_ms = min(times[1:]) * 1e3, min(pls[1:]) * 1e3
+        res[tag] = {"n": n, "p": list(dims), "sweeps": sweeps, "fit_ms": round(fit_ms, 2), "ms_per_sweep": round(fit_ms / sweeps, 3),
+                    "cd_sweeps_per_solve": round(est.n_inner_iter_[0] / (sweeps * m), 2), "gram_setup_ms": round(min(setup) * 1e3, 3),
+                    "pls_als_fit_ms_same_sweeps": round(pls_ms, 2),
+                    "cd_share_estimate": round(max(0.0, 1.0 - pls_ms / fit_ms), 3),
+                    "support": [int(np.count_nonzero(w)) for w in est.weights_]}
+    out.setdefault("enet_device", {})[model] = {"params": ENET_PAR, "dtype": "float32", **res,
+                                                "note": "fit wall time includes upload-free setup, the Gram and the read-back; "
+                                                        "cd_share_estimate = 1 - PLS_ALS fit time / fit time"}
+
+
+def enet_cpu(out, model):
+    """The reference's structure with scikit-learn's own solver: float64 copies, explicit deflation, random selection."""
+    from sklearn.linear_model import ElasticNet
+
+    res = {}
+    for tag, (n, dims) in ENET_SHAPES.items():
+        X = [v.astype(np.float64) for v in _enet_views(n, dims)]
+        X = [x - x.mean(axis=0) for x in X]
+        m = len(X)
+        rng = np.random.default_rng(0)
+        w = [rng.standard_normal(d) for d in dims]
+        w = [x / np.linalg.norm(x) for x in w]
+        regs = [ElasticNet(alpha=ENET_PAR["alpha"], l1_ratio=ENET_PAR["l1_ratio"], fit_intercept=False, warm_start=True,
+                           tol=ENET_PAR["tol"], random_state=0, selection="random") for _ in X]
+        t0 = time.perf_counter()
+        sweeps = 0
+        for sweeps in range(1, ENET_PAR["max_iter"] + 1):
+            prev = [x.copy() for x in w]
+            for i in range(m):
+                t = sum(X[j] @ w[j] for j in range(m) if model == "ElasticCCA" or j != i)
+                nt = np.linalg.norm(t)
+                t = t / nt if nt > 1e-12 else t
+                c = regs[i].fit(X[i], t).coef_.copy()
+                if model == "SCCA_IPLS":
+                    sd = (X[i] @ c).std()
+                    c = c / sd if sd > 1e-12 else c
+                w[i] = c
+            if max(np.linalg.norm(a - b) for a, b in zip(w, prev)) < ENET_PAR["tol"]:
+                break
+        dt = time.perf_counter() - t0
+        res[tag] = {"n": n, "p": list(dims), "sweeps": sweeps, "fit_ms": round(dt * 1e3, 2), "ms_per_sweep": round(dt * 1e3 / sweeps, 3)}
+    out.setdefault("enet_cpu_comparator", {})[model] = {
+        "what": "scikit-learn-structured float64 fit on host copies (ElasticNet, selection=random, warm start)",
+        "threads": os.environ.get("OMP_NUM_THREADS", "unset"), **res}
+
+
 RULE_KERNELS = ("k_als_fold", "k_als_levels", "k_als_norm", "k_als_apply", "k_als_admm_fold", "k_als_admm_apply")
 ONE_WORKGROUP_KERNELS = ("k_als_prologue", "k_als_admm_prologue", "k_als_finish", "k_als_advance", "k_als_admm_h",
                          "k_als_admm_lfinal")
@@ -167,13 +275,19 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--only", choices=["device", "cpu", "none"])
     ap.add_argument("--kernel-stats", action="append", default=[], metavar="MODEL=TABLE.md")
-    ap.add_argument("--model", choices=["PLS_ALS", "SCCA_PMD", "SCCA_ADMM"], help="device part: this model alone (for a profiler run)")
+    ap.add_argument("--model", choices=["PLS_ALS", "SCCA_PMD", "SCCA_ADMM", "SCCA_IPLS", "ElasticCCA"],
+                    help="device part: this model alone (for a profiler run); SCCA_IPLS / ElasticCCA: the elastic-net probe")
     ap.add_argument("--sweeps", type=int, default=20)
     a = ap.parse_args()
     out = {}
-    if a.only in (None, "device"):
+    if a.model in ("SCCA_IPLS", "ElasticCCA"):
+        if a.only in (None, "device"):
+            enet_device(out, a.model)
+        if a.only in (None, "cpu"):
+            enet_cpu(out, a.model)
+    elif a.only in (None, "device"):
         device(out, a.sweeps, (a.model,) if a.model else ("PLS_ALS", "SCCA_PMD", "SCCA_ADMM"))
-    if a.only in (None, "cpu"):
+    if a.only in (None, "cpu") and a.model not in ("SCCA_IPLS", "ElasticCCA"):
         cpu(out)
     for spec in a.kernel_stats:
         kernel_split(out, spec)
@@ -183,7 +297,7 @@ def main():
             with open(a.out) as f:
                 prev = json.load(f)
         for key, val in out.items():
-            if key == "kernel_split":
+            if key in ("kernel_split", "enet_device", "enet_cpu_comparator"):
                 prev.setdefault(key, {}).update(val)
             else:
                 prev[key] = val
