@@ -20,5 +20,5 @@ def k1_route(route=None, device=None):
     return _backend.default_handle(device).k1_route(route)
 
 
-__all__ = ["row_sharded", "shard_bounds", "k1_route", "linear", "nonparametric", "deep", "datasets"]
+__all__ = ["row_sharded", "shard_bounds", "k1_route", "linear", "nonparametric", "deep", "datasets", "tree"]
 __version__ = "0.1.0"

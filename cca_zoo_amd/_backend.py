@@ -171,6 +171,20 @@ SIGNATURES = {
     "ccz_rrr_get_result": (_int, [_vp, _vp, _pdbl, _vp]),
     "ccz_rownorm4": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
     "ccz_moments_block": (_int, [_vp, _vp, _i64, _i64, _int, _i64, _i64, _i64, _i64, _dbl, _vp, _i64]),
+    "ccz_tree_create": (_int, [_vp, _int, _pi64, _i64, _i64, _i64, _i64, _dbl, _dbl, _int, _dbl, C.c_uint64, _i64, C.POINTER(_vp)]),
+    "ccz_tree_destroy": (_int, [_vp, _vp]),
+    "ccz_tree_setup": (_int, [_vp, _vp, _int, C.POINTER(View), C.POINTER(_vp), _pi64, _i64]),
+    "ccz_tree_project": (_int, [_vp, _vp, _int, C.POINTER(View), C.POINTER(_vp), _pdbl, _pdbl]),
+    "ccz_tree_set_margin": (_int, [_vp, _vp, _pdbl]),
+    "ccz_tree_set_features": (_int, [_vp, _vp, _pint, _pint]),
+    "ccz_tree_rounds": (_int, [_vp, _vp, _i64, _pi64, _pint]),
+    "ccz_tree_status": (_int, [_vp, _vp, _pi64, _pint]),
+    "ccz_tree_get_bins": (_int, [_vp, _vp, _int, _vp, _vp, _vp]),
+    "ccz_tree_get_trees": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "ccz_tree_get_embedding": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "ccz_tree_grow": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _i64, _vp, _vp, _vp, _vp,
+                             _vp, _vp]),
+    "ccz_tree_predict": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64]),
 }
 
 

@@ -786,6 +786,57 @@ CCZ_API int ccz_rownorm4(ccz_handle h, int dtype, const ccz_view* view, int64_t 
 CCZ_API int ccz_moments_block(ccz_handle h, const double* moments_dev, int64_t D, int64_t n_rows, int center, int64_t r0,
                               int64_t rows, int64_t c0, int64_t cols, double shift, double* out_dev, int64_t ldo);
 
+/* ---- TreeCCA (csrc/tree.hip): boosted-tree CCA, histogram tree growth on the device ---------------------------------------
+ * The booster is the one tests/treecca_restatement.py specifies: 256 bins per feature from the sorted column of at most 8192
+ * sampled rows, gradients in fixed point (q = rint(g 2^S), |q| <= 2^30, node sums exact integers), gain in float64 with every
+ * operation rounded once, ties to the lowest feature, then the lowest bin.  A tree is a heap of 2^(max_depth + 1) - 1 nodes
+ * (children of i: 2 i + 1 and 2 i + 2): feature (-1: not a split), bin, threshold (float32 cut), leaf (float32, 0 on a split),
+ * gain (float64, 0 on a leaf).  Limits: 2..8 views, 1 <= k <= 32 and k <= every p_i, 1 <= max_depth <= 8, p_i <= 32768,
+ * n < 2^31; the histogram workspace is 64 MiB (the features of a level are tiled to fit it).
+ *   create         a fit state for n_rounds rounds; subsample in (0, 1], seed the hash seed of the row samples
+ *   setup          cuts and bins of every view from DEVICE rows (dtype CCZ_F32 / CCZ_F64, means_dev of the same dtype or null);
+ *                  sample_rows (host) are the min(n, 8192) rows the cuts are taken from
+ *   project        Z0_i = (X_i - mean_i) W_i (W_host: the p_i x k blocks one after another, float64) kept on the device;
+ *                  sumsq_host (n_views x k) receives the column sums of squares
+ *   set_margin     base margin = float32(Z0 / scale) (scale_host: n_views x k), tree sums zero, the round counter zero
+ *   set_features   per view n_selected[i] ascending feature indices for every round (lists_host: view after view, round after
+ *                  round)
+ *   rounds         enqueues n_rounds (at most chunk_rounds) whole rounds: per view in turn the EY gradient of all views, the shared
+ *                  rescale to std 0.1, one tree per component, and with gauss_seidel a fresh gradient before the next view; no
+ *                  host wait but for the status of the chunk two calls back (rounds_known: -1 while unknown)
+ *   get_bins       bins (p x n, feature-major), cuts (p x 256, unused entries +inf) and cut counts of a view, to the host
+ *   get_trees      the trees of a view, rounds x k x nodes each, to the host
+ *   get_embedding  double(base margin) + double(float32 tree sum), n x k float64, to the host and / or the device
+ *   grow           TEST SEAM: the k trees of one view from caller-supplied HOST bins (p x n), cuts (p x 256), cut counts,
+ *                  quantised gradients (k x n, int32), shifts (k), row mask (n) and ascending feature list; hist_bytes > 0
+ *                  replaces the workspace bound (to force feature tiling).  Returns k x nodes heap arrays and node_out (k x n):
+ *                  a row's position in the last level, a leaf above it continued to the left (pos -> 2 pos).
+ *   predict        out_dev (n x k, float64) = (X - mean) P (proj_dev: p x k float64, null: 0) + the float32 leaves of n_trees
+ *                  trees ([n_trees][k][nodes] DEVICE arrays) summed in tree order; left iff float32(x - mean) < threshold */
+CCZ_API int ccz_tree_create(ccz_handle h, int n_views, const int64_t* p, int64_t n_rows, int64_t k, int64_t max_depth, int64_t n_rounds,
+                            double learning_rate, double min_child_weight, int gauss_seidel, double subsample, uint64_t seed,
+                            int64_t chunk_rounds, void** state_out);
+CCZ_API int ccz_tree_destroy(ccz_handle h, void* state);
+CCZ_API int ccz_tree_setup(ccz_handle h, void* state, int dtype, const ccz_view* views, const void* const* means_dev,
+                           const int64_t* sample_rows, int64_t n_sample);
+CCZ_API int ccz_tree_project(ccz_handle h, void* state, int dtype, const ccz_view* views, const void* const* means_dev, const double* W_host,
+                             double* sumsq_host);
+CCZ_API int ccz_tree_set_margin(ccz_handle h, void* state, const double* scale_host);
+CCZ_API int ccz_tree_set_features(ccz_handle h, void* state, const int* n_selected, const int* lists_host);
+CCZ_API int ccz_tree_rounds(ccz_handle h, void* state, int64_t n_rounds, int64_t* rounds_known, int* stopped_known);
+CCZ_API int ccz_tree_status(ccz_handle h, void* state, int64_t* rounds, int* stopped);
+CCZ_API int ccz_tree_get_bins(ccz_handle h, void* state, int view, uint8_t* bins_host, float* cuts_host, int* ncuts_host);
+CCZ_API int ccz_tree_get_trees(ccz_handle h, void* state, int view, int* feature_host, int* bin_host, float* threshold_host,
+                               float* leaf_host, double* gain_host);
+CCZ_API int ccz_tree_get_embedding(ccz_handle h, void* state, int view, double* Z_host, double* Z_dev);
+CCZ_API int ccz_tree_grow(ccz_handle h, int64_t n_rows, int64_t p, int64_t k, int64_t max_depth, const uint8_t* bins_host,
+                          const float* cuts_host, const int* ncuts_host, const int* q_host, const int* shift_host, const uint8_t* mask_host,
+                          const int* features_host, int64_t n_features, double learning_rate, double min_child_weight, int64_t hist_bytes,
+                          int* feature_out, int* bin_out, float* threshold_out, float* leaf_out, double* gain_out, uint8_t* node_out);
+CCZ_API int ccz_tree_predict(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev, const double* proj_dev,
+                             int64_t k, int64_t n_trees, int64_t max_depth, const int* feature_dev, const float* threshold_dev,
+                             const float* leaf_dev, double* out_dev, int64_t ldo);
+
 #ifdef __cplusplus
 }
 #endif
