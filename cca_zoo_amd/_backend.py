@@ -154,6 +154,14 @@ SIGNATURES = {
     "ccz_gfa_peek": (_int, [_vp, _vp, _int, _int, _pdbl]),
     "ccz_gfa_get_result": (_int, [_vp, _vp, _pint, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
     "ccz_gfa_sumsq": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl]),
+    "ccz_svi_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _i64, _dbl, C.c_uint64, _i64, C.POINTER(_vp)]),
+    "ccz_svi_destroy": (_int, [_vp, _vp]),
+    "ccz_svi_set_init": (_int, [_vp, _vp, _pdbl]),
+    "ccz_svi_steps": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pint]),
+    "ccz_svi_status": (_int, [_vp, _vp, _pi64, _pint, _pi64]),
+    "ccz_svi_peek": (_int, [_vp, _vp, _int, _pdbl]),
+    "ccz_svi_get_result": (_int, [_vp, _vp, _pdbl, _pdbl, _pdbl]),
+    "ccz_colsumsq_weighted": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl, _pdbl]),
     "ccz_kr_moment": (_int, [_vp, C.POINTER(View), _int, _i64, _dbl, _vp]),
     "ccz_kr_apply": (_int, [_vp, C.POINTER(View), _int, _i64, _vp, _int, _dbl, _vp, _i64]),
     "ccz_cp_create": (_int, [_vp, _int, _pi64, _i64, _dbl, _i64, _i64, C.POINTER(_vp)]),

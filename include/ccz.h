@@ -667,6 +667,83 @@ CCZ_API int ccz_gfa_get_result(ccz_handle h, void* state, int* k_active, double*
  * noise variance that is constant within a view).  Synchronises. */
 CCZ_API int ccz_gfa_sumsq(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev, double* sumsq_host);
 
+/* ---- VariationalBayesCCA: mean-field stochastic variational inference (csrc/svi.hip) --------------------------------------
+ * Whole SVI steps on the device, no host wait inside a chunk of steps.  The model is that of
+ * cca_zoo/probabilistic/_vbcca.py:108-159; the reference fits it with numpyro (AutoNormal, Trace_ELBO, Adam), which this
+ * library cannot call, so the algorithm is written out here and restated in NumPy in tests/vbcca_restatement.py.  These are
+ * NOT numpyro's bits: its PRNG differs.
+ *
+ * Model, in unconstrained sites, a0 = b0 = 1e-3, K latent dimensions, M views of p_i columns, n rows, P = sum p_i:
+ *   a = log alpha (K)       alpha_k ~ Gamma(a0, b0) (rate b0), Jacobian + a_k
+ *   W_i (p_i x K)           W_i[j, k] ~ N(0, 1 / alpha_k)
+ *   s_i = log psi_i (p_i)   s_i[j] ~ N(0, 1)
+ *   Z (n x K)               Z[r, k] ~ N(0, 1)
+ *   x_i[r, j] ~ N((Z W_i')[r, j], exp(s_i[j])): exp(s) is the STANDARD DEVIATION of the likelihood, as in the reference.
+ * Guide: every element an independent normal, loc and scale = softplus(rho); scale starts at 0.1, loc is uploaded.
+ * The flat parameter vector of N = K + P K + P + n K doubles is [ a | W_0 .. W_{M-1} (row-major, back to back) |
+ * s_0 .. s_{M-1} | Z (row-major) ]; loc, rho, the Adam moments, theta, eps and the gradient all use it.
+ * Sites are numbered 0: a, 1 + 2 i: W_i, 2 + 2 i: s_i, 1 + 2 M: Z.  With splitmix64 of csrc/rng_hash.h and 64-bit wrap-around,
+ *   stream(seed, t, site) = splitmix64(splitmix64(splitmix64(seed) + t) + site)
+ * Step t = 0, 1, ..:
+ *   eps[e] = hash_normal(stream(seed, t, site of e), row-major index of e within its site); theta = loc + scale eps
+ *   R_i = fl(X_i - mu_i) - Z W_i' (x - mu rounded in the views' dtype, everything after it float64), D_i = R_i o exp(-2 s_i)
+ *   loss_t = -(log p(x, theta) + sum_k a_k - log q(theta)), every normalising constant included
+ *   d W_i = D_i' Z - alpha o W_i;  d Z = sum_i D_i W_i - Z;  d s_i[j] = sum_r R_i[r, j]^2 exp(-2 s_i[j]) - n - s_i[j]
+ *   d a_k = a0 - b0 alpha_k + P / 2 - alpha_k / 2 sum_{i, j} W_i[j, k]^2
+ *   d loc = d theta;  d rho = (d theta eps + 1 / scale) sigmoid(rho)
+ *   Adam on the loss (gradient -d): b1 = 0.9, b2 = 0.999, eps = 1e-8, m^ = m / (1 - b1^(t+1)), v^ = v / (1 - b2^(t+1)),
+ *   x -= lr m^ / (sqrt(v^) + eps)
+ * A step whose loss is not finite stops the fit (the parameters have taken that step); later steps are no-ops.
+ * No floating-point atomics: two fits give the same bits, whatever the chunk length. */
+
+/* Create a fit state: n_views (2..8) views of widths p[i] >= 1, n_rows (>= 2) rows, k (1..32) latent dimensions, num_steps steps
+ * in all, up to chunk_steps per ccz_svi_steps call.  Refusals come before any device work. */
+CCZ_API int ccz_svi_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t n_rows, int64_t k, int64_t num_steps,
+                           double learning_rate, uint64_t seed, int64_t chunk_steps, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op. */
+CCZ_API int ccz_svi_destroy(ccz_handle h, void* state);
+
+/* Upload the initial loc (host, float64, N entries in the flat layout) and reset rho, the moments, the losses and the status:
+ * starts a new fit on the state. */
+CCZ_API int ccz_svi_set_init(ccz_handle h, void* state, const double* loc_host);
+
+/* Enqueue n_steps (<= chunk_steps) steps.  Returns without waiting for the device; the only host wait is for the chunk that
+ * used the same status slot two calls earlier, whose state is returned in steps_known / stopped_known (-1 / 0 when there is
+ * none yet).  Views and means_dev (NULL, or NULL entries, for no centring) as for ccz_gfa_iterations. */
+CCZ_API int ccz_svi_steps(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_steps,
+                          int64_t* steps_known, int* stopped_known);
+
+/* Steps done, whether the fit has stopped (all steps done, or a non-finite loss), and the step of the non-finite loss (-1 when
+ * there was none).  Synchronises. */
+CCZ_API int ccz_svi_status(ccz_handle h, void* state, int64_t* steps, int* stopped, int64_t* bad_step);
+
+/* Copy one buffer to the host (float64) -- what the kernel tests compare with NumPy term by term.  LOC .. GRAD hold N entries
+ * in the flat layout (THETA, EPS and GRAD = d theta are those of the last step), LOSS num_steps, PLAN the planned launch of the
+ * fused kernel: row chunks, rows per chunk, strips in all, then the strips of every view.  Synchronises. */
+#define CCZ_SVI_PEEK_LOC 0
+#define CCZ_SVI_PEEK_RHO 1
+#define CCZ_SVI_PEEK_M_LOC 2
+#define CCZ_SVI_PEEK_V_LOC 3
+#define CCZ_SVI_PEEK_M_RHO 4
+#define CCZ_SVI_PEEK_V_RHO 5
+#define CCZ_SVI_PEEK_THETA 6
+#define CCZ_SVI_PEEK_EPS 7
+#define CCZ_SVI_PEEK_GRAD 8
+#define CCZ_SVI_PEEK_LOSS 9
+#define CCZ_SVI_PEEK_PLAN 10
+CCZ_API int ccz_svi_peek(ccz_handle h, void* state, int what, double* out_host);
+
+/* loc and rho (N each, flat layout) and the losses (num_steps; zero for steps not taken).  NULL outputs are skipped.
+ * Synchronises. */
+CCZ_API int ccz_svi_get_result(ccz_handle h, void* state, double* loc_host, double* rho_host, double* losses_host);
+
+/* *out_host = sum_j weights_host[j] sum_rows fl(x - mean)[row, j]^2 of one view of DEVICE rows, in float64 (mean_dev: the
+ * view's dtype, NULL for none): x' Psi^-1 x of the marginal log-likelihood with one noise variance per feature
+ * (cca_zoo/probabilistic/_utils.py:102-103).  Synchronises. */
+CCZ_API int ccz_colsumsq_weighted(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev,
+                                  const double* weights_host, double* out_host);
+
 /* ---- Khatri-Rao moment and its adjoint (tensor CCA) -------------------------------------------------------------------
  * Views are float64 DEVICE matrices H_i (n x d_i), 2..8 of them, prod d_i <= 2^24.  Tensors are row-major, the last view's
  * index fastest.  Both run on the handle's stream without a host wait and use no floating-point atomics: two calls give the
