@@ -161,6 +161,15 @@ SIGNATURES = {
     "ccz_svi_status": (_int, [_vp, _vp, _pi64, _pint, _pi64]),
     "ccz_svi_peek": (_int, [_vp, _vp, _int, _pdbl]),
     "ccz_svi_get_result": (_int, [_vp, _vp, _pdbl, _pdbl, _pdbl]),
+    "ccz_nuts_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _i64, _i64, _int, _dbl, C.c_uint64, C.POINTER(_vp)]),
+    "ccz_nuts_destroy": (_int, [_vp, _vp]),
+    "ccz_nuts_set_init": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _pdbl, _pdbl]),
+    "ccz_nuts_set_adapt": (_int, [_vp, _vp, _dbl, _pdbl]),
+    "ccz_nuts_leapfrog": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _int, _int, _i64, _int, _pdbl]),
+    "ccz_nuts_run": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pdbl]),
+    "ccz_nuts_status": (_int, [_vp, _vp, _pi64, _pint, _pi64]),
+    "ccz_nuts_peek": (_int, [_vp, _vp, _int, _pdbl]),
+    "ccz_nuts_get_stats": (_int, [_vp, _vp, _pdbl, _pdbl, _pdbl]),
     "ccz_colsumsq_weighted": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _pdbl, _pdbl]),
     "ccz_kr_moment": (_int, [_vp, C.POINTER(View), _int, _i64, _dbl, _vp]),
     "ccz_kr_apply": (_int, [_vp, C.POINTER(View), _int, _i64, _vp, _int, _dbl, _vp, _i64]),

@@ -6,20 +6,13 @@
 // and loc, rho, the four Adam moments, theta, eps and the gradient share that layout.  One step t, for M views:
 //   k_svi_draw              theta = loc + softplus(rho) eps, eps = hash_normal(stream(seed, t, site), index in the site)
 //   per view i:
-//     k_svi_fused_*         ONE read of X_i.  A tile is a strip of 256 columns x a chunk of rc rows; R = fl(x - mu) - Z W_i' is formed
-//                           per tile, scaled to D = R o exp(-2 s), and contracted both ways: D' Z summed over the chunk's rows
-//                           (one partial per row chunk), D W_i summed over the strip's columns (one partial per strip), and
-//                           sum R^2 exp(-2 s) per column (one partial per row chunk)
+//     k_svi_fused_*         ONE read of X_i (svi_fused.h, shared with nuts.hip): the row-chunk partials of D' Z and of
+//                           sum R^2 exp(-2 s), the strip partials of D W_i
 //   k_svi_adam              W, Z and s sites: the partials folded in index order, the prior terms, d loc / d rho, Adam; per-workgroup
 //                           partial sums of the loss terms and of the column sums of W^2
 //   k_svi_finish            one workgroup: the a site (its gradient needs sum W^2), loss[t], the non-finite stop
 // which is 3 + M launches.  No kernel uses floating-point atomics; every sum has a fixed order, so two fits give the same bits
 // whatever the chunk length.  Every kernel reads the status word first and returns at once when the fit has stopped.
-//
-// The fused kernel runs on v_mfma_f64_16x16x4f64 when K exceeds 4 (lane maps as in gfa.hip: A operand m = lane & 15, k = lane >> 4;
-// B operand k = lane >> 4, n = lane & 15; C/D col = lane & 15, row = (lane >> 4) + 4 reg), on plain FMAs below.  In the MFMA form
-// R is produced with its rows on the C rows and its features on the lanes, which is the A operand of D' Z as it stands; D W
-// contracts over the features, so the tile goes through LDS once to put them on the contraction index.
 //
 // Precision: x - mu is rounded in the views' precision, then widened; every product and sum is fp64.
 #include <algorithm>
@@ -33,40 +26,23 @@
 #include "reduce.h"
 #include "rng_hash.h"
 #include "row_load.h"
+#include "svi_fused.h"
 
 namespace ccz {
 
 namespace {
 
-constexpr int SVI_MAXV = 8;
-constexpr int SVI_MAXK = 32;
-constexpr int SVI_PLAIN_K = 4;          // K up to which the fused kernel runs on plain FMAs
-constexpr int SVI_SW = 256;             // columns of a strip
 constexpr int SVI_G = 1024;             // most workgroups of k_svi_adam
 constexpr int SVI_PT = 1024;            // threads of k_svi_finish
-constexpr int SVI_MAXCHUNK = 512;       // most row chunks of the fused kernel
-constexpr int64_t SVI_WANT_TILES = 8192;   // tiles (strip x row chunk) the plan aims for
 
 constexpr double SVI_A0 = 1e-3, SVI_B0 = 1e-3;       // cca_zoo/probabilistic/_vbcca.py:16-17
 constexpr double SVI_B1 = 0.9, SVI_B2 = 0.999, SVI_ADAM_EPS = 1e-8;
 constexpr double SVI_INIT_SCALE = 0.1;
 
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
 struct SviStatus {
   long long steps;        // steps done
   long long bad_step;     // the step whose loss was not finite, -1 when none
   int stopped;
-};
-
-struct SviViews {
-  const void* X[SVI_MAXV];
-  const void* mu[SVI_MAXV];
-  int64_t ld[SVI_MAXV];
-  int64_t p[SVI_MAXV];
-  int64_t off[SVI_MAXV];     // offset of view i in the concatenated rows of W and entries of s
-  int ns[SVI_MAXV];          // strips of view i
-  int soff[SVI_MAXV];        // index of its first strip among all strips
 };
 
 struct SviSeeds {
@@ -119,218 +95,6 @@ __global__ void __launch_bounds__(256) k_svi_draw(SviBuf B, SviViews vw, SviSeed
     const double ep = hash_normal(sd.s[site], uint64_t(idx));
     B.eps[e] = ep;
     B.theta[e] = B.loc[e] + svi_softplus(B.rho[e]) * ep;
-  }
-}
-
-// ---- the fused residual kernel ---------------------------------------------------------------------------------------------
-// plain: grid (ceil(ns / 4), nchunk), 256 threads; wave w owns strip 4 bx + w on its own (no workgroup barrier), lane l the four
-// columns 256 strip + 4 l .. + 3, over rows [rc by, rc (by + 1)).  wpart / s2part point at the view's first column of chunk 0,
-// zpart at the view's first strip.
-template <typename T>
-__global__ void __launch_bounds__(256) k_svi_fused_plain(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
-                                                        int rc, int K, int64_t ptot, const double* __restrict__ tw,
-                                                        const double* __restrict__ ts, const double* __restrict__ tz,
-                                                        double* __restrict__ wpart, double* __restrict__ s2part,
-                                                        double* __restrict__ zpart, const SviStatus* st) {
-  if (fit_stopped(st)) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t strip = int64_t(blockIdx.x) * 4 + wave;
-  if (strip * SVI_SW >= p) return;
-  const int64_t f0 = strip * SVI_SW + 4 * lane;
-  const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
-  const bool vec = vec_ok(X, ld, mu);
-  T m[4] = {T(0), T(0), T(0), T(0)};
-  if (mu && f0 < p) load4<T>(mu, f0, p, vec, m);
-  double w[4][SVI_PLAIN_K], acc[4][SVI_PLAIN_K], e2[4], s2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bool live = f0 + q < p;
-    e2[q] = live ? exp(-2.0 * ts[f0 + q]) : 0.0;
-    s2[q] = 0.0;
-#pragma unroll
-    for (int a = 0; a < SVI_PLAIN_K; ++a) {
-      w[q][a] = (live && a < K) ? tw[(f0 + q) * K + a] : 0.0;
-      acc[q][a] = 0.0;
-    }
-  }
-  double keep[SVI_PLAIN_K] = {0.0, 0.0, 0.0, 0.0};
-  for (int r = r0; r < r1; ++r) {
-    T x[4] = {T(0), T(0), T(0), T(0)};
-    if (f0 < p) load4<T>(X + int64_t(r) * ld, f0, p, vec, x);
-    double zr[SVI_PLAIN_K], t[SVI_PLAIN_K];
-#pragma unroll
-    for (int a = 0; a < SVI_PLAIN_K; ++a) {
-      zr[a] = a < K ? tz[int64_t(r) * K + a] : 0.0;
-      t[a] = 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      double R = f0 + q < p ? double(T(x[q] - m[q])) : 0.0;
-#pragma unroll
-      for (int a = 0; a < SVI_PLAIN_K; ++a) R -= zr[a] * w[q][a];
-      const double D = R * e2[q];
-      s2[q] += R * D;
-#pragma unroll
-      for (int a = 0; a < SVI_PLAIN_K; ++a) {
-        acc[q][a] += D * zr[a];
-        t[a] += D * w[q][a];
-      }
-    }
-    const int slot = (r - r0) & 63;
-#pragma unroll
-    for (int a = 0; a < SVI_PLAIN_K; ++a)
-      if (a < K) {
-        const double s = wave_sum(t[a]);
-        if (lane == slot) keep[a] = s;
-      }
-    if (slot == 63 || r == r1 - 1) {     // the wave's last 64 rows (or fewer), one row per lane
-      const int rr = r - slot + lane;
-      if (rr <= r)
-#pragma unroll
-        for (int a = 0; a < SVI_PLAIN_K; ++a)
-          if (a < K) zpart[(strip * n + rr) * K + a] = keep[a];
-    }
-  }
-  double* wout = wpart + int64_t(blockIdx.y) * ptot * K;
-  double* sout = s2part + int64_t(blockIdx.y) * ptot;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (f0 + q < p) {
-      sout[f0 + q] = s2[q];
-#pragma unroll
-      for (int a = 0; a < SVI_PLAIN_K; ++a)
-        if (a < K) wout[(f0 + q) * K + a] = acc[q][a];
-    }
-}
-
-// MFMA: grid (ns, nchunk), 256 threads; the workgroup owns strip bx, wave w its features 256 bx + 64 w .. + 63 as four groups q of 16:
-// feature index i of group q is feature 4 i + q of the wave (a lane loads 4 consecutive features).  Rows go 16 at a time.
-//   R_q (16 rows x 16 features) = x - Z W_q'          A = Z (m: row, k: latent), B = W_q' (k: latent, n: feature); ceil(K / 4) MFMAs
-//   dW_q (16 features x 16 latent) += D_q' Z           A = D_q as the C registers hold it (m: feature = lane & 15, k: row), B = Z
-//   dZ (16 rows x 16 latent) += D_q W_q                A = D_q read back from LDS (m: row, k: feature), B = W_q
-// the four waves' dZ are summed in wave order through LDS and written once per 16 rows.
-template <typename T, int KT>
-__global__ void __launch_bounds__(256) k_svi_fused_mfma(const T* __restrict__ X, const T* __restrict__ mu, int64_t ld, int64_t p, int n,
-                                                       int rc, int K, int64_t ptot, const double* __restrict__ tw,
-                                                       const double* __restrict__ ts, const double* __restrict__ tz,
-                                                       double* __restrict__ wpart, double* __restrict__ s2part,
-                                                       double* __restrict__ zpart, const SviStatus* st) {
-  if (fit_stopped(st)) return;
-  __shared__ double dt[4][4][16][17];
-  __shared__ double red[4][16][16 * KT + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 15, lg = lane >> 4;
-  const int64_t strip = blockIdx.x;
-  const int64_t fw = strip * SVI_SW + 64 * wave;
-  const int64_t f0 = fw + 4 * li;
-  const int r0 = blockIdx.y * rc, r1 = min(n, r0 + rc);
-  const bool vec = vec_ok(X, ld, mu);
-  T m[4] = {T(0), T(0), T(0), T(0)};
-  if (mu && f0 < p) load4<T>(mu, f0, p, vec, m);
-  double wb[4][4 * KT];        // B operand of R: W[feature 4 li + q][latent lg + 4 j]
-  double wa[4][4][KT];         // B operand of dZ: W[feature 4 (lg + 4 jp) + q][latent 16 kt + li]
-  double e2[4], s2[4];
-  v4f64 acc[4][KT];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bool live = f0 + q < p;
-    e2[q] = live ? exp(-2.0 * ts[f0 + q]) : 0.0;
-    s2[q] = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4 * KT; ++j) wb[q][j] = (live && lg + 4 * j < K) ? tw[(f0 + q) * K + lg + 4 * j] : 0.0;
-#pragma unroll
-    for (int jp = 0; jp < 4; ++jp) {
-      const int64_t f = fw + 4 * (lg + 4 * jp) + q;
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) wa[q][jp][kt] = (f < p && 16 * kt + li < K) ? tw[f * K + 16 * kt + li] : 0.0;
-    }
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) acc[q][kt] = v4f64{0.0, 0.0, 0.0, 0.0};
-  }
-  for (int rb = r0; rb < r1; rb += 16) {
-    v4f64 C[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) C[q] = v4f64{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 4 * KT; ++j) {
-      if (4 * j >= K) break;
-      const double za = (rb + li < r1 && lg + 4 * j < K) ? tz[int64_t(rb + li) * K + lg + 4 * j] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) C[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(za, wb[q][j], C[q], 0, 0, 0);
-    }
-    double D[4][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row = rb + lg + 4 * g;
-      const bool live = row < r1;
-      T x[4] = {T(0), T(0), T(0), T(0)};
-      if (live && f0 < p) load4<T>(X + int64_t(row) * ld, f0, p, vec, x);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double R = (live && f0 + q < p) ? double(T(x[q] - m[q])) - C[q][g] : 0.0;
-        D[q][g] = R * e2[q];
-        s2[q] += R * D[q][g];
-      }
-    }
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-      if (16 * kt >= K) break;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int row = rb + lg + 4 * g;
-        const double zb = (row < r1 && 16 * kt + li < K) ? tz[int64_t(row) * K + 16 * kt + li] : 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q][kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[q][g], zb, acc[q][kt], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) dt[wave][q][lg + 4 * g][li] = D[q][g];
-    __syncthreads();
-    v4f64 dz[KT];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) dz[kt] = v4f64{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int jp = 0; jp < 4; ++jp) {
-        const double da = dt[wave][q][li][lg + 4 * jp];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          if (16 * kt >= K) break;
-          dz[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(da, wa[q][jp][kt], dz[kt], 0, 0, 0);
-        }
-      }
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) red[wave][lg + 4 * g][16 * kt + li] = dz[kt][g];
-    __syncthreads();
-    for (int e = threadIdx.x; e < 16 * 16 * KT; e += 256) {
-      const int rr = e / (16 * KT), col = e % (16 * KT);
-      const int row = rb + rr;
-      if (row < r1 && col < K) zpart[(strip * n + row) * K + col] = ((red[0][rr][col] + red[1][rr][col]) + red[2][rr][col]) + red[3][rr][col];
-    }
-  }
-  double* wout = wpart + int64_t(blockIdx.y) * ptot * K;
-  double* sout = s2part + int64_t(blockIdx.y) * ptot;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    double v = s2[q];
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    if (lg == 0 && f0 + q < p) sout[f0 + q] = v;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-      const int col = 16 * kt + li;
-      if (col >= K) continue;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int64_t f = fw + 4 * (lg + 4 * g) + q;
-        if (f < p) wout[f * K + col] = acc[q][kt][g];
-      }
-    }
   }
 }
 
@@ -503,33 +267,6 @@ SviViews make_views(const SviState& S, const ccz_view* views, const void* const*
   return vw;
 }
 
-template <typename T>
-void launch_fused(ccz_ctx* c, const SviState& S, const SviViews& vw, int i) {
-  const SviBuf& B = S.B;
-  const T* X = static_cast<const T*>(vw.X[i]);
-  const T* mu = static_cast<const T*>(vw.mu[i]);
-  const double* tw = B.theta + B.oW + vw.off[i] * B.K;
-  const double* ts = B.theta + B.oS + vw.off[i];
-  const double* tz = B.theta + B.oZ;
-  double* wpart = B.wpart + vw.off[i] * B.K;
-  double* s2part = B.s2part + vw.off[i];
-  double* zpart = B.zpart + int64_t(vw.soff[i]) * B.n * B.K;
-  if (S.K <= SVI_PLAIN_K) {
-    const dim3 grid(unsigned((vw.ns[i] + 3) / 4), unsigned(B.nchunk));
-    hipLaunchKernelGGL((k_svi_fused_plain<T>), grid, dim3(256), 0, stream(c), X, mu, vw.ld[i], vw.p[i], B.n, B.rc, B.K, B.ptot, tw, ts, tz, wpart,
-                       s2part, zpart, S.drv.dev);
-  } else {
-    const dim3 grid(unsigned(vw.ns[i]), unsigned(B.nchunk));
-    if (S.K <= 16)
-      hipLaunchKernelGGL((k_svi_fused_mfma<T, 1>), grid, dim3(256), 0, stream(c), X, mu, vw.ld[i], vw.p[i], B.n, B.rc, B.K, B.ptot, tw, ts, tz,
-                         wpart, s2part, zpart, S.drv.dev);
-    else
-      hipLaunchKernelGGL((k_svi_fused_mfma<T, 2>), grid, dim3(256), 0, stream(c), X, mu, vw.ld[i], vw.p[i], B.n, B.rc, B.K, B.ptot, tw, ts, tz,
-                         wpart, s2part, zpart, S.drv.dev);
-  }
-  CCZ_LAUNCH_CHECK();
-}
-
 void enqueue_step(ccz_ctx* c, const SviState& S, const SviViews& vw, long long step) {
   const SviBuf& B = S.B;
   SviSeeds sd;
@@ -541,7 +278,11 @@ void enqueue_step(ccz_ctx* c, const SviState& S, const SviViews& vw, long long s
   const int gd = int(std::max<int64_t>(1, std::min<int64_t>(4096, (B.N + 1023) / 1024)));
   hipLaunchKernelGGL(k_svi_draw, dim3(gd), dim3(256), 0, stream(c), B, vw, sd, S.drv.dev);
   CCZ_LAUNCH_CHECK();
-  for (int i = 0; i < S.M; ++i) by_dtype(S.dtype, [&](auto t) { launch_fused<decltype(t)>(c, S, vw, i); });
+  const FusedPlan P{B.ptot, B.n, B.K, B.nchunk, B.rc, B.NS};
+  for (int i = 0; i < S.M; ++i)
+    by_dtype(S.dtype, [&](auto t) {
+      launch_fused<decltype(t)>(c, P, vw, i, B.theta + B.oW, B.theta + B.oS, B.theta + B.oZ, B.wpart, B.s2part, B.zpart, S.drv.dev);
+    });
   hipLaunchKernelGGL(k_svi_adam, dim3(B.gadam), dim3(256), 0, stream(c), B, ad, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_svi_finish, dim3(1), dim3(SVI_PT), 0, stream(c), B, ad, step, S.drv.dev);
@@ -563,23 +304,9 @@ SviState* svi_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
     memset(&B, 0, sizeof(B));
     memset(&S.shape, 0, sizeof(S.shape));
     B.n = int(n); B.M = M; B.K = int(k); B.total = num_steps; B.lr = lr;
-    for (int i = 0; i < M; ++i) {
-      SviViews& sh = S.shape;
-      sh.p[i] = p[i];
-      sh.off[i] = B.ptot;
-      B.ptot += p[i];
-      sh.ns[i] = int((p[i] + SVI_SW - 1) / SVI_SW);
-      sh.soff[i] = B.NS;
-      B.NS += sh.ns[i];
-    }
-    if (B.ptot > (int64_t(1) << 31)) fail(CCZ_EUNSUP, "svi: at most 2^31 columns in all");
-    // row chunks: enough tiles to fill the device; a chunk holds a multiple of 16 rows and at least 4 K, which keeps the
-    // D' Z partials (nchunk x ptot x K doubles) at or below 2 n ptot bytes
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(SVI_MAXCHUNK, (SVI_WANT_TILES + B.NS - 1) / B.NS));
-    int64_t rc = std::max<int64_t>((n + want - 1) / want, std::max<int64_t>(16, 4 * k));
-    rc = (rc + 15) / 16 * 16;
-    B.rc = int(rc);
-    B.nchunk = int((n + rc - 1) / rc);
+    FusedPlan P;
+    fused_plan("svi", M, p, n, k, S.shape, P);
+    B.ptot = P.ptot; B.NS = P.NS; B.rc = P.rc; B.nchunk = P.nchunk;
     B.N = k + B.ptot * k + B.ptot + n * k;
     B.oW = k; B.oS = k + B.ptot * k; B.oZ = B.oS + B.ptot;
     B.gadam = int(std::max<int64_t>(1, std::min<int64_t>(SVI_G, (std::max<int64_t>(B.ptot, n) * k + 255) / 256)));

@@ -16,12 +16,10 @@ from typing import Any, ClassVar
 
 import numpy as np
 from sklearn.utils._param_validation import Interval
-from sklearn.utils.validation import check_is_fitted
 
 from cca_zoo_amd._base import BaseModel
-from cca_zoo_amd._utils._resident import (MEANS_COLMEANS, MEANS_TORCH, ResidentViews, check_limits, fit_state,
-                                           refuse_row_sharded, run_chunks)
-from cca_zoo_amd._utils._validation import validate_views
+from cca_zoo_amd._utils._resident import (MEANS_COLMEANS, ResidentViews, check_limits, fit_state, refuse_row_sharded,
+                                           run_chunks)
 from cca_zoo_amd.probabilistic._posterior import PosteriorMeanMixin
 
 #: steps per ``ccz_svi_steps`` call: one host wait (for the chunk two calls back) per chunk; the result does not depend on it
@@ -192,26 +190,4 @@ class VariationalBayesCCA(PosteriorMeanMixin, BaseModel):
         out.append(("z", (n, k), slice(o_z, o_z + n * k)))
         return out
 
-    # -- after the fit (transform, the correlations' variates: PosteriorMeanMixin) ---------------------------------
-    def log_likelihood(self, views) -> float:
-        """Mean per-sample marginal log-likelihood with ``z`` integrated out (``_utils.py:51-109``).  The noise variance
-        differs per feature, so ``x' Psi^-1 x`` is ``sum_j sum_rows fl(x - mean)^2 / psi_j`` per view (one device pass,
-        ``ccz_colsumsq_weighted``) and the Woodbury correction the ``n x k`` projection; no ``n x P`` array is formed."""
-        check_is_fitted(self)
-        validated = validate_views(views, check_finite=False)
-        psi, psi_inv = self._psi_inv()
-        n = int(validated[0].shape[0])
-        quad_diag = 0.0
-        pd = C.POINTER(C.c_double)
-        res = ResidentViews(validated, False, MEANS_TORCH)
-        with res:
-            h = res.handle
-            dt = np.float32 if res.f32 else np.float64
-            for i in range(self.n_views_):
-                mu = h.to_device(np.asarray(self.means_[i], dtype=dt)) if self.center else None
-                wt = np.ascontiguousarray(psi_inv[i], dtype=np.float64)
-                out = C.c_double(0.0)
-                h.check(h.lib.ccz_colsumsq_weighted(h.raw, res.code, C.byref(res.varr[i]), n, C.c_void_p(mu.ptr if mu else None),
-                                                    wt.ctypes.data_as(pd), C.byref(out)))
-                quad_diag += out.value
-        return self._woodbury_log_likelihood(validated, psi, psi_inv, quad_diag)
+    # -- after the fit: transform, the correlations' variates and log_likelihood come from PosteriorMeanMixin

@@ -744,6 +744,110 @@ CCZ_API int ccz_svi_get_result(ccz_handle h, void* state, double* loc_host, doub
 CCZ_API int ccz_colsumsq_weighted(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, const void* mean_dev,
                                   const double* weights_host, double* out_host);
 
+/* ---- ProbabilisticCCA: the No-U-Turn sampler (csrc/nuts.hip) ------------------------------------------------------------------
+ * Whole leapfrog steps on the device; the tree and the adaptation scalars on the host, which reads one small record per
+ * leapfrog (the tree is data-dependent).  The model is that of cca_zoo/probabilistic/_pcca.py:90-131; the reference samples it
+ * with numpyro (NUTS, MCMC with their defaults), which this library cannot call, so the sampler is written out here and
+ * restated in NumPy in tests/pcca_restatement.py, which is the specification.  These are NOT numpyro's bits: the random
+ * numbers are this library's.
+ *
+ * Model (VariationalBayesCCA's without the ARD site), K latent dimensions, M views of p_i columns, n rows, P = sum p_i:
+ *   W_i[j, k] ~ N(0, 1);  s_i = log psi_i, s_i[j] ~ N(0, 1);  Z[r, k] ~ N(0, 1)
+ *   x_i[r, j] ~ N((Z W_i')[r, j], exp(s_i[j])): exp(s) is the STANDARD DEVIATION of the likelihood, as in the reference.
+ * State: one flat vector of N = P K + P + n K doubles, q = [ W_0 .. W_{M-1} (row-major, back to back) | s_0 .. s_{M-1} |
+ * Z (row-major) ]; the momentum p, the gradient g, minv and the Welford vectors all use it.
+ * Potential, every normalising constant included, with R_i = fl(X_i - mu_i) - Z W_i' (x - mu rounded in the views' dtype,
+ * everything after it float64) and D_i = R_i o exp(-2 s_i):
+ *   U = |W|^2 / 2 + |s|^2 / 2 + |Z|^2 / 2 + sum_ij (n s_ij + exp(-2 s_ij) sum_r R_rj^2 / 2) + log(2 pi) (N + n P) / 2
+ *   dU/dW_i = W_i - D_i' Z;  dU/dZ = Z - sum_i D_i W_i;  dU/ds_ij = s_ij + n - exp(-2 s_ij) sum_r R_rj^2
+ * Leapfrog with the diagonal inverse mass minv (initially 1) and the step eps (negative: backwards in time):
+ *   p -= (eps / 2) g;  q += eps minv o p;  g = dU(q);  p -= (eps / 2) g;  kinetic energy sum minv p^2 / 2
+ * Sites are numbered 2 i: W_i, 2 i + 1: s_i, 2 M: Z, and 2 M + 1 is the tree's stream.  With splitmix64 / hash_normal of
+ * csrc/rng_hash.h, stream(seed, t, site) = splitmix64(splitmix64(splitmix64(seed) + t) + site) as for ccz_svi_*:
+ *   p[e] = hash_normal(stream(seed, t, site of e), row-major index of e within its site) / sqrt(minv[e])
+ *   u_j = (splitmix64(stream(seed, t, 2 M + 1) ^ splitmix64(j)) >> 11) 2^-53, used in order: the direction coin of a doubling
+ *   (u < 1/2: forwards), the selections of its leaves 1 .., the tree's selection
+ * Transition t: multinomial NUTS, built iteratively.  H0 = U + kinetic at the start.  A doubling at depth d adds 2^d leaves at
+ * one end; leaf i: one leapfrog; dH = H - H0 (NaN is +inf); statistic min(1, exp(-dH)); dH > 1000 is a divergence and ends the
+ * transition; the subtree's proposal is leaf 0, then leaf i with probability w_i / (w_before + w_i), w = exp(-dH); rsum += p;
+ * an even leaf is checkpoint c = popcount(i >> 1), keeping (p, rsum); an odd leaf closes one subtree per trailing one-bit of i
+ * (checkpoints c, c - 1, ..): rho = rsum - rsum_c + p_c, rho~ = rho - (p_c + p) / 2, turning when (minv o p_c) . rho~ <= 0 or
+ * (minv o p) . rho~ <= 0, which ends the transition.  A whole subtree: the tree takes its proposal with probability
+ * min(1, w_sub / w_tree), w_tree += w_sub, rho_tree += rsum, and the whole tree is tested the same way with its two ends'
+ * momenta; up to max_tree_depth doublings.  accept_prob is the mean statistic of all leaves.
+ * Warm-up: dual averaging of log eps (t0 = 10, kappa = 0.75, gamma = 0.05, mu = log(10 eps), eps_0 = 1, no step-size
+ * heuristic); Stan's windows as numpyro builds them (below 20 transitions one window; else 75 / 50 / 25 doubling, or
+ * 15 % / 10 % / the rest); in the MIDDLE windows a Welford mean / M2 of q, and at such a window's end (count c)
+ * minv = (c / (c + 5)) M2 / (c - 1) + 1e-3 (5 / (c + 5)), the Welford state reset, dual averaging restarted at
+ * mu = log(10 eps); after the last warm-up transition eps = exp(averaged log eps).
+ * No floating-point atomics: two fits give the same bits.  A leapfrog is M + 3 launches.
+ * Limits: 2..8 views, k 1..32, n_rows >= 2, max_tree_depth 1..10, and the 15 + 2 max_tree_depth slots of N doubles may not
+ * exceed 2^33 doubles (64 GiB): CCZ_EUNSUP before any device work. */
+
+/* Create a fit state.  Refusals come before any device work. */
+CCZ_API int ccz_nuts_create(ccz_handle h, int dtype, int n_views, const int64_t* p, int64_t n_rows, int64_t k, int64_t num_warmup,
+                            int64_t num_samples, int max_tree_depth, double target_accept_prob, uint64_t seed, void** state_out);
+
+/* Free a fit state (synchronises the handle's stream).  NULL is a no-op. */
+CCZ_API int ccz_nuts_destroy(ccz_handle h, void* state);
+
+/* Upload the initial point q (host, float64, N entries), evaluate U and g there and reset the chain (eps = 1, minv = 1, no
+ * transitions done).  *potential_out = U; when U is not finite the fit is stopped (every kernel becomes a no-op,
+ * ccz_nuts_run refuses) and *potential_out is NaN.  Views and means_dev as for ccz_svi_steps.  Synchronises. */
+CCZ_API int ccz_nuts_set_init(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, const double* q_host,
+                              double* potential_out);
+
+/* Test seam: set eps (dual averaging restarts from it) and, unless NULL, minv (host, N entries). */
+CCZ_API int ccz_nuts_set_adapt(ccz_handle h, void* state, double step_size, const double* minv_host);
+
+/* Test seam: leaf `leaf` (0 .. 2^depth - 1) of a doubling at `depth` in `direction` (+1: the right end forwards, -1: the left
+ * end backwards), as ccz_nuts_run would take it; with `begin` the momentum of `transition` is drawn first (both ends = the
+ * chain's point).  Every intermediate stays in its slot for ccz_nuts_peek.  record_host (27 doubles): U, kinetic, H, the
+ * dots (2 l, 2 l + 1: the l-th closed subtree, smallest first; 20, 21: the whole tree), finite, the kinetic energy of the
+ * drawn momentum (0 without `begin`).  Dots of tests the leaf does not close are 0.  Synchronises. */
+CCZ_API int ccz_nuts_leapfrog(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t transition,
+                              int begin, int direction, int64_t leaf, int depth, double* record_host);
+
+/* Run the next n_transitions (warm-up first, with its adaptation).  The q of kept draw d (transition num_warmup + d) is
+ * written to draws_host + d N as its transition ends (NULL: not fetched).  Synchronises. */
+CCZ_API int ccz_nuts_run(ccz_handle h, void* state, const ccz_view* views, const void* const* means_dev, int64_t n_transitions,
+                         double* draws_host);
+
+/* Transitions done, whether the fit has stopped (a non-finite initial potential: bad = 0, else -1).  Synchronises. */
+CCZ_API int ccz_nuts_status(ccz_handle h, void* state, int64_t* transitions, int* stopped, int64_t* bad);
+
+/* Copy one slot (N doubles) or one small table to the host -- what the kernel tests compare with NumPy term by term.
+ * Slots: the tree's left / right end q, p, g; the chain's point q, g; the subtree's proposal q, g; the momentum sum of the
+ * tree and of the subtree; minv; the Welford mean and M2; checkpoint c at CKPT + 2 c (p) and CKPT + 2 c + 1 (sum).
+ * PLAN: row chunks, rows per chunk, strips in all, workgroups of the passes over N, slots, then the strips of every view.
+ * RECORD: the last record (26 doubles, as ccz_nuts_leapfrog).  SCALARS: U of the chain's point, eps, the Welford count, the
+ * window index.  PLAN is known from ccz_nuts_create on; the rest needs ccz_nuts_set_init.  Synchronises. */
+#define CCZ_NUTS_PEEK_LEFT_Q 0
+#define CCZ_NUTS_PEEK_LEFT_P 1
+#define CCZ_NUTS_PEEK_LEFT_G 2
+#define CCZ_NUTS_PEEK_RIGHT_Q 3
+#define CCZ_NUTS_PEEK_RIGHT_P 4
+#define CCZ_NUTS_PEEK_RIGHT_G 5
+#define CCZ_NUTS_PEEK_Q 6
+#define CCZ_NUTS_PEEK_G 7
+#define CCZ_NUTS_PEEK_SUB_Q 8
+#define CCZ_NUTS_PEEK_SUB_G 9
+#define CCZ_NUTS_PEEK_RHO 10
+#define CCZ_NUTS_PEEK_RSUM 11
+#define CCZ_NUTS_PEEK_MINV 12
+#define CCZ_NUTS_PEEK_WELFORD_MEAN 13
+#define CCZ_NUTS_PEEK_WELFORD_M2 14
+#define CCZ_NUTS_PEEK_CKPT 15
+#define CCZ_NUTS_PEEK_PLAN 100
+#define CCZ_NUTS_PEEK_RECORD 101
+#define CCZ_NUTS_PEEK_SCALARS 102
+CCZ_API int ccz_nuts_peek(ccz_handle h, void* state, int what, double* out_host);
+
+/* Per transition done so far (T of them, warm-up included), six arrays of T doubles back to back: tree_depth, n_leapfrog,
+ * accept_prob, diverging, potential_energy, step_size (the one the transition used); the current step size; minv (N).
+ * NULL outputs are skipped.  Synchronises. */
+CCZ_API int ccz_nuts_get_stats(ccz_handle h, void* state, double* stats_host, double* step_size, double* minv_host);
+
 /* ---- Khatri-Rao moment and its adjoint (tensor CCA) -------------------------------------------------------------------
  * Views are float64 DEVICE matrices H_i (n x d_i), 2..8 of them, prod d_i <= 2^24.  Tensors are row-major, the last view's
  * index fastest.  Both run on the handle's stream without a host wait and use no floating-point atomics: two calls give the
