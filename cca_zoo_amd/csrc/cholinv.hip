@@ -12,8 +12,8 @@
 //                A_ik -= L_ij L_kj'  (3 x 64^3 MFMA flops instead of 1: the panel solve needs no launch of its own
 //                and no workgroup waits for another);
 //              * the workgroup that owns tile (j+1, j+1) goes straight on to factor it (LOOK-AHEAD: one wave,
-//                shift-register recurrence, Newton rsqrt instead of sqrt + divide, reciprocal diagonal kept for
-//                the inverse) and publishes L_(j+1)(j+1) and T_(j+1) for the next launch;
+//                16-column panels on the matrix pipe, rsqrt seed + one third-order step instead of sqrt + divide,
+//                reciprocal diagonal kept for the inverse) and publishes L_(j+1)(j+1) and T_(j+1) for the next launch;
 //              * row j of X = L^-1 is formed from the rows above it:  X_jk = -T_j' sum_{t=k}^{j-1} L_jt X_tk.
 //
 // so a d x d factor + inverse costs d / 64 + 1 launches whose critical path is the diagonal recurrence alone.
@@ -139,37 +139,15 @@ __device__ __forceinline__ void load_tile_shared(double* dst, const double* src,
   store_tile<TRANS>(dst, t, tid);
 }
 
-// ---------------------------------------------------------------------------
-// One wavefront factors the 64 x 64 SPD tile held in `Xs` (row-major, stride CLD, identity-padded beyond the valid
-// size) and forms the inverse of the factor:
-//   Ls[t * CLD + i] = L[i][t]            (column-major factor, left in LDS)
-//   Xs[c * CLD + t] = (L^-T)[c][t]       (row-major L^-T)
-// Lane i owns row i of the current Schur complement in 64 registers used as a SHIFT REGISTER (step j reads column
-// j from a[0] and writes the updated row one register down: all register indices are compile-time constants while
-// j is a run-time counter); the multipliers come back as wave-uniform LDS broadcasts.  1 / sqrt(pivot) is a
-// v_rsq_f64 seed + two Newton steps (no IEEE sqrt / divide chains on the critical path); it is also 1 / L_jj, which
-// the forward substitution of the inverse phase multiplies by instead of dividing.  Returns the first non-positive
-// pivot (0-based) or 0x7fffffff.
-// ---------------------------------------------------------------------------
 __device__ __forceinline__ double bcast_lane(double v, int src) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
   return __hiloint2double(hi, lo);
 }
 
-__device__ __forceinline__ double rsqrt_newton(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const double e = __builtin_fma(-x * y, y, 1.0);       // 1 - x y^2
-    y = __builtin_fma(0.5 * y, e, y);
-  }
-  return y;
-}
-
 // v_rsq_f64 seed + ONE third-order step (y (1 + e/2 + 3 e^2/8), e = 1 - x y^2): five dependent operations instead of
-// the seven of two Newton steps -- a dependent fp64 operation costs 32 cycles on this chip (profiles/r02c_clock_probe.md)
-// and this is the pivot chain of every 64 x 64 block.  Relative error ~ (5/16) e0^3 with e0 the seed's (~2^-26): rounding.
+// the seven of two Newton steps -- this is the pivot chain of every 64 x 64 block (chol_panel16 spells the step out so that
+// 1 / pivot comes from the same seed).  Relative error ~ (5/16) e0^3 with e0 the seed's (~2^-26): rounding.
 __device__ __forceinline__ double rsqrt_cubic(double x) {
   const double y0 = __builtin_amdgcn_rsq(x);
   const double t = x * y0;
@@ -177,96 +155,6 @@ __device__ __forceinline__ double rsqrt_cubic(double x) {
   const double p = __builtin_fma(e, 0.375, 0.5);
   const double q = y0 * e;
   return __builtin_fma(q, p, y0);
-}
-
-// 16-byte reads of a buffer that is written through plain `double` lvalues: may_alias, or type-based alias analysis
-// may reorder / forward across the two access types
-typedef double v2f64 __attribute__((ext_vector_type(2), may_alias));
-
-// The multipliers of a step are 63 wave-uniform doubles from one LDS column: read as 32 ds_read_b128 (the column
-// starts at byte 528 j: 16-byte aligned) -- a single wave issues narrow LDS reads at a fifth of the array rate and the
-// 63 ds_read_b64 of the first version were the critical path (1000 cycles per pivot).
-// `progress` (LDS): number of finished columns, published with workgroup-scope release after the column and its
-// reciprocal diagonal are in LDS; the inverse wave consumes column t as soon as progress > t.
-template <int KMAX>
-__device__ __forceinline__ void cf_chol_steps(double (&a)[CB], int j_begin, int j_end, int lane, double* Ls, double* Rd, int* progress,
-                                              int& first_bad) {
-#pragma unroll 1
-  for (int j = j_begin; j < j_end; ++j) {
-    const double col = a[0];
-    double piv = bcast_lane(col, j);
-    const bool bad = !(piv > 0.0);                 // wave-uniform; NaN counts as bad
-    first_bad = bad ? min(first_bad, j) : first_bad;
-    piv = bad ? 1.0 : piv;
-    const double rs = rsqrt_newton(piv);
-    const double l = col * rs;                     // lanes >= j: L[lane][j]; lanes < j hold junk that nobody reads
-    double* lcol = Ls + j * CLD;
-    lcol[lane] = lane >= j ? l : 0.0;
-    if (lane == 0) Rd[j] = rs;                     // 1 / L_jj
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(progress, j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const v2f64* lrow2 = reinterpret_cast<const v2f64*>(Ls) + j * (CLD + 1) / 2;   // &Ls[j * CLD + j], (CLD + 1) j / 2 pairs
-    // reads past row 63 land in the slack behind the tile and only feed junk registers
-#pragma unroll
-    for (int p = 0; p <= KMAX / 2; ++p) {
-      const v2f64 m = lrow2[p];
-      if (2 * p >= 1 && 2 * p <= KMAX) a[2 * p - 1] = a[2 * p] - l * m[0];
-      if (2 * p + 1 <= KMAX) a[2 * p] = a[2 * p + 1] - l * m[1];
-      if ((p & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <int KMAX>
-__device__ __forceinline__ void cf_inv_steps(double (&v)[CB], int t_begin, int t_end, int lane, const double* Ls, const double* Rd,
-                                             int* progress, double* Xs) {
-#pragma unroll 1
-  for (int t = t_begin; t < t_end; ++t) {
-    // wait until the factorization wave has published column t (uniform branch: lane 0 polls, everyone follows)
-    while (__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) <= t) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const v2f64* lcol2 = reinterpret_cast<const v2f64*>(Ls) + t * (CLD + 1) / 2;    // &Ls[t * CLD + t]: L[t][t], L[t+1][t], ...
-    const double x = v[0] * Rd[t];
-    Xs[lane * CLD + t] = x;                        // (L^-1)[t][lane] = (L^-T)[lane][t]
-#pragma unroll
-    for (int p = 0; p <= KMAX / 2; ++p) {
-      const v2f64 m = lcol2[p];
-      if (2 * p >= 1 && 2 * p <= KMAX) v[2 * p - 1] = v[2 * p] - m[0] * x;
-      if (2 * p + 1 <= KMAX) v[2 * p] = v[2 * p + 1] - m[1] * x;
-      if ((p & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// Waves 0 and 1 of the calling workgroup (tid < 128), after a __syncthreads() that made the input tile `In`
-// (row-major, stride CLD, identity-padded) visible and with *progress == 0:
-//   wave 0: Cholesky recurrence, columns into Ls[t * CLD + i] = L[i][t], reciprocal diagonal into Rd
-//   wave 1: forward substitution L x = e_c for all 64 right-hand sides at once, one step behind wave 0,
-//           Xs[c * CLD + t] = (L^-T)[c][t]
-// Returns (wave 0) the first non-positive pivot (0-based) or 0x7fffffff.
-__device__ __forceinline__ int wave_factor_lds(double* Ls, const double* In, double* Xs, double* Rd, int* progress, int tid) {
-  const int lane = tid & 63;
-  int first_bad = 0x7fffffff;
-  if (tid < 64) {
-    double a[CB];
-#pragma unroll
-    for (int k = 0; k < CB; ++k) a[k] = In[lane * CLD + k];
-    cf_chol_steps<63>(a, 0, 16, lane, Ls, Rd, progress, first_bad);
-    cf_chol_steps<47>(a, 16, 32, lane, Ls, Rd, progress, first_bad);
-    cf_chol_steps<31>(a, 32, 48, lane, Ls, Rd, progress, first_bad);
-    cf_chol_steps<15>(a, 48, 64, lane, Ls, Rd, progress, first_bad);
-  } else {
-    double v[CB];
-#pragma unroll
-    for (int k = 0; k < CB; ++k) v[k] = (k == lane) ? 1.0 : 0.0;
-    cf_inv_steps<63>(v, 0, 16, lane, Ls, Rd, progress, Xs);
-    cf_inv_steps<47>(v, 16, 32, lane, Ls, Rd, progress, Xs);
-    cf_inv_steps<31>(v, 32, 48, lane, Ls, Rd, progress, Xs);
-    cf_inv_steps<15>(v, 48, 64, lane, Ls, Rd, progress, Xs);
-  }
-  return first_bad;
 }
 
 constexpr int CMAXB = 8;
@@ -281,116 +169,29 @@ struct CholInvBatch {
   int inv_only;           // 1: L and T are given; only the rows of X = L^-1 are formed (no trailing updates)
 };
 
-// ---------------------------------------------------------------------------
-// MFMA form of the 64 x 64 factorization (default).  The shift-register recurrence above spends ~1000 cycles per
-// pivot on the rank-1 update (63 FMAs + 32 wave-uniform LDS reads issued by ONE wave); here the Schur complement
-// lives in v_mfma_f64_16x16x4_f64 accumulators (10 lower 16 x 16 tiles, 40 registers) and is updated once per
-// PANEL of four pivots by <= 10 MFMAs; only the 4-column panel itself goes through the scalar recurrence
-// (lane = row: four values per lane, multipliers by v_readlane, no LDS on the pivot chain):
-//   per panel:  panel columns accumulators -> LDS (64 x 4)  ->  4 pivots in registers  ->  L panel -> LDS
-//               ->  four ds_read_b64 give the A (and, by symmetry, B) fragments  ->  acc[ti][tj] -= L_ti L_tj'
-// All 16 panels are unrolled (every register / lane index is a constant).
-// The inverse is blocked as well: the four 16 x 16 diagonal blocks are inverted by substitution (one wave each, 16
-// steps), the six blocks below the diagonal follow from 16 x 16 MFMA products, column j on wave j:
-//   X_ij = -X_ii sum_{t=j}^{i-1} L_it X_tj
-// ---------------------------------------------------------------------------
 // Lanes of ONE wave exchange data through LDS below.  LDS operations of a wave execute in order, but the COMPILER
 // reasons per thread: without a fence it forwards a thread's own earlier store to its later load of the same address
-// even though another lane has overwritten it in between (first version of chol_panel: rows 8..15 of every panel
-// kept the previous panel's values).  A wavefront-scope release/acquire pair is the (free) way to say "shared".
+// even though another lane has overwritten it in between (a panel then keeps rows of the previous panel's values).
+// A wavefront-scope release/acquire pair is the (free) way to say "shared".
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int Q>
-__device__ __forceinline__ void chol_panel(v4f64 (&acc)[4][4], int lane, double* Ls, double* Rd, double* PL, int& first_bad) {
-  constexpr int C0 = 4 * Q, TJ0 = Q / 4, CL = C0 % 16;
-  // 1. the panel's four columns of the Schur complement: accumulators -> PL[row][0..3]
-  const int pc = (lane & 15) - CL;
-  if (pc >= 0 && pc < 4) {
-#pragma unroll
-    for (int ti = TJ0; ti < 4; ++ti)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) PL[(16 * ti + (lane >> 4) + 4 * r) * 4 + pc] = acc[ti][TJ0][r];
-  }
-  wave_lds_sync();
-  // 2. lane = row: its four panel values (rows above the panel's tile row were not written: never used)
-  // (plain double accesses on purpose: reading this buffer through a vector type while it is written through
-  // `double` lets type-based alias analysis forward the PREVIOUS panel's stores to the lanes that did not write)
-  double pv[4] = {PL[lane * 4 + 0], PL[lane * 4 + 1], PL[lane * 4 + 2], PL[lane * 4 + 3]};
-  double l[4];
-  // 3. four pivots: everything in registers, multipliers by v_readlane with constant lane numbers
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    double piv = bcast_lane(pv[t], C0 + t);
-    const bool bad = !(piv > 0.0);
-    first_bad = bad ? min(first_bad, C0 + t) : first_bad;
-    piv = bad ? 1.0 : piv;
-    const double rs = rsqrt_newton(piv);
-    l[t] = lane >= C0 + t ? pv[t] * rs : 0.0;       // select, not multiply: rows above hold stale values
-    if (lane == 0) Rd[C0 + t] = rs;                 // 1 / L_jj for the substitution of the inverse
-#pragma unroll
-    for (int u = t + 1; u < 4; ++u) pv[u] -= l[t] * bcast_lane(l[t], C0 + u);
-  }
-  // 4. L panel: column-major factor Ls[col][row] (final output) and the 64 x 4 operand image PL[row][0..3]
-#pragma unroll
-  for (int t = 0; t < 4; ++t) Ls[(C0 + t) * CLD + lane] = l[t];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) PL[lane * 4 + t] = l[t];
-  if (Q == 15) return;
-  wave_lds_sync();
-  // 5. acc[ti][tj] -= L[rows of ti][panel] L[rows of tj][panel]'   (A fragment: (m = lane & 15, k = lane >> 4);
-  //    the B fragment of tile column tj is the A fragment of tile row tj)
-  double a[4];
-#pragma unroll
-  for (int t4 = TJ0; t4 < 4; ++t4) a[t4] = PL[(16 * t4 + (lane & 15)) * 4 + (lane >> 4)];
-#pragma unroll
-  for (int tj = TJ0; tj < 4; ++tj)
-#pragma unroll
-    for (int ti = tj; ti < 4; ++ti)
-      acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[ti], a[tj], acc[ti][tj], 0, 0, 0);
-  wave_lds_sync();          // the next panel overwrites PL
-}
-
-template <int Q>
-struct CholPanels {
-  static __device__ __forceinline__ void run(v4f64 (&acc)[4][4], int lane, double* Ls, double* Rd, double* PL, int& first_bad) {
-    CholPanels<Q - 1>::run(acc, lane, Ls, Rd, PL, first_bad);
-    chol_panel<Q>(acc, lane, Ls, Rd, PL, first_bad);
-  }
-};
-template <>
-struct CholPanels<-1> {
-  static __device__ __forceinline__ void run(v4f64 (&)[4][4], int, double*, double*, double*, int&) {}
-};
-
-// wave 0: In (row-major, stride CLD) -> Ls[col * CLD + row] = L[row][col] (whole columns, zeros above the diagonal),
-// Rd[j] = 1 / L_jj.  Returns the first non-positive pivot or 0x7fffffff.
-__device__ __forceinline__ int chol64_mfma(const double* In, double* Ls, double* Rd, double* PL, int lane) {
-  v4f64 acc[4][4];
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        acc[ti][tj][r] = tj <= ti ? In[(16 * ti + (lane >> 4) + 4 * r) * CLD + 16 * tj + (lane & 15)] : 0.0;
-  int first_bad = 0x7fffffff;
-  CholPanels<15>::run(acc, lane, Ls, Rd, PL, first_bad);
-  return first_bad;
-}
-
 // ---------------------------------------------------------------------------
-// MFMA form with 16-COLUMN panels (round 5, the default).  The 4-column form above makes 15 accumulator -> LDS -> lane
-// = row -> LDS -> MFMA-fragment round trips per block (~500 cycles each) around a pivot chain of ~290 cycles per pivot;
-// here a panel is a whole tile column: ONE trip through LDS brings it into lane = row registers (16 values per lane),
+// The 64 x 64 factorization: ONE wave, MFMA with 16-COLUMN panels.  The Schur complement lives in
+// v_mfma_f64_16x16x4_f64 accumulators (the lower 16 x 16 tiles right of the first tile column) and a panel is a whole
+// tile column: ONE trip through LDS brings it into lane = row registers (16 values per lane),
 // all 16 pivots run in registers -- the update of the panel's remaining columns by pivot t is (15 - t) readlane + FMA
 // pairs that are independent of each other and fill the latency shadow of the NEXT pivot's rsqrt chain -- and the
 // trailing tiles (strictly right of the panel) take the panel as FOUR k-steps of v_mfma_f64_16x16x4_f64 whose operand
-// fragments are read straight from the column-major factor image.  3 + 3 LDS trips per block instead of 31, and the
-// tile column of panel 0 never visits the accumulators at all.
+// fragments are read straight from the column-major factor image.  3 + 3 LDS trips per block, and the
+// tile column of panel 0 never visits the accumulators at all.  The wave issues ~3000 instructions per block (24.3k
+// shader cycles inside the chain kernel): the block is issue-bound.
+// The inverse (inv64_* below) is blocked as well: the four 16 x 16 diagonal blocks are inverted by substitution (one wave
+// each, 16 steps), the six blocks below the diagonal follow from 16 x 16 MFMA products, column j on wave j:
+//   X_ij = -X_ii sum_{t=j}^{i-1} L_it X_tj
 // ---------------------------------------------------------------------------
 template <int P>
 __device__ __forceinline__ void chol_panel16(v4f64 (&acc)[4][4], int lane, const double* In, double* Ls, double* Rd, double* PL,
@@ -602,7 +403,9 @@ __device__ __forceinline__ void publish_block_shared(const double* lds, int tid,
   }
 }
 
-template <int FORM, bool SHARED = false, bool STORE = true>
+// lds: the input tile in tile 1 (row-major, identity-padded) -> factor image in tile 0, L^-T in tile 2; behind the three
+// tiles: Rd (64 doubles), 8 doubles of flags (the chain kernel's), the panel image
+template <bool SHARED = false, bool STORE = true>
 __device__ __forceinline__ void factor_and_publish_t(double* lds, int tid, int nbv, double* __restrict__ Lblk, int64_t ldl,
                                                      double* __restrict__ Tblk, int* __restrict__ info, int64_t col0,
                                                      unsigned long long* stamps = nullptr) {
@@ -610,27 +413,17 @@ __device__ __forceinline__ void factor_and_publish_t(double* lds, int tid, int n
   const double* In = lds + CTILE;
   double* Xs = lds + 2 * CTILE;
   double* Rd = lds + 3 * CTILE;
-  int* progress = reinterpret_cast<int*>(Rd + CB);
   double* PL = Rd + CB + 8;
-  if (FORM != 0) {
-    __syncthreads();
-    if (tid < 64) {
-      if (stamps && tid == 0) stamps[0] = __builtin_readcyclecounter();
-      const int bad = FORM == 2 ? chol64_p16(In, Ls, Rd, PL, tid) : chol64_mfma(In, Ls, Rd, PL, tid);
-      if (tid == 0 && bad != 0x7fffffff) atomicMin(info, int(col0 + bad + 1));
-      if (stamps && tid == 0) stamps[1] = __builtin_readcyclecounter();
-    }
-    __syncthreads();
-    inv64_mfma(Ls, Rd, Xs, tid);
-    if (stamps && tid == 0) stamps[2] = __builtin_readcyclecounter();
-  } else {
-    if (tid == 0) *progress = 0;
-    __syncthreads();
-    if (tid < 128) {
-      const int bad = wave_factor_lds(Ls, In, Xs, Rd, progress, tid);
-      if (tid == 0 && bad != 0x7fffffff) atomicMin(info, int(col0 + bad + 1));
-    }
+  __syncthreads();
+  if (tid < 64) {
+    if (stamps && tid == 0) stamps[0] = __builtin_readcyclecounter();
+    const int bad = chol64_p16(In, Ls, Rd, PL, tid);
+    if (tid == 0 && bad != 0x7fffffff) atomicMin(info, int(col0 + bad + 1));
+    if (stamps && tid == 0) stamps[1] = __builtin_readcyclecounter();
   }
+  __syncthreads();
+  inv64_mfma(Ls, Rd, Xs, tid);
+  if (stamps && tid == 0) stamps[2] = __builtin_readcyclecounter();
   __syncthreads();
   if (!STORE) return;
   const int c = tid & 63;
@@ -646,7 +439,6 @@ __device__ __forceinline__ void factor_and_publish_t(double* lds, int tid, int n
 }
 
 // first diagonal block of every matrix
-template <int FORM>
 __global__ __launch_bounds__(256) void k_cholinv_first(CholInvBatch bt, int* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char ci_smem[];
   double* lds = reinterpret_cast<double*>(ci_smem);
@@ -661,11 +453,10 @@ __global__ __launch_bounds__(256) void k_cholinv_first(CholInvBatch bt, int* __r
     if (r < nbv && c < nbv) v = c <= r ? bt.A[b][int64_t(r) * bt.lda[b] + c] : bt.A[b][int64_t(c) * bt.lda[b] + r];
     Xs[r * CLD + c] = v;
   }
-  factor_and_publish_t<FORM>(lds, tid, nbv, bt.L[b], bt.ldl[b], bt.T[b], info + b, 0);
+  factor_and_publish_t(lds, tid, nbv, bt.L[b], bt.ldl[b], bt.T[b], info + b, 0);
 }
 
 // step j: trailing update (+ look-ahead factorization of block j + 1) and row j of the inverse
-template <int FORM>
 __global__ __launch_bounds__(256) void k_cholinv_step(CholInvBatch bt, int j, int* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char ci_smem[];
   double* lds = reinterpret_cast<double*>(ci_smem);
@@ -746,7 +537,7 @@ __global__ __launch_bounds__(256) void k_cholinv_step(CholInvBatch bt, int j, in
         }
         Q[rr * CLD + cc] = v;                             // tile 1 = Xs of the wave factorization
       }
-    factor_and_publish_t<FORM>(lds, tid, rows_i, L + ri * ldl + ri, ldl, bt.T[b] + int64_t(j + 1) * CB * CB, info + b, ri);
+    factor_and_publish_t(lds, tid, rows_i, L + ri * ldl + ri, ldl, bt.T[b] + int64_t(j + 1) * CB * CB, info + b, ri);
     return;
   }
 
@@ -925,7 +716,6 @@ __device__ __forceinline__ void chain_publish_set(unsigned* p, unsigned v, int t
 // (the thread index passes through an empty asm at the head of this path and of the helper items: without it the compiler
 // forms every path's index constants at the kernel's entry, keeps them alive across the whole kernel, and spills 65 to 126
 // registers that are reloaded from scratch memory inside the chain)
-template <int FORM>
 __device__ __forceinline__ void chain_matrix(int64_t d, int64_t lda, int64_t ldl, double* A, double* L, double* T, bool with_x, int b,
                                                        ChainSync* sy, int* __restrict__ info, double* lds4, int* flag, int tid,
                                                        unsigned long long* dbg) {
@@ -953,7 +743,7 @@ __device__ __forceinline__ void chain_matrix(int64_t d, int64_t lda, int64_t ldl
     }
     __syncthreads();
     if (tid < 64) {
-      const int bad = FORM == 2 ? chol64_p16(IN, lds4 + cur * CTILE, Rd, PL, tid) : chol64_mfma(IN, lds4 + cur * CTILE, Rd, PL, tid);
+      const int bad = chol64_p16(IN, lds4 + cur * CTILE, Rd, PL, tid);
       if (tid == 0 && bad != 0x7fffffff) atomicMin(info + b, int(bad + 1));
     }
     __syncthreads();
@@ -1043,7 +833,7 @@ __device__ __forceinline__ void chain_matrix(int64_t d, int64_t lda, int64_t ldl
     // ---- fork: wave 0 factors block j + 1, waves 1-3 finish and publish block j ----
     if (w == 0) {
       if (more) {
-        const int bad = FORM == 2 ? chol64_p16(IN, Lnxt, Rd, PL, lane) : chol64_mfma(IN, Lnxt, Rd, PL, lane);
+        const int bad = chol64_p16(IN, Lnxt, Rd, PL, lane);
         if (lane == 0 && bad != 0x7fffffff) atomicMin(info + b, int(ri + bad + 1));
         if (dj && lane == 0) dj[5] = __builtin_readcyclecounter();
       }
@@ -1239,13 +1029,12 @@ __device__ __forceinline__ void chain_helper(int j, int q, int hU, int nXT, int 
   if (!ok && tid == 0) atomicMin(info + b, CH_TIMEOUT_INFO);
 }
 
-template <int FORM>
 __global__ __launch_bounds__(256) void k_cholinv_chain(CholInvBatch bt, ChainPlan plan, ChainSync* __restrict__ sy, int* __restrict__ info,
                                                        unsigned long long* __restrict__ dbg) {
   extern __shared__ __attribute__((aligned(16))) char ci_smem[];
   double* lds4 = reinterpret_cast<double*>(ci_smem);          // extra tile, then the step kernels' layout
   double* lds = lds4 + CTILE;
-  int* flags = reinterpret_cast<int*>(lds + 3 * CTILE + CB);   // [0] progress word of the shift-register form, [2] wait flag, [3] ticket
+  int* flags = reinterpret_cast<int*>(lds + 3 * CTILE + CB);   // [2] wait flag, [3] ticket ([4] chain_matrix's pubcnt)
   const int tid = threadIdx.x;
   for (;;) {
     __syncthreads();                                           // everyone is done with the previous item (LDS, flags)
@@ -1255,7 +1044,7 @@ __global__ __launch_bounds__(256) void k_cholinv_chain(CholInvBatch bt, ChainPla
     if (ticket >= plan.total) break;
     if (ticket < bt.count) {
       const int b = ticket;
-      chain_matrix<FORM>(bt.d[b], bt.lda[b], bt.ldl[b], bt.A[b], bt.L[b], bt.T[b], bt.X[b] != nullptr, b, sy, info, lds4, flags + 2, tid, dbg);
+      chain_matrix(bt.d[b], bt.lda[b], bt.ldl[b], bt.A[b], bt.L[b], bt.T[b], bt.X[b] != nullptr, b, sy, info, lds4, flags + 2, tid, dbg);
     } else {
       int q = ticket - bt.count;
       int j = 0;
@@ -1285,33 +1074,16 @@ __global__ __launch_bounds__(256) void k_cholinv_chain(CholInvBatch bt, ChainPla
   }
 }
 
-template <int FORM>
-static void cholinv_attr_form() {
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_first<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHOLINV_LDS)));
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_step<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHOLINV_LDS)));
-}
-
 static void cholinv_attr_once() {
   static thread_local int done_for_device = -1;
   int dev = -1;
   CCZ_HIP(hipGetDevice(&dev));
   if (done_for_device == dev) return;
-  cholinv_attr_form<0>();
-  cholinv_attr_form<1>();
-  cholinv_attr_form<2>();
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_chain<1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHAIN_LDS)));
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_chain<2>), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHAIN_LDS)));
+  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_first), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHOLINV_LDS)));
+  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_step), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHOLINV_LDS)));
+  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholinv_chain), hipFuncAttributeMaxDynamicSharedMemorySize, int(CHAIN_LDS)));
   CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_f64_multi), hipFuncAttributeMaxDynamicSharedMemorySize, int(MG_LDS_FWD)));
   done_for_device = dev;
-}
-
-// CCZ_CHOLINV_MFMA: 0 shift-register (two-wave) form of the 64 x 64 factorization, 1 MFMA form with 4-column panels
-// (rounds 2-4: 30.4k shader cycles per block inside the chain kernel), 2 MFMA form with 16-column panels (24.3k).
-// Either way ONE wave issues ~3000 instructions per block: a dependent fp64 operation costs 4-8 cycles, not the 32 that
-// rounds 2-4 designed around (tools/probes/lat_probe.hip: that probe timed a loop branch) -- the block is issue-bound.
-static int cholinv_form() {
-  const int v = env::once(env::CHOLINV_MFMA);
-  return v < 0 || v > 2 ? 2 : v;
 }
 
 // The sync block of the chain kernel belongs to the STREAM the launch goes into: launches on one stream are ordered, so
@@ -1330,8 +1102,7 @@ static ChainSync* chain_sync_for(ccz_ctx* c) {
 // CCZ_CHOLINV_CHAIN=0: the launch-per-link form (rounds 2-4).  CCZ_CHAIN_WGS: workgroups of the persistent launch
 // (Impl::chain_cap overrides it for callers that share the chip with throughput work on another stream).
 static bool chain_launch(ccz_ctx* c, const CholInvBatch& bt, int nbmax, int* info_dev) {
-  const int form = cholinv_form();
-  if (!env::once(env::CHOLINV_CHAIN) || form == 0 || bt.inv_only || nbmax > CH_MAXNB) return false;
+  if (!env::once(env::CHOLINV_CHAIN) || bt.inv_only || nbmax > CH_MAXNB) return false;
   ChainPlan plan{};
   plan.nbmax = nbmax;
   int total = 0;
@@ -1359,8 +1130,7 @@ static bool chain_launch(ccz_ctx* c, const CholInvBatch& bt, int nbmax, int* inf
     dbg = static_cast<unsigned long long*>(im->chain_dbg.get());
     CCZ_HIP(hipMemsetAsync(dbg, 0, 8 * (CH_MAXNB + 1) * sizeof(unsigned long long), stream(c)));
   }
-  if (form == 2) hipLaunchKernelGGL(k_cholinv_chain<2>, dim3(grid), dim3(256), CHAIN_LDS, stream(c), bt, plan, sy, info_dev, dbg);
-  else hipLaunchKernelGGL(k_cholinv_chain<1>, dim3(grid), dim3(256), CHAIN_LDS, stream(c), bt, plan, sy, info_dev, dbg);
+  hipLaunchKernelGGL(k_cholinv_chain, dim3(grid), dim3(256), CHAIN_LDS, stream(c), bt, plan, sy, info_dev, dbg);
   CCZ_LAUNCH_CHECK();
   if (debug) {
     std::vector<unsigned long long> hst(size_t(8) * (CH_MAXNB + 1));
@@ -1398,11 +1168,8 @@ void cholinv_batched(ccz_ctx* c, int count, double* const* A, const int64_t* lda
     bt.lda[b] = lda[b]; bt.ldl[b] = ldl[b]; bt.ldx[b] = X ? ldx[b] : 0; bt.d[b] = d[b];
     nbmax = std::max(nbmax, int((d[b] + CB - 1) / CB));
   }
-  const int form = cholinv_form();
   if (chain_launch(c, bt, nbmax, info_dev)) return;        // ONE persistent launch (below); false: not applicable / switched off
-  if (form == 2) hipLaunchKernelGGL(k_cholinv_first<2>, dim3(count), dim3(256), CHOLINV_LDS, st, bt, info_dev);
-  else if (form == 1) hipLaunchKernelGGL(k_cholinv_first<1>, dim3(count), dim3(256), CHOLINV_LDS, st, bt, info_dev);
-  else hipLaunchKernelGGL(k_cholinv_first<0>, dim3(count), dim3(256), CHOLINV_LDS, st, bt, info_dev);
+  hipLaunchKernelGGL(k_cholinv_first, dim3(count), dim3(256), CHOLINV_LDS, st, bt, info_dev);
   for (int j = 0; j < nbmax; ++j) {
     int total = 0;
     for (int b = 0; b < count; ++b) {
@@ -1415,15 +1182,13 @@ void cholinv_batched(ccz_ctx* c, int count, double* const* A, const int64_t* lda
     }
     bt.first[count] = total;
     if (total == 0) continue;
-    if (form == 2) hipLaunchKernelGGL(k_cholinv_step<2>, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, info_dev);
-    else if (form == 1) hipLaunchKernelGGL(k_cholinv_step<1>, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, info_dev);
-    else hipLaunchKernelGGL(k_cholinv_step<0>, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, info_dev);
+    hipLaunchKernelGGL(k_cholinv_step, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, info_dev);
   }
   CCZ_LAUNCH_CHECK();
 }
 
 // X[b] = L[b]^-1 for `count` (<= 8) lower-triangular blocks whose 64 x 64 diagonal inverses T[b] (L_jj^-T, as
-// k_wave_chol_inv / cholinv_batched leave them) are known: d_max / 64 launches, rows of all blocks advance together.
+// k_diag_block_inv / cholinv_batched leave them) are known: d_max / 64 launches, rows of all blocks advance together.
 // Blocks of X above the diagonal are not written.
 void trinv_batched(ccz_ctx* c, int count, const double* const* L, const int64_t* ldl, const int64_t* d, double* const* X,
                    const int64_t* ldx, const double* const* T) {
@@ -1447,7 +1212,7 @@ void trinv_batched(ccz_ctx* c, int count, const double* const* L, const int64_t*
     }
     bt.first[count] = total;
     if (total == 0) continue;
-    hipLaunchKernelGGL(k_cholinv_step<2>, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, static_cast<int*>(nullptr));
+    hipLaunchKernelGGL(k_cholinv_step, dim3(total), dim3(256), CHOLINV_LDS, st, bt, j, static_cast<int*>(nullptr));
   }
   CCZ_LAUNCH_CHECK();
 }

@@ -67,7 +67,6 @@ using STR = const char*;
   X(GEMM_HALF_TILE, I64, 1, ONCE, "0: no half-height tiles on grids smaller than the chip -- gemm64_big.hip gemm_f64_big: A/B")              \
   X(GEMM_SKINNY_OFF, STR, nullptr, ONCE, "text starting with 1: the skinny kernel is never eligible -- gemm64_skinny.hip gemm_f64_skinny_eligible: A/B") \
   /* ---- Cholesky and triangular solves (cholinv.hip, ops_hip.hip) ---- */                                                                   \
-  X(CHOLINV_MFMA, INT, 2, ONCE, "64 x 64 block: 0 shift-register form, 1 MFMA with 4-column panels, 2 with 16-column panels (else: 2) -- cholinv.hip cholinv_form: A/B") \
   X(CHOLINV_CHAIN, INT, 1, ONCE, "0: the launch-per-link form instead of the persistent chain kernel -- cholinv.hip chain_launch: A/B")      \
   X(CHAIN_WGS, INT, 128, ONCE, "workgroups of the chain launch (below 2: 2; Impl::chain_cap overrides it) -- cholinv.hip chain_launch: A/B")  \
   X(CHAIN_WGS_LA, INT, 64, ONCE, "the same on the look-ahead stream, next to the update GEMMs -- ops_hip.hip potrf_lower_batched_sb: A/B")   \

@@ -815,51 +815,17 @@ void gather_rows(ccz_ctx* c, int64_t rows, int64_t cols, const double* in, int64
 constexpr int NB = 64;
 
 // ---------------------------------------------------------------------------
-// 64 x 64 diagonal block on ONE wavefront, no barriers.  Lane i owns row i of the current Schur
-// complement in 64 registers and the block is consumed as a SHIFT REGISTER: at step j register a[0]
-// is column j, the rank-1 update writes its result one register down (a[k-1] = a[k] - l_i l_{j+k}),
-// so every register index is a compile-time constant while j is a run-time loop counter
-// (v_readlane with an SGPR lane index broadcasts l_{j+k}).  The loop body is ~200 instructions;
-// four bodies of decreasing width (63, 47, 31, 15 live columns) keep ~2/3 of the triangular saving.
-// The first version unrolled all 2016 (j, k) pairs with static register indices: 134 KB of
-// straight-line code for one wavefront -- larger than the instruction cache, so its run time was
-// set by where the code happened to be cached (46 us ... 210 us for the same block; rocprofv3).
-// The finished column goes to LDS (Ls[j][i], stride 65); the second phase forms invT = L^-T by
-// forward substitution in the same shift-register form (lane c solves L x = e_c, the multipliers
-// L[t+k][t] are wave-uniform LDS broadcasts).  Global loads / stores are whole 512-byte rows,
-// transposed through LDS.  Blocks narrower than 64 are padded with the identity.
+// invT = L_bb^-T of every 64 x 64 diagonal block of a given lower factor L, each on ONE wavefront, no barriers.
+// The block goes to LDS column-major (Ls[j][i] = L[i][j], stride 65); lane c then solves L x = e_c by forward
+// substitution with its right-hand side in 64 registers consumed as a SHIFT REGISTER: at step t register v[0] is the
+// current entry, the update writes its result one register down (v[k-1] = v[k] - L[t+k][t] x), so every register
+// index is a compile-time constant while t is a run-time loop counter; the multipliers L[t+k][t] are wave-uniform
+// LDS broadcasts.  Four loop bodies of decreasing width (63, 47, 31, 15 live entries) keep ~2/3 of the triangular
+// saving without unrolling all 2016 (t, k) pairs -- straight-line code of that size does not fit the instruction
+// cache.  Global loads / stores are whole 512-byte rows, transposed through LDS.  Blocks narrower than 64 are
+// padded with the identity.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double lane_bcast(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-
 constexpr int WLD = NB + 1;   // LDS tile stride (doubles): column and row accesses both conflict-free
-
-template <int KMAX>
-__device__ __forceinline__ void chol_steps(double (&a)[NB], int j_begin, int j_end, int lane, double* Ls, int& first_bad) {
-#pragma unroll 1
-  for (int j = j_begin; j < j_end; ++j) {
-    const double col = a[0];
-    double piv = lane_bcast(col, j);
-    const bool bad = !(piv > 0.0);                 // wave-uniform
-    first_bad = bad ? min(first_bad, j) : first_bad;
-    piv = bad ? 1.0 : piv;
-    const double l = col * (1.0 / sqrt(piv));      // lanes >= j: L[lane][j]; lanes < j hold junk that nobody reads
-    double* lcol = Ls + j * WLD;
-    lcol[lane] = lane >= j ? l : 0.0;
-    // l_{j+k} comes back as a wave-uniform LDS broadcast (one ds_read_b64 with an immediate offset instead of
-    // two v_readlane + an SALU add); reads past row 63 land in junk that only feeds junk registers
-    const double* lrow = lcol + j;
-#pragma unroll
-    for (int k = 1; k <= KMAX; ++k) {
-      a[k - 1] = a[k] - l * lrow[k];
-      if ((k & 7) == 0) __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
 template <int KMAX>
 __device__ __forceinline__ void inv_steps(double (&v)[NB], int t_begin, int t_end, int lane, const double* Ls, double* Xs) {
@@ -877,62 +843,33 @@ __device__ __forceinline__ void inv_steps(double (&v)[NB], int t_begin, int t_en
   }
 }
 
-// Ajj: the diagonal block (row stride lda), nb valid rows/columns.  do_chol: factor it in place (lower
-// triangle written back) else it already holds L.  invT (may be null): 64 x 64 row-major L^-T.
-// Returns the first non-positive pivot (0-based) or 0x7fffffff.
-__device__ __forceinline__ int wave_block(double* __restrict__ Ajj, int64_t lda, int nb, bool do_chol,
-                                          double* __restrict__ invT, double* lds) {
+// Ljj: the diagonal block of L (row stride ldl), nb valid rows/columns.  invT: 64 x 64 row-major L_jj^-T.
+__device__ __forceinline__ void diag_block_inv(const double* __restrict__ Ljj, int64_t ldl, int nb, double* __restrict__ invT, double* lds) {
   const int lane = threadIdx.x;
   double* Ls = lds;                 // Ls[t * WLD + i] = L[i][t]
-  double* Xs = lds + NB * WLD;      // input tile first, then Xs[c * WLD + t] = (L^-T)[c][t]
-  int first_bad = 0x7fffffff;
-  if (do_chol) {
-    // rows arrive as full 512-byte lines (lane = column), each lane then picks up its own row
-    for (int r = 0; r < NB; ++r) {
-      double v = (r == lane) ? 1.0 : 0.0;
-      if (r < nb && lane < nb) v = Ajj[int64_t(r) * lda + lane];
-      Xs[r * WLD + lane] = v;
-    }
-    double a[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) a[k] = Xs[lane * WLD + k];
-    chol_steps<63>(a, 0, 16, lane, Ls, first_bad);
-    chol_steps<47>(a, 16, 32, lane, Ls, first_bad);
-    chol_steps<31>(a, 32, 48, lane, Ls, first_bad);
-    chol_steps<15>(a, 48, 64, lane, Ls, first_bad);
-    for (int r = 0; r < nb; ++r)
-      if (lane <= r && lane < nb) Ajj[int64_t(r) * lda + lane] = Ls[lane * WLD + r];
-  } else {
-    for (int r = 0; r < NB; ++r) {
-      double v = (r == lane) ? 1.0 : 0.0;
-      if (r < nb && lane < nb) v = lane <= r ? Ajj[int64_t(r) * lda + lane] : 0.0;
-      Ls[lane * WLD + r] = v;
-    }
+  double* Xs = lds + NB * WLD;      // Xs[c * WLD + t] = (L^-T)[c][t]
+  for (int r = 0; r < NB; ++r) {
+    double v = (r == lane) ? 1.0 : 0.0;
+    if (r < nb && lane < nb) v = lane <= r ? Ljj[int64_t(r) * ldl + lane] : 0.0;
+    Ls[lane * WLD + r] = v;
   }
-  if (invT) {
-    double v[NB];
+  double v[NB];
 #pragma unroll
-    for (int k = 0; k < NB; ++k) v[k] = (k == lane) ? 1.0 : 0.0;
-    inv_steps<63>(v, 0, 16, lane, Ls, Xs);
-    inv_steps<47>(v, 16, 32, lane, Ls, Xs);
-    inv_steps<31>(v, 32, 48, lane, Ls, Xs);
-    inv_steps<15>(v, 48, 64, lane, Ls, Xs);
-    for (int r = 0; r < NB; ++r) invT[r * NB + lane] = Xs[r * WLD + lane];
-  }
-  return first_bad;
+  for (int k = 0; k < NB; ++k) v[k] = (k == lane) ? 1.0 : 0.0;
+  inv_steps<63>(v, 0, 16, lane, Ls, Xs);
+  inv_steps<47>(v, 16, 32, lane, Ls, Xs);
+  inv_steps<31>(v, 32, 48, lane, Ls, Xs);
+  inv_steps<15>(v, 48, 64, lane, Ls, Xs);
+  for (int r = 0; r < NB; ++r) invT[r * NB + lane] = Xs[r * WLD + lane];
 }
 
 constexpr size_t WAVE_BLOCK_LDS = (size_t(2) * NB * WLD + 2 * NB) * sizeof(double);   // two tiles + slack for the over-reads
 
-template <bool DO_CHOL>
-__global__ __launch_bounds__(64) void k_wave_chol_inv(double* __restrict__ A, int64_t lda, int64_t d, int64_t j_first,
-                                                      int* __restrict__ info, double* __restrict__ invT) {
+__global__ __launch_bounds__(64) void k_diag_block_inv(const double* __restrict__ L, int64_t ldl, int64_t d, double* __restrict__ invT) {
   extern __shared__ __attribute__((aligned(16))) char wave_smem[];
-  const int64_t j0 = j_first + int64_t(blockIdx.x) * NB;
+  const int64_t j0 = int64_t(blockIdx.x) * NB;
   const int nb = int(min(int64_t(NB), d - j0));
-  const int bad = wave_block(A + j0 * lda + j0, lda, nb, DO_CHOL, invT ? invT + int64_t(blockIdx.x) * NB * NB : nullptr,
-                             reinterpret_cast<double*>(wave_smem));
-  if (DO_CHOL && bad != 0x7fffffff && threadIdx.x == 0) atomicMin(info, int(j0 + bad + 1));
+  diag_block_inv(L + j0 * ldl + j0, ldl, nb, invT + int64_t(blockIdx.x) * NB * NB, reinterpret_cast<double*>(wave_smem));
 }
 
 // the wave kernel uses 65 KiB of dynamic LDS: opt in once per device (never inside a graph capture)
@@ -941,15 +878,14 @@ void wave_kernels_init() {
   int dev = -1;
   CCZ_HIP(hipGetDevice(&dev));
   if (done_for_device == dev) return;
-  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wave_chol_inv<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(WAVE_BLOCK_LDS)));
+  CCZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_diag_block_inv), hipFuncAttributeMaxDynamicSharedMemorySize, int(WAVE_BLOCK_LDS)));
   done_for_device = dev;
 }
 
 // invT[b] = L_bb^-T for every diagonal block b of L (one wave each, all blocks in one launch)
 static void diag_inverses(ccz_ctx* c, const double* L, int64_t ldl, int64_t d, double* invT) {
   const unsigned nblk = (unsigned)((d + NB - 1) / NB);
-  hipLaunchKernelGGL(k_wave_chol_inv<false>, dim3(nblk), dim3(64), WAVE_BLOCK_LDS, stream(c), const_cast<double*>(L), ldl, d,
-                     int64_t(0), static_cast<int*>(nullptr), invT);
+  hipLaunchKernelGGL(k_diag_block_inv, dim3(nblk), dim3(64), WAVE_BLOCK_LDS, stream(c), L, ldl, d, invT);
   CCZ_LAUNCH_CHECK();
 }
 

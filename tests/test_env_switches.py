@@ -26,7 +26,7 @@ def _read(path):
 
 def _table():
     rows = ROW.findall(_read(os.path.join(CSRC, "env.h")))
-    assert len(rows) >= 60, "the table of env.h no longer parses: %d rows" % len(rows)
+    assert len(rows) >= 59, "the table of env.h no longer parses: %d rows" % len(rows)
     return rows
 
 

@@ -1,5 +1,5 @@
-"""GPU parity, round 2: the building blocks added this round (batched Cholesky + inverse, batched GEMM, pilot-mean
-K1, counter-based generator, device loadings / GCCALoss) and the BASELINE shapes that had no GPU test:
+"""GPU parity, round 2: the building blocks added this round (batched GEMM, pilot-mean K1; the batched
+Cholesky + inverse: test_gpu_cholinv.py; counter-based generator, device loadings / GCCALoss) and the BASELINE shapes that had no GPU test:
 NS (2 x 4096, k = 64, fp32), C3 (MCCA 4 x 2048, k = 64), C5 (GCCA [4096, 4096, 8192], k = 128, fp64), plus the
 recursive Cholesky / TRSM paths (d >= 6144) and split-K GEMM shapes.
 
@@ -21,69 +21,6 @@ def H():
     from cca_zoo_amd import _backend
 
     return _backend.default_handle(0)
-
-
-def _spd(rng, d, cond=1e3):
-    q, _ = np.linalg.qr(rng.standard_normal((d, d)))
-    lam = np.geomspace(1.0, 1.0 / cond, d)
-    return (q * lam) @ q.T
-
-
-# ---------------------------------------------------------------------------------------------
-# cholinv.hip
-# ---------------------------------------------------------------------------------------------
-def _cholinv(H, mats, want_x=True):
-    bufs, ptrs_a, ptrs_l, ptrs_x = [], [], [], []
-    for A in mats:
-        d = A.shape[0]
-        a = H.to_device(A)
-        l = H.to_device(np.full((d, d), np.nan))
-        x = H.to_device(np.zeros((d, d)))
-        bufs.append((a, l, x))
-        ptrs_a.append(a.ptr)
-        ptrs_l.append(l.ptr)
-        ptrs_x.append(x.ptr)
-    n = len(mats)
-    arr = lambda p: (C.c_void_p * n)(*p)
-    dd = (C.c_int64 * n)(*[m.shape[0] for m in mats])
-    H.check(H.lib.ccz_cholinv(H.raw, n, arr(ptrs_a), dd, arr(ptrs_l), arr(ptrs_x) if want_x else None))
-    out = []
-    for (a, l, x), A in zip(bufs, mats):
-        d = A.shape[0]
-        out.append((H.to_host(l, (d, d)), H.to_host(x, (d, d))))
-    return out
-
-
-@pytest.mark.parametrize("d", [1, 5, 63, 64, 65, 128, 200, 512, 1000])
-def test_cholinv_single(H, d):
-    rng = np.random.default_rng(d)
-    A = _spd(rng, d)
-    (L, X), = _cholinv(H, [A])
-    Lr = np.linalg.cholesky(A)
-    assert np.abs(np.tril(L) - Lr).max() < 1e-11 * np.abs(Lr).max()
-    assert np.all(np.isnan(L[np.triu_indices(d, 1)]))            # strictly-upper part untouched
-    Xl = np.tril(X)
-    assert np.abs(Xl @ Lr - np.eye(d)).max() < 1e-9
-    # blocks strictly above the block diagonal were left at the zeros we put there
-    for bi in range(0, d, 64):
-        assert np.all(X[bi:bi + 64, bi + 64:] == 0.0)
-
-
-def test_cholinv_batched_mixed_sizes_and_failure(H):
-    rng = np.random.default_rng(7)
-    mats = [_spd(rng, d, 1e4) for d in (512, 70, 512, 1, 333, 64, 129, 200)]
-    for (L, X), A in zip(_cholinv(H, mats), mats):
-        Lr = np.linalg.cholesky(A)
-        assert np.abs(np.tril(L) - Lr).max() < 1e-10 * np.abs(Lr).max()
-        assert np.abs(np.tril(X) @ Lr - np.eye(A.shape[0])).max() < 1e-8
-    # factor only
-    (L, X), = _cholinv(H, [mats[0]], want_x=False)
-    assert np.abs(np.tril(L) - np.linalg.cholesky(mats[0])).max() < 1e-10 and np.all(X == 0.0)
-    # an indefinite matrix is reported, with the others in the batch unaffected up to that point
-    bad = mats[4].copy()
-    bad[150, 150] = -1.0
-    with pytest.raises(np.linalg.LinAlgError, match="not positive definite"):
-        _cholinv(H, [mats[1], bad])
 
 
 # ---------------------------------------------------------------------------------------------

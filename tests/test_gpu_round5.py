@@ -1,7 +1,8 @@
-"""Round-5 GPU tests: the persistent Cholesky chain (csrc/cholinv.hip: k_cholinv_chain, 16-column panels), the loss
-fast path (K1 partial sums -> k_loss_prep_partials -> chain -> product stages with the loss riding on the third ->
-k_loss_tail) and the two-phase loss ABI (ccz_pair_loss_forward / _backward: the upstream gradient applied inside the
-sample-side product).  Reference seams: cca_zoo/deep/objectives.py:61-102 (CCALoss.forward + autograd), :138-153."""
+"""Round-5 GPU tests: the loss fast path (K1 partial sums -> k_loss_prep_partials -> Cholesky chain -> product stages
+with the loss riding on the third -> k_loss_tail), the two-phase loss ABI (ccz_pair_loss_forward / _backward: the
+upstream gradient applied inside the sample-side product), and the switches of the chain and of the loss, each in a child
+process (ccz_cholinv itself: test_gpu_cholinv.py).  Reference seams: cca_zoo/deep/objectives.py:61-102
+(CCALoss.forward + autograd), :138-153."""
 
 import ctypes as C
 import os
@@ -21,74 +22,6 @@ def H():
     from cca_zoo_amd import _backend
 
     return _backend.default_handle()
-
-
-def _spd(rng, d, cond=1e3):
-    q, _ = np.linalg.qr(rng.standard_normal((d, d)))
-    w = np.exp(np.linspace(0.0, np.log(cond), d))
-    return (q * w) @ q.T
-
-
-def _cholinv(H, mats, want_x=True):
-    bufs, pa, pl, px = [], [], [], []
-    for A in mats:
-        d = A.shape[0]
-        a, l, x = H.to_device(A), H.to_device(np.full((d, d), np.nan)), H.to_device(np.zeros((d, d)))
-        bufs.append((a, l, x))
-        pa.append(a.ptr), pl.append(l.ptr), px.append(x.ptr)
-    n = len(mats)
-    arr = lambda p: (C.c_void_p * n)(*p)
-    dd = (C.c_int64 * n)(*[m.shape[0] for m in mats])
-    H.check(H.lib.ccz_cholinv(H.raw, n, arr(pa), dd, arr(pl), arr(px) if want_x else None))
-    return [(H.to_host(l, A.shape), H.to_host(x, A.shape)) for (a, l, x), A in zip(bufs, mats)]
-
-
-# ---------------------------------------------------------------------------------------------
-# the chain kernel
-# ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("d", [64, 65, 127, 128, 192, 448, 512, 513, 1024, 1500, 2048])
-def test_chain_single_matrix(H, d):
-    rng = np.random.default_rng(1000 + d)
-    A = _spd(rng, d, 1e5)
-    (L, X), = _cholinv(H, [A])
-    Lr = np.linalg.cholesky(A)
-    assert np.abs(np.tril(L) - Lr).max() < 2e-11 * np.abs(Lr).max()
-    assert np.all(np.isnan(L[np.triu_indices(d, 1)]))            # strictly-upper part untouched
-    Xr = np.linalg.inv(Lr)
-    assert np.abs(np.tril(X) - Xr).max() < 1e-9 * np.abs(Xr).max()
-    for bi in range(0, d, 64):                                    # blocks above the block diagonal: left alone
-        assert np.all(X[bi:bi + 64, bi + 64:] == 0.0)
-
-
-def test_chain_repeated_launches_leave_the_sync_block_clean(H):
-    """The last workgroup of a launch clears the progress counters: twenty launches in a row (different shapes in
-    between) must all be right."""
-    rng = np.random.default_rng(5)
-    for it in range(20):
-        ds = [512, 512] if it % 3 else [200, 64, 700]
-        mats = [_spd(rng, d, 1e4) for d in ds]
-        for (L, X), A in zip(_cholinv(H, mats), mats):
-            Lr = np.linalg.cholesky(A)
-            assert np.abs(np.tril(L) - Lr).max() < 1e-10 * np.abs(Lr).max()
-            assert np.abs(np.tril(X) @ Lr - np.eye(A.shape[0])).max() < 1e-8
-
-
-def test_chain_eight_matrices_and_failure(H):
-    rng = np.random.default_rng(9)
-    mats = [_spd(rng, d, 1e4) for d in (512, 512, 512, 512, 333, 512, 129, 512)]
-    for (L, X), A in zip(_cholinv(H, mats), mats):
-        Lr = np.linalg.cholesky(A)
-        assert np.abs(np.tril(L) - Lr).max() < 1e-10 * np.abs(Lr).max()
-        assert np.abs(np.tril(X) @ Lr - np.eye(A.shape[0])).max() < 1e-8
-    (L, X), = _cholinv(H, [mats[0]], want_x=False)
-    assert np.abs(np.tril(L) - np.linalg.cholesky(mats[0])).max() < 1e-10 and np.all(X == 0.0)
-    bad = mats[4].copy()
-    bad[150, 150] = -1.0
-    with pytest.raises(np.linalg.LinAlgError, match="not positive definite"):
-        _cholinv(H, [mats[1], bad])
-    # ... and the launch after a failed one is clean again
-    (L, X), = _cholinv(H, [mats[6]])
-    assert np.abs(np.tril(L) - np.linalg.cholesky(mats[6])).max() < 1e-10
 
 
 _CHILD = r"""
@@ -132,9 +65,7 @@ print("child ok")
 
 
 @pytest.mark.parametrize("env", [
-    {"CCZ_CHOLINV_CHAIN": "0"},                           # launch-per-link form, 16-column panels
-    {"CCZ_CHOLINV_CHAIN": "0", "CCZ_CHOLINV_MFMA": "1"},  # ... with the 4-column panels of rounds 2-4
-    {"CCZ_CHOLINV_MFMA": "1"},                            # chain kernel on the 4-column panels
+    {"CCZ_CHOLINV_CHAIN": "0"},                           # launch-per-link kernels instead of the chain kernel
     {"CCZ_CHAIN_WGS": "2"},                               # chain workgroups + ONE helper: progress must not need co-residency
     {"CCZ_CHAIN_WGS": "24"},
     {"CCZ_LOSS_FAST": "0"},                               # the general route of the loss (moments + k_loss_prep)

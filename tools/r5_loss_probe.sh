@@ -11,10 +11,7 @@ tail -5 $O/t_loss_old.log >> $O/summary.txt
 echo "== timings (python tools/loss_profile.py 8192 512 40: median ms per fwd+bwd)" >> $O/summary.txt
 run() { name=$1; shift; echo -n "$name: " >> $O/summary.txt; env "$@" timeout 120 python tools/loss_profile.py 8192 512 40 2> $O/lp_$name.err | tail -1 >> $O/summary.txt; }
 run default CCZ_DUMMY=1
-run legacy_all CCZ_LOSS_FAST=0 CCZ_CHOLINV_CHAIN=0 CCZ_CHOLINV_MFMA=1
 run nochain CCZ_CHOLINV_CHAIN=0
-run nochain_p4 CCZ_CHOLINV_CHAIN=0 CCZ_CHOLINV_MFMA=1
-run chain_p4 CCZ_CHOLINV_MFMA=1
 run nofast CCZ_LOSS_FAST=0
 run splitk1 CCZ_LOSS_SPLITK=1
 run splitk4 CCZ_LOSS_SPLITK=4

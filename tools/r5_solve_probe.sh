@@ -6,10 +6,8 @@ timeout 1200 python -m pytest tests/test_gpu_round5.py tests/test_gpu_round2.py 
 run() { name=$1; shift; echo "== $name $*" >> $O/summary.txt; env "$@" timeout 300 python tools/solve_probe.py rcca 4096,4096 64 100000 2>&1 | grep solve | tail -2 >> $O/summary.txt; }
 run default CCZ_NOP=1
 run nochain CCZ_CHOLINV_CHAIN=0
-run nochain_p4 CCZ_CHOLINV_CHAIN=0 CCZ_CHOLINV_MFMA=1
 run la32 CCZ_CHAIN_WGS_LA=32
 run la128 CCZ_CHAIN_WGS_LA=128
-run p4 CCZ_CHOLINV_MFMA=1
 echo "== mcca 4x2048 default / nochain" >> $O/summary.txt
 timeout 300 python tools/solve_probe.py mcca 2048,2048,2048,2048 64 100000 2>&1 | grep solve | tail -2 >> $O/summary.txt
 CCZ_CHOLINV_CHAIN=0 timeout 300 python tools/solve_probe.py mcca 2048,2048,2048,2048 64 100000 2>&1 | grep solve | tail -2 >> $O/summary.txt
