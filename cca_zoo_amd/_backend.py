@@ -19,6 +19,16 @@ import numpy as np
 __all__ = ["CCZError", "Handle", "bind", "library", "library_path", "default_handle", "handle_for", "device_index"]
 
 F32, F64 = 0, 1
+BF16, F16 = 2, 3          # the 2-byte formats of the deep objectives' batches (include/ccz.h: CCZ_BF16, CCZ_F16), device rows only
+
+
+def dtype_code(dtype) -> int:
+    """``CCZ_*`` code of a torch dtype (float32, float64, bfloat16 or float16)."""
+    import torch
+
+    return {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16, torch.float16: F16}[dtype]
+
+
 _ERRORS = {
     -1: ValueError,
     -2: MemoryError,

@@ -45,8 +45,27 @@ namespace ccz {
 // out = (X - mean) W     reference: cca_zoo/_base.py:108-123
 static void transform_impl(ccz_ctx* c, int dtype, const void* X, int64_t n, int64_t d, int64_t ld, const double* mean,
                            const double* W, int64_t k, void* out, int64_t ldo) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "transform: dtype must be CCZ_F32 or CCZ_F64");
+  if (dtype != CCZ_F32 && dtype != CCZ_F64 && !is_half_dtype(dtype)) fail(CCZ_EUNSUP, "transform: dtype must be CCZ_F32, CCZ_F64, CCZ_BF16 or CCZ_F16");
   if (!X || !W || !out || n < 1 || d < 1 || k < 1 || ld < d || ldo < k) fail(CCZ_EINVAL, "transform: bad argument");
+  if (is_half_dtype(dtype)) {
+    // half rows in and out: row chunks through float32 scratch, the float32 projection unchanged on them, one rounding on the way out
+    const int64_t widths[2] = {d, k};
+    const int64_t chunk = half_chunk_rows(half_row_bytes(widths, 2), n);
+    const int64_t cap = chunk < n ? chunk + 1 : n;
+    HalfStage xs, os;
+    half_stage(c, &d, 1, cap, &xs);
+    half_stage(c, &k, 1, cap, &os);
+    const ccz_view xv{X, d, ld};
+    void* const dst[1] = {out};
+    for (int64_t r0 = 0; r0 < n;) {
+      const int64_t rows = half_next_chunk(r0, chunk, n);
+      half_widen(c, dtype, &xv, 1, r0, rows, xs);
+      transform_impl(c, CCZ_F32, xs.fv[0].data, rows, d, xs.fv[0].ld, mean, W, k, const_cast<void*>(os.fv[0].data), os.fv[0].ld);
+      half_narrow(c, dtype, os, rows, dst, &ldo, r0);
+      r0 += rows;
+    }
+    return;
+  }
   if (dtype == CCZ_F32 && project_split_eligible(c, n, d, k, ld, X, ldo)) {
     // large fp32 projections: the split arithmetic of K1 with the conversion in registers (project_split.hip) -- HBM-bound
     project_split(c, static_cast<const float*>(X), n, d, ld, mean, W, k, static_cast<float*>(out), ldo);

@@ -51,6 +51,7 @@ using STR = const char*;
   X(SPLIT_ORDER, INT, 1, LIVE, "0: row blocks fastest in the split pass's grid (the first form), else panels fastest -- gram_split.hip launch_split_pass: A/B") \
   X(SPLIT_WALK, INT, 0, LIVE, "1: every XCD walks the SAME row chunk also when ksplit % 8 == 0 -- gram_split.hip split_row_plan: A/B")       \
   X(LOSS_K1_SPLIT, INT, 1, LIVE, "0 never, 1 split-route partial sums from 32768 rows on, 2 and above from 4096 -- gram_split.hip gram_partials_split_f32: knob") \
+  X(HALF_SCRATCH_MB, REAL, 256.0, LIVE, "MiB of float32 scratch a row chunk of CCZ_BF16 / CCZ_F16 views may take on the routes that widen them (fractions allowed; at least 4 KiB and 2 rows) -- half_io.hip half_chunk_rows: knob; tests shrink it to get several chunks") \
   /* ---- loss, projection, fp32 products (loss.hip, gemm_split.hip, project_split.hip, gemm_big.hip) ---- */                                 \
   X(LOSS_FUSED, INT, 1, ONCE, "0: every shape takes the wide route (super-blocked factorization, 128-tile GEMMs) -- loss.hip narrow_ok: test") \
   X(LOSS_SPLITK, INT, 2, ONCE, "split-K factor of the narrow product stages (1 and below: none) -- loss.hip pair_core: A/B")                  \

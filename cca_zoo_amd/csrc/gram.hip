@@ -29,9 +29,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "hip_common.h"
+#include "half_cvt.h"
 #include "gram_map.h"
 
 namespace ccz {
@@ -823,13 +825,13 @@ __global__ __launch_bounds__(256) void k_colsum(const T* __restrict__ X, int64_t
   double q0 = 0.0, q1 = 0.0;
   int64_t r = r0;
   for (; r + 3 < r1; r += 4) {
-    const double x0 = double(X[(r + 0) * ld + col]), x1 = double(X[(r + 1) * ld + col]);
-    const double x2 = double(X[(r + 2) * ld + col]), x3 = double(X[(r + 3) * ld + col]);
+    const double x0 = to_f64(X[(r + 0) * ld + col]), x1 = to_f64(X[(r + 1) * ld + col]);
+    const double x2 = to_f64(X[(r + 2) * ld + col]), x3 = to_f64(X[(r + 3) * ld + col]);
     a0 += x0; a1 += x1; a2 += x2; a3 += x3;
     if (SQ) { q0 += x0 * x0 + x2 * x2; q1 += x1 * x1 + x3 * x3; }
   }
   for (; r < r1; ++r) {
-    const double x = double(X[r * ld + col]);
+    const double x = to_f64(X[r * ld + col]);
     a0 += x;
     if (SQ) q0 += x * x;
   }
@@ -899,6 +901,26 @@ __global__ __launch_bounds__(256) void k_colsum_pilot(ColsumViews cv, int64_t n,
 __global__ void k_pilot_from_sums(const double* __restrict__ s, int64_t D, double inv_n, float* __restrict__ pilot) {
   const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j < D) pilot[j] = float(s[j] * inv_n);
+}
+
+// The pilot of HALF rows (bf16_t / f16_t views on the split route): the sample mean snapped to the rows' own grid -- a multiple of the
+// type's spacing at the column's scale (rms of the sample; `bits` = 7 for bfloat16, 10 for float16).  Rows of a 2-byte type lie on a
+// coarse grid; with an arbitrary float32 pilot the residual plane mid = bf16((x - p) - hi) is then nearly the SAME number for every
+// row of a binade (about -p), the dropped products mid_i mid_j add up coherently over the rows instead of averaging out, and K1's error
+// stops falling with the row count (4100 x 512 bfloat16 rows: 2.4e-6 in tests/test_gpu_k1_split.py's measure, all of it that term).
+// With the pilot ON the grid, x - p stays on it, hi + mid hold it exactly and the residual is the row's own low bits (the same rows:
+// 4.5e-7).  Any pilot near the mean serves -- the fix-up is exact in p -- so nothing else changes.
+__global__ void k_pilot_on_grid(const double* __restrict__ s, const double* __restrict__ sq, int64_t D, double inv_n, int bits,
+                                float* __restrict__ pilot) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= D) return;
+  const double mean = s[j] * inv_n, rms = sqrt(sq[j] * inv_n);
+  double p = mean;
+  if (isfinite(mean) && isfinite(rms) && rms > 0.0) {
+    const double u = ldexp(1.0, ilogb(rms) - bits);
+    p = rint(mean / u) * u;
+  }
+  pilot[j] = float(p);
 }
 
 // Undo the pilot shift on the d x d side, in fp64, and fold the launch's column sums into the running ones:
@@ -1237,32 +1259,43 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
                     bool time_it, PoolBuf<GramTile>* tile_cache = nullptr, int pilot_mode = 0) {
   Impl* im = impl(c);
   hipStream_t st = stream(c);
-  constexpr bool is32 = sizeof(T) == 4;
+  constexpr bool is32 = sizeof(T) == 4, is16 = sizeof(T) == 2;     // is16: bf16_t / f16_t rows, widened exactly to float32 on load
+  constexpr int dtype = is16 ? (std::is_same<T, bf16_t>::value ? CCZ_BF16 : CCZ_F16) : (is32 ? CCZ_F32 : CCZ_F64);
   const int ncu = std::max(1, im->props.multiProcessorCount);
   // ---- the pilot mode and the arithmetic route first: they decide what the launch needs at all ----
   const int pilot_env = env::once(env::GRAM_PILOT);
   if (pilot_env == 0 || pilot_env == 1) pilot_mode = pilot_env == 1 ? 2 : 0;
-  if (!is32) pilot_mode = 0;                                  // fp64 views accumulate in fp64: nothing to protect
+  if (!is32 && !is16) pilot_mode = 0;                         // fp64 views accumulate in fp64: nothing to protect
   // arithmetic route of fp32 views (ccz_k1_route): the split-bf16 route always shifts by the pilot -- the subtraction rides
   // in its split pass for free and needs no read-back
+  // Half views follow the same rule: the split route's pass reads them where they lie, the fp32 route sees them through the
+  // row-chunk adapter of half_io.hip (which calls back here with float32 scratch rows).
   bool split = false;
-  if (is32) {
+  if (is32 || is16) {
     const char* e = env::once(env::K1_ROUTE);
     const int route_env = !e ? 0 : !strcmp(e, "fp32") ? int(CCZ_K1_FP32) : !strcmp(e, "bf16x2") ? int(CCZ_K1_BF16X2) : 0;
     const int route = c->k1_route != CCZ_K1_AUTO ? c->k1_route : route_env;
     split = (route == CCZ_K1_BF16X2 || (route == CCZ_K1_AUTO && gram_split_worthwhile(n, D))) && n_views <= 16;
     if (split) pilot_mode = 2;
   }
-  c->last_route = !is32 ? CCZ_K1_FP64 : (split ? CCZ_K1_BF16X2 : CCZ_K1_FP32);
+  if constexpr (is16) {
+    if (!split) {
+      half_moments(c, dtype, views, n_views, n, G, pilot_mode, time_it);
+      return c->last_pilot != 0;
+    }
+  }
+  c->last_route = !(is32 || is16) ? CCZ_K1_FP64 : (split ? CCZ_K1_BF16X2 : CCZ_K1_FP32);
   // (k_pilot_fixup runs one grid row per column of G; checked before anything is enqueued where the pilot is already certain)
   if (pilot_mode == 2 && D > 65535) fail(CCZ_EUNSUP, "gram: pilot fix-up supports D <= 65535");
   // the fp32 and fp64 kernels walk a tile table over the views' pointers by a row plan; the split route keeps tables of its own
   // (gram_split.hip) and uses neither
   TileTable tt;
   RowPlan rp;
-  if (!split) {
-    tt = build_tile_table<T>(c, views, n_views, tile_cache);
-    rp = plan_rows<T>(c, views, n_views, n, tt.ntiles, tt.fast);
+  if constexpr (!is16) {
+    if (!split) {
+      tt = build_tile_table<T>(c, views, n_views, tile_cache);
+      rp = plan_rows<T>(c, views, n_views, n, tt.ntiles, tt.fast);
+    }
   }
   // ---- column sums first: they are the means, and for fp32 views they decide (and define) the pilot shift ----
   // (Round 3 tried to hide this 5.4 ms HBM-bound pass under the MFMA-bound K1 on a second stream, with the pilot decided
@@ -1287,19 +1320,23 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
     // their mean -- it is the mean of a strided sample of <= 2048 rows spread over the whole launch (sorted / drifting inputs
     // included).  Any pilot near the mean serves: the fix-up  sum x x' = sum (x-p)(x-p)' + p s' + s p' - n p p'  is exact in p.
     const int64_t nsamp = std::min<int64_t>(n, 2048), stride = n / nsamp;
-    PoolBuf<double> samp(c, D);
-    zero(c, samp, size_t(D) * 8);
+    PoolBuf<double> samp(c, is16 ? 2 * D : D);                 // half rows: the sample's sums of squares too (k_pilot_on_grid)
+    zero(c, samp, size_t(is16 ? 2 * D : D) * 8);
     for (int v = 0; v < n_views; ++v) {
       const int64_t colblocks = (views[v].cols + 255) / 256;
       int64_t rpb = 256;
       while (rpb > 16 && colblocks * ((nsamp + rpb - 1) / rpb) < 2 * int64_t(ncu)) rpb /= 2;
       dim3 grid((unsigned)colblocks, (unsigned)((nsamp + rpb - 1) / rpb));
-      hipLaunchKernelGGL((k_colsum<T, false>), grid, dim3(256), 0, st, static_cast<const T*>(views[v].data), nsamp, views[v].cols,
-                         views[v].ld * stride, samp.get() + off, static_cast<double*>(nullptr), rpb);
+      hipLaunchKernelGGL((k_colsum<T, is16>), grid, dim3(256), 0, st, static_cast<const T*>(views[v].data), nsamp, views[v].cols,
+                         views[v].ld * stride, samp.get() + off, is16 ? samp.get() + D + off : static_cast<double*>(nullptr), rpb);
       off += views[v].cols;
     }
     pilot = pilot_own = PoolBuf<float>(c, D);
-    hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), D, 1.0 / double(nsamp), pilot);
+    if (is16)
+      hipLaunchKernelGGL(k_pilot_on_grid, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), samp.get() + D, D, 1.0 / double(nsamp),
+                         std::is_same<T, bf16_t>::value ? 7 : 10, pilot);
+    else
+      hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), D, 1.0 / double(nsamp), pilot);
     samp.reset();
   }
   for (int v = 0; v < n_views && !split; ++v) {
@@ -1342,7 +1379,7 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   }
 
   if (time_it) CCZ_HIP(hipEventRecord(im->ev[0].get(), st));
-  if (split) gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it);
+  if (split) gram_split_f32(c, views, n_views, n, G, D, pilot, s_launch, time_it, dtype);
   else if (is32) launch_gram_f32(c, tt, rp, n, G, D, pilot);
   else launch_gram_f64(c, tt, rp, n, G, D);
   CCZ_LAUNCH_CHECK();
@@ -1555,7 +1592,8 @@ void gram_partials_release(ccz_ctx* c, GramPartials* gp) {
 void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int64_t n_rows, bool on_device,
                   double* moments, bool accumulate, int pilot_mode, bool time_it) {
   if (!views || n_views < 1 || !moments) fail(CCZ_EINVAL, "moments: null argument");
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "moments: dtype must be CCZ_F32 or CCZ_F64");
+  if (dtype != CCZ_F32 && dtype != CCZ_F64 && !is_half_dtype(dtype)) fail(CCZ_EUNSUP, "moments: dtype must be CCZ_F32, CCZ_F64, CCZ_BF16 or CCZ_F16");
+  if (is_half_dtype(dtype) && !on_device) fail(CCZ_EUNSUP, "moments: CCZ_BF16 / CCZ_F16 views must be on the device");
   if (n_rows < 0) fail(CCZ_EINVAL, "moments: negative row count");
   int64_t D = 0;
   for (int v = 0; v < n_views; ++v) {
@@ -1572,6 +1610,8 @@ void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int
   const size_t es = dtype == CCZ_F32 ? 4 : 8;
   if (on_device) {
     if (dtype == CCZ_F32) launch_moments<float>(c, views, n_views, n_rows, G, s, D, time_it, nullptr, pilot_mode);
+    else if (dtype == CCZ_BF16) launch_moments<bf16_t>(c, views, n_views, n_rows, G, s, D, time_it, nullptr, pilot_mode);
+    else if (dtype == CCZ_F16) launch_moments<f16_t>(c, views, n_views, n_rows, G, s, D, time_it, nullptr, pilot_mode);
     else launch_moments<double>(c, views, n_views, n_rows, G, s, D, time_it, nullptr, 0);
     return;
   }

@@ -37,12 +37,15 @@
 #include <vector>
 
 #include "hip_common.h"
+#include "half_cvt.h"
 #include "gram_map.h"
 #include "split_mma.h"
 
 namespace ccz {
 
-constexpr int SP_MAXV = 16;          // views per launch (their base pointers travel as a kernel argument, the tables hold no pointers)
+typedef unsigned int sp_v2u32 __attribute__((ext_vector_type(2)));   // four 2-byte elements of a half row
+
+constexpr int SP_MAXV = 16;         // views per launch (their base pointers travel as a kernel argument, the tables hold no pointers)
 
 struct SplitPanel {
   int32_t view;          // which view
@@ -52,7 +55,7 @@ struct SplitPanel {
 };
 
 struct SplitViews {
-  const float* data[SP_MAXV];
+  const void* data[SP_MAXV];       // rows of the launch's input type (float, or a 2-byte format widened on load)
   int64_t ld[SP_MAXV];
 };
 
@@ -65,10 +68,13 @@ struct SplitTile {
 };
 
 // ---------------------------------------------------------------------------
-// split pass: fp32 rows [r0, r0 + nrows) of every view -> the two bf16 planes of this launch (k-steps [0, ksteps)),
+// split pass: rows [r0, r0 + nrows) of every view -> the two bf16 planes of this launch (k-steps [0, ksteps)),
 // and msq[j] += sum_k mid_kj^2.  grid = (row blocks of rb <= SP_RB rows, panels).  A thread owns 4 consecutive columns and, per
 // pass, the 8 rows of one k half: its 8 float4 loads are one 1 KiB-per-wave row segment each, its stores 64 contiguous
 // bytes per plane.  HBM-bound: 4 bytes in, 4 bytes out per element.
+// T = float, or bf16_t / f16_t (half_cvt.h): the same thread then loads 8 bytes per row and widens them exactly -- 2 bytes in,
+// 4 out, no float32 copy of the view anywhere; everything after the load is the float32 code.  ALIGNED: every row of every view
+// starts on a 4-element boundary (16 bytes of float, 8 bytes of a half type) and whole 4-column groups are in or out.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void sp_wave_lds_sync() {    // lanes of ONE wave exchange data through LDS (see cholinv.hip::wave_lds_sync)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -82,7 +88,7 @@ __device__ __forceinline__ void sp_wave_lds_sync() {    // lanes of ONE wave exc
 // requests per clock on 128 L2 channels.  So the eight lanes of a column tile swap pieces through a wave-private 4 KB of LDS
 // (no workgroup barrier) until store e of lane j is piece 8 e + j: every wave-level store is eight whole 128-byte lines
 // (2.03e8 L2 requests per 262144 rows; the pass at the metric shape 14.0 -> 12.4 ms).
-template <bool ALIGNED>
+template <typename T, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_split_bf16x2(const SplitPanel* __restrict__ panels, SplitViews vws, int64_t r0, int64_t nrows, int64_t ksteps,
                                                       const float* __restrict__ pilot, char* __restrict__ planes,
                                                       double* __restrict__ msq, double* __restrict__ csum, int rb, int panel_fast) {
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(256) void k_split_bf16x2(const SplitPanel* __restri
     cok[e] = c0 + e < pn.width;
     if (pilot && cok[e]) p[e] = pilot[pn.gcol0 + c0 + e];
   }
-  const float* __restrict__ X = vws.data[pn.view] + pn.col0 + c0;
+  const T* __restrict__ X = static_cast<const T*>(vws.data[pn.view]) + pn.col0 + c0;
   const int64_t pld = vws.ld[pn.view];
   char* out = planes + int64_t(pidx) * ksteps * SP_PSTEP + (cg >> 3) * 1024 + (cg & 7) * 64;
   sp_v4f32 q = {0.f, 0.f, 0.f, 0.f};
@@ -116,13 +122,19 @@ __global__ __launch_bounds__(256) void k_split_bf16x2(const SplitPanel* __restri
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const bool rok = row + k < nrows;
-      const float* src = X + (r0 + (rok ? row + k : 0)) * pld;
+      const T* src = X + (r0 + (rok ? row + k : 0)) * pld;
       if (ALIGNED) {
         v[k] = p;                                          // (whole 4-column groups are inside or outside the panel's width)
-        if (cok[0]) v[k] = __builtin_nontemporal_load(reinterpret_cast<const sp_v4f32*>(src));   // read once: keep L2 / MALL for the planes
+        if constexpr (sizeof(T) == 4) {
+          if (cok[0]) v[k] = __builtin_nontemporal_load(reinterpret_cast<const sp_v4f32*>(src));   // read once: keep L2 / MALL for the planes
+        } else if (cok[0]) {
+          const sp_v2u32 w = __builtin_nontemporal_load(reinterpret_cast<const sp_v2u32*>(src));   // 4 elements of 2 bytes
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[k][e] = widen(T{uint16_t(w[e >> 1] >> (16 * (e & 1)))});
+        }
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[k][e] = cok[e] ? src[e] : 0.f;
+        for (int e = 0; e < 4; ++e) v[k][e] = cok[e] ? widen(src[e]) : 0.f;
       }
       if (!rok) v[k] = p;                                  // d = 0 exactly for the rows that pad the last k-step
       else if (csum) {
@@ -389,25 +401,30 @@ static SplitTables split_tables(ccz_ctx* c, const int64_t* cols, int n_views) {
   return tb;
 }
 
-static bool split_views_arg(const ccz_view* views, int n_views, SplitViews* vws) {
+// (row starts on 4-element boundaries: 16 bytes of float, 8 bytes of a half type)
+static bool split_views_arg(const ccz_view* views, int n_views, SplitViews* vws, int dtype = CCZ_F32) {
   bool aligned = true;
+  const uintptr_t bytes = dtype == CCZ_F32 ? 16 : 8;
   for (int v = 0; v < n_views; ++v) {
-    vws->data[v] = static_cast<const float*>(views[v].data);
+    vws->data[v] = views[v].data;
     vws->ld[v] = views[v].ld;
-    if (views[v].cols % 4 != 0 || views[v].ld % 4 != 0 || reinterpret_cast<uintptr_t>(views[v].data) % 16 != 0) aligned = false;
+    if (views[v].cols % 4 != 0 || views[v].ld % 4 != 0 || reinterpret_cast<uintptr_t>(views[v].data) % bytes != 0) aligned = false;
   }
   return aligned;
 }
 
 static void launch_split_pass(ccz_ctx* c, const SplitTables& tb, const SplitViews& vws, bool aligned, int64_t r0, int64_t rows, int64_t ksteps,
-                              const float* pilot, char* planes, double* msq, double* colsum) {
+                              const float* pilot, char* planes, double* msq, double* colsum, int dtype = CCZ_F32) {
   const int rb = split_rows_per_block(ksteps * SP_K, tb.np, std::max(1, impl(c)->props.multiProcessorCount));
   const unsigned nrb = (unsigned)((ksteps * SP_K + rb - 1) / rb);
   // panels fastest in the grid (CCZ_SPLIT_ORDER=0: row blocks fastest, the first form).  Measured at the
   // metric shape, alternating runs (tools/r6_split_order.sh): 12.1 / 10.7 / 10.6 ms against 12.6 / 12.3 / 11.9 -- never slower.
   const int panel_fast = (env::live(env::SPLIT_ORDER) != 0 && nrb <= 65535u) ? 1 : 0;
   const dim3 grid = panel_fast ? dim3((unsigned)tb.np, nrb) : dim3(nrb, (unsigned)tb.np);
-  hipLaunchKernelGGL(aligned ? &k_split_bf16x2<true> : &k_split_bf16x2<false>, grid, dim3(256), 0, stream(c), tb.panels, vws, r0, rows, ksteps, pilot, planes, msq, colsum, rb, panel_fast);
+  auto* kern = aligned ? &k_split_bf16x2<float, true> : &k_split_bf16x2<float, false>;
+  if (dtype == CCZ_BF16) kern = aligned ? &k_split_bf16x2<bf16_t, true> : &k_split_bf16x2<bf16_t, false>;
+  else if (dtype == CCZ_F16) kern = aligned ? &k_split_bf16x2<f16_t, true> : &k_split_bf16x2<f16_t, false>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream(c), tb.panels, vws, r0, rows, ksteps, pilot, planes, msq, colsum, rb, panel_fast);
 }
 
 // The K1-layout planes of ONE fp32 matrix X (rows x cols, ld): panels of 256 columns, `ksteps` k-steps of 16 rows each (rows past
@@ -515,13 +532,14 @@ bool gram_split_worthwhile(int64_t n, int64_t D) {
 }
 
 // G (upper tiles) += sum over rows of d d' for d = x - pilot (pilot may be null: d = x), through the split-bf16 route;
+// dtype: the views' element type (CCZ_F32, or CCZ_BF16 / CCZ_F16: widened exactly by the split pass's load);
 // colsum (may be null) += the exact fp64 column sums of x, gathered by the split pass on its way over the rows.
 // Per row super-chunk one straight chain on the handle's stream: zero msq, split pass, MFMA kernel, reduce.  With time_it four HIP
 // events bracket the three stages (one host wait per row super-chunk) into c->last_split_ms / last_mfma_ms / last_reduce_ms.
 // (Round 6 also built a piped form, the split pass of the next row piece on a CU-masked side stream under the MFMA kernel of the
 // current one: slower in every setting, profiles/r06_split_pipe_sweep.log and DESIGN.md section 7 item 2, and removed.)
 void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, double* G, int64_t D, const float* pilot, double* colsum,
-                    bool time_it) {
+                    bool time_it, int dtype) {
   Impl* im = impl(c);
   hipStream_t st = stream(c);
   // ---- panels and tiles (device tables cached with the handle by the views' widths) ----
@@ -531,7 +549,7 @@ void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   for (int v = 0; v < n_views; ++v) cols[v] = views[v].cols;
   const SplitTables tb = split_tables(c, cols, n_views);
   SplitViews vws{};
-  const bool aligned = split_views_arg(views, n_views, &vws);
+  const bool aligned = split_views_arg(views, n_views, &vws, dtype);
   const int np = tb.np, ntiles = tb.ntiles;
   PoolBuf<double> msq(c, D);
   // ---- rows per launch (scratch budget) and per workgroup ----
@@ -578,7 +596,7 @@ void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
     const SplitRowPlan& rp = r0 + launch_rows < n ? rp_full : rp_last;
     zero(c, msq, size_t(D) * 8);
     if (time_it) CCZ_HIP(hipEventRecord(ev[0], st));
-    launch_split_pass(c, tb, vws, aligned, r0, rows, ksteps, pilot, planes, msq, colsum);
+    launch_split_pass(c, tb, vws, aligned, r0, rows, ksteps, pilot, planes, msq, colsum, dtype);
     if (time_it) CCZ_HIP(hipEventRecord(ev[1], st));
     hipLaunchKernelGGL(k_gram_bf16x2, dim3((unsigned)rp.nblocks), dim3(256), fifo_bytes, st, tb.tiles, ntiles, rp.per_xcd, rp.ksplit, planes.get(), ksteps,
                        rp.steps_per_wg, partial.get());

@@ -244,7 +244,7 @@ struct GramPartials {
 // accumulator, the diagonal's mid'mid added back exactly): G (upper tiles) += sum_rows (x - pilot)(x - pilot)'.
 bool gram_split_worthwhile(int64_t n, int64_t D);
 void gram_split_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, double* G, int64_t D, const float* pilot, double* colsum,
-                    bool time_it);
+                    bool time_it, int dtype = CCZ_F32);
 // gemm_split.hip: the two-view loss backward [C1 | C2] = alpha (*alpha_dev) ([A1 | A2] - 1 mean') Gamma on the bf16 pipe (same split arithmetic)
 bool gemm_split_pair_eligible(int64_t M, int64_t N, int64_t K, int64_t K1, int64_t nsplit, const void* A1, int64_t lda1, const void* A2,
                               int64_t lda2, const void* C1, int64_t ldc1, const void* C2, int64_t ldc2);
@@ -269,6 +269,25 @@ void gram_partials_release(ccz_ctx* c, GramPartials* gp);
 // time_it: record HIP events around the Gram and column-sum kernels (costs a host wait at the end)
 void moments_impl(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int64_t n_rows,
                   bool on_device, double* moments, bool accumulate, int pilot_mode = 1, bool time_it = true);
+// half_io.hip: the 2-byte formats (CCZ_BF16 / CCZ_F16, half_cvt.h) in front of the float32 routes.  A HalfStage is float32 scratch from
+// the handle's pool for `rows` rows of up to 16 views, with leading dimensions that suit the float32 kernels' aligned paths;
+// half_widen fills it from rows [r0, r0 + rows) of half views, half_narrow rounds float32 rows into half rows (one launch per 8 views).
+inline bool is_half_dtype(int dtype) { return dtype == CCZ_BF16 || dtype == CCZ_F16; }
+constexpr int HALF_MAXV = 16;
+struct HalfStage {
+  PoolBuf<float> buf;
+  ccz_view fv[HALF_MAXV];          // the float32 views (data inside buf)
+  int m = 0;
+  int64_t rows = 0;
+};
+int64_t half_row_bytes(const int64_t* cols, int m);                       // float32 scratch bytes per row of views of these widths
+int64_t half_chunk_rows(int64_t row_bytes, int64_t n);                    // rows per chunk within CCZ_HALF_SCRATCH_MB (at least 2; n when all fit)
+int64_t half_next_chunk(int64_t r0, int64_t chunk, int64_t n);            // rows of the chunk at r0: a 1-row tail is folded into its neighbour
+void half_stage(ccz_ctx* c, const int64_t* cols, int m, int64_t rows, HalfStage* st);
+void half_widen(ccz_ctx* c, int dtype, const ccz_view* views, int m, int64_t r0, int64_t rows, const HalfStage& st);
+void half_narrow(ccz_ctx* c, int dtype, const HalfStage& st, int64_t rows, void* const* dst, const int64_t* ldd, int64_t r0);
+// ccz_moments on the fp32 route: moments += those of the widened row chunks (each with its own pilot, like streamed host views)
+void half_moments(ccz_ctx* c, int dtype, const ccz_view* views, int n_views, int64_t n, double* moments, int pilot_mode, bool time_it);
 // small host -> device copy through a ring of pinned slots: asynchronous on the handle's stream (the pageable source
 // may be reused as soon as this returns); larger than a slot falls back to the synchronous copy
 void h2d_small(ccz_ctx* c, void* dst, const void* src, size_t bytes);

@@ -500,7 +500,7 @@ struct LossShape {
 };
 
 static LossShape loss_shape(const ccz_view* z, int m, int64_t n, int dtype, const char* what) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "%s: dtype must be CCZ_F32 or CCZ_F64", what);
+  if (dtype != CCZ_F32 && dtype != CCZ_F64 && !is_half_dtype(dtype)) fail(CCZ_EUNSUP, "%s: dtype must be CCZ_F32, CCZ_F64, CCZ_BF16 or CCZ_F16", what);
   if (!z) fail(CCZ_EINVAL, "%s: null argument", what);
   if (m < 2 || m > LMAXV) fail(CCZ_EUNSUP, "%s: 2 .. %d views are supported, got %d", what, LMAXV, m);
   if (n < 2) fail(CCZ_EINVAL, "%s: bad shape (at least 2 rows are required)", what);
@@ -530,6 +530,19 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
   const LossShape sh = loss_shape(z, m, n, dtype, "cca_loss");
   if (!loss_dev) fail(CCZ_EINVAL, "cca_loss: null argument");
   const int64_t D = sh.D;
+  // Half views (CCZ_BF16 / CCZ_F16; the loss element and the state are float32's).  A batch whose float32 image fits the scratch
+  // budget is widened once and takes the float32 forward below unchanged, fast paths included; a larger one takes the general route,
+  // where ccz_moments' machinery reads the half rows (split pass, or row chunks through the adapter).
+  const bool half = is_half_dtype(dtype);
+  if (half && half_chunk_rows(half_row_bytes(sh.dims, m), n) == n) {
+    HalfStage hs;
+    half_stage(c, sh.dims, m, n, &hs);
+    half_widen(c, dtype, z, m, 0, n, hs);
+    pair_loss_forward_impl(c, CCZ_F32, hs.fv, m, n, eps, loss_dev, state);
+    return;
+  }
+  const int vdtype = dtype;            // the views' element type: what K1 reads
+  if (half) dtype = CCZ_F32;           // ... and the arithmetic, the loss element and the state behind it
   hipStream_t st = stream(c);
   const bool narrow = narrow_ok(sh.dims, m);
   const bool want = state != nullptr;
@@ -543,7 +556,7 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
   const int fast_env = env::once(env::LOSS_FAST);
   GramPartials gp;
   bool fast = false;
-  if (fast_env && narrow && dtype == CCZ_F32) fast = gram_partials_f32(c, z, m, n, &gp);
+  if (fast_env && narrow && vdtype == CCZ_F32) fast = gram_partials_f32(c, z, m, n, &gp);
   struct Release {
     ccz_ctx* c; GramPartials* gp; bool on;
     ~Release() { if (on) gram_partials_release(c, gp); }
@@ -554,7 +567,7 @@ void pair_loss_forward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, int
     // general route: the moments [G | s] through ccz_moments' machinery.  Wide views (n ~ 1e6 rows x 8192): the automatic
     // pilot choice (one 2 D-double read-back) keeps centred data on the faster FIFO kernel.
     DBuf mom(c, D * D + D);
-    moments_impl(c, dtype, z, m, n, true, mom, false, dtype == CCZ_F32 ? (narrow ? 2 : 1) : 0, false);
+    moments_impl(c, vdtype, z, m, n, true, mom, false, dtype == CCZ_F32 ? (narrow ? 2 : 1) : 0, false);
     pair_core(c, mom, n, sh.dims, m, eps, want, acc, gamma, mean, info.get(), bias, nullptr, narrow);
   }
   if (want) {
@@ -584,6 +597,28 @@ void pair_loss_backward_impl(ccz_ctx* c, int dtype, const ccz_view* z, int m, in
     }
   }
   if (!any) return;
+  if (is_half_dtype(dtype)) {
+    // row chunks: widen the views' rows, the float32 backward below on the scratch (grad_out, a float32 element, applied inside its
+    // products), and ONE rounding of the float32 gradient rows into the caller's
+    int64_t gcols[LMAXV], zg[2 * LMAXV];
+    void* gdst[LMAXV];
+    for (int a = 0; a < m; ++a) { zg[a] = sh.dims[a]; gcols[a] = zg[m + a] = g[a] ? sh.dims[a] : 0; }   // (no scratch for a gradient nobody wants)
+    const int64_t chunk = half_chunk_rows(half_row_bytes(zg, 2 * m), n);
+    HalfStage zs, gs;
+    half_stage(c, sh.dims, m, chunk < n ? chunk + 1 : n, &zs);
+    half_stage(c, gcols, m, chunk < n ? chunk + 1 : n, &gs);
+    int64_t ldf[LMAXV];
+    void* gf[LMAXV];
+    for (int a = 0; a < m; ++a) { ldf[a] = gs.fv[a].ld; gf[a] = g[a] ? const_cast<void*>(gs.fv[a].data) : nullptr; gdst[a] = g[a]; }
+    for (int64_t r0 = 0; r0 < n;) {
+      const int64_t rows = half_next_chunk(r0, chunk, n);
+      half_widen(c, dtype, z, m, r0, rows, zs);
+      pair_loss_backward_impl(c, CCZ_F32, zs.fv, m, rows, state, grad_out, gf, ldf);
+      half_narrow(c, dtype, gs, rows, gdst, ldg, r0);
+      r0 += rows;
+    }
+    return;
+  }
   hipStream_t st = stream(c);
   const double* gamma = static_cast<const double*>(state);
   const double* bias = gamma + D * D;

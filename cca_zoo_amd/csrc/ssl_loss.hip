@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "hip_common.h"
+#include "half_cvt.h"
 #include "reduce.h"
 
 namespace ccz {
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(256) void k_sqdiff(const T* __restrict__ z1, int64_
     const VecOf<T, V> y = *reinterpret_cast<const VecOf<T, V>*>(z2 + row * ld2 + col * V);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const double df = double(x.v[k]) - double(y.v[k]);
+      const double df = to_f64(x.v[k]) - to_f64(y.v[k]);
       acc += df * df;
     }
     row += srow;
@@ -299,7 +300,11 @@ int64_t moment_loss_state_bytes_impl(int dtype, int64_t d, int m) {
 
 void moment_loss_forward_impl(ccz_ctx* c, int dtype, int kind, const double* params, const ccz_view* z, int m, int64_t n, const ccz_view* zi,
                               int64_t n_ind, void* loss_dev, double* terms_dev, void* state, void* state_ind) {
-  if (dtype != CCZ_F32 && dtype != CCZ_F64) fail(CCZ_EUNSUP, "moment loss: dtype must be CCZ_F32 or CCZ_F64");
+  if (dtype != CCZ_F32 && dtype != CCZ_F64 && !is_half_dtype(dtype)) fail(CCZ_EUNSUP, "moment loss: dtype must be CCZ_F32, CCZ_F64, CCZ_BF16 or CCZ_F16");
+  // half views: K1 and the squared difference read them where they lie (widened exactly on load); the map, the loss element and the
+  // state behind them are float32's
+  const int vdtype = dtype;
+  if (is_half_dtype(dtype)) dtype = CCZ_F32;
   if (kind < CCZ_MOMENT_EY || kind > CCZ_MOMENT_SDL) fail(CCZ_EINVAL, "moment loss: unknown kind %d", kind);
   if (!z || !loss_dev) fail(CCZ_EINVAL, "moment loss: null argument");
   const bool two = kind == CCZ_MOMENT_BARLOW || kind == CCZ_MOMENT_VICREG;
@@ -320,22 +325,29 @@ void moment_loss_forward_impl(ccz_ctx* c, int dtype, int kind, const double* par
   hipStream_t st = stream(c);
   const int pilot = dtype == CCZ_F32 ? 2 : 0;       // always shifted, decided on the device: no read-back
   DBuf mom(c, D * D + D), momi(c, zi ? D * D + D : 0);
-  moments_impl(c, dtype, z, m, n, true, mom, false, pilot, false);
-  if (zi) moments_impl(c, dtype, zi, m, n_ind, true, momi, false, pilot, false);
+  moments_impl(c, vdtype, z, m, n, true, mom, false, pilot, false);
+  if (zi) moments_impl(c, vdtype, zi, m, n_ind, true, momi, false, pilot, false);
   int nsq = 0;
   DBuf sq_part;
   if (kind == CCZ_MOMENT_VICREG || kind == CCZ_MOMENT_SDL) {
-    const bool f32 = dtype == CCZ_F32;
-    const bool vec = vec_ok(z[0], 16, f32 ? 4 : 2) && vec_ok(z[1], 16, f32 ? 4 : 2);
-    const int64_t items = n * d / (vec ? (f32 ? 4 : 2) : 1);
+    const bool f32 = vdtype == CCZ_F32, f64 = vdtype == CCZ_F64;
+    const int per16 = f32 ? 4 : (f64 ? 2 : 8);          // elements of a 16-byte load
+    const bool vec = vec_ok(z[0], 16, per16) && vec_ok(z[1], 16, per16);
+    const int64_t items = n * d / (vec ? per16 : 1);
     nsq = int(std::min<int64_t>(SQ_MAX_BLOCKS, std::max<int64_t>(1, (items + 1023) / 1024)));
     sq_part = DBuf(c, nsq);
     if (f32) {
       if (vec) launch_sqdiff<float, 4>(st, nsq, z[0], z[1], n, sq_part);
       else launch_sqdiff<float, 1>(st, nsq, z[0], z[1], n, sq_part);
-    } else {
+    } else if (f64) {
       if (vec) launch_sqdiff<double, 2>(st, nsq, z[0], z[1], n, sq_part);
       else launch_sqdiff<double, 1>(st, nsq, z[0], z[1], n, sq_part);
+    } else if (vdtype == CCZ_BF16) {
+      if (vec) launch_sqdiff<bf16_t, 8>(st, nsq, z[0], z[1], n, sq_part);
+      else launch_sqdiff<bf16_t, 1>(st, nsq, z[0], z[1], n, sq_part);
+    } else {
+      if (vec) launch_sqdiff<f16_t, 8>(st, nsq, z[0], z[1], n, sq_part);
+      else launch_sqdiff<f16_t, 1>(st, nsq, z[0], z[1], n, sq_part);
     }
     CCZ_LAUNCH_CHECK();
   }

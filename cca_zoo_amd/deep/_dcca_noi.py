@@ -4,7 +4,8 @@ Only ``_BatchWhiten`` -- the part of that file on the covariance / eigen hot pat
 Lightning ``DCCA_NOI`` trainer class is outside SURVEY.md section 8.  Per training step: the uncentred
 second moment ``x'x`` comes from K1 (``ccz_moments``), the running matrix is an exponential moving average,
 its clamped inverse square root is the device Jacobi EVD (``ccz_inv_sqrtm``) and ``x @ w`` / its gradient
-``g @ w'`` are ``ccz_transform`` GEMMs.  No gradient flows through ``w`` (as in the reference).
+``g @ w'`` are ``ccz_transform`` GEMMs.  No gradient flows through ``w`` (as in the reference).  A bfloat16 / float16 batch goes
+through the same calls (widened exactly on load) and comes back in its own dtype.
 """
 
 from __future__ import annotations
@@ -58,8 +59,7 @@ class _BatchWhiten(nn.Module):
         mom = torch.empty(d * d + d, dtype=torch.float64, device=x.device)
         sp = int(torch.cuda.current_stream(x.device).cuda_stream)
         h.acquire(sp)                                      # enqueue-only: the stream hand-over happens on the device
-        h.moments([(a.data_ptr(), d, a.stride(0))], n, _backend.F32 if a.dtype == torch.float32 else _backend.F64,
-                  True, mom.data_ptr(), pilot=True, timed=False)
+        h.moments([(a.data_ptr(), d, a.stride(0))], n, _backend.dtype_code(a.dtype), True, mom.data_ptr(), pilot=True, timed=False)
         h.moments_symmetrize(mom.data_ptr(), d)
         h.release(sp)
         batch_cov = (mom[: d * d].reshape(d, d) / n).to(self.running_covar.dtype)

@@ -12,6 +12,9 @@ the sample-side product ``Z Gamma - 1 (mean' Gamma_c)`` of ``ccz_pair_loss_backw
 No centred copies, no n x d x d products per term, no boolean masks, no autograd through any of it; enqueue-only in torch's
 current stream.
 
+``torch.bfloat16`` / ``torch.float16`` views are accepted as a format (see ``objectives.py``): the objective and the terms are then
+float32 0-dim tensors and every gradient is rounded once into its input's dtype.
+
 Differences from the reference, on purpose:
 
 * all views of a list must have the same width (the reference fails or broadcasts in ``torch`` depending on the loss);
@@ -29,7 +32,7 @@ from torch.autograd.function import once_differentiable
 import torch.nn as nn
 
 from cca_zoo_amd import _backend
-from cca_zoo_amd.deep.objectives import _require_cuda, _stream_ptr, _view_of, _views_of
+from cca_zoo_amd.deep.objectives import _loss_dtype, _require_cuda, _stream_ptr, _view_of, _views_of
 
 __all__ = ["EYLoss", "BarlowTwinsLoss", "VICRegLoss", "SDLLoss"]
 
@@ -74,8 +77,8 @@ def _evaluate(kind: int, params, vs, vis, want_state: bool, want_state_ind: bool
     dt, dev = vs[0].dtype, vs[0].device
     m, n, d = len(vs), int(vs[0].shape[0]), int(vs[0].shape[1])
     h = _backend.handle_for(vs)
-    code = _backend.F32 if dt == torch.float32 else _backend.F64
-    loss = torch.empty((), dtype=dt, device=dev)
+    code = _backend.dtype_code(dt)
+    loss = torch.empty((), dtype=_loss_dtype(dt), device=dev)       # half views: a float32 element
     terms = torch.empty(3, dtype=torch.float64, device=dev) if want_terms else None
 
     def new_state():
@@ -135,8 +138,8 @@ class _MomentLossFn(torch.autograd.Function):
         groups = [(saved[:m], state, ctx.wanted[:m]), (saved[m:], state_ind, ctx.wanted[m:])]
         dt = saved[0].dtype
         h = _backend.handle_for(saved[:m])
-        go = grad_out.detach().to(device=saved[0].device, dtype=dt).reshape(()).contiguous()
-        code = _backend.F32 if dt == torch.float32 else _backend.F64
+        go = grad_out.detach().to(device=saved[0].device, dtype=_loss_dtype(dt)).reshape(()).contiguous()
+        code = _backend.dtype_code(dt)
         out = []
         sp = _stream_ptr(saved[0])
         for vs, st, wanted in groups:
@@ -186,7 +189,7 @@ class _MomentLoss(nn.Module):
             loss, terms, _, _ = _evaluate(self._kind, self._params(), _prepare(zs, dt), _prepare(zi, dt) if zi else None, False, False, True)
             out = {"objective": loss}
             for i, k in enumerate(_TERM_KEYS[self._kind]):
-                out[k] = terms[i].to(dt)
+                out[k] = terms[i].to(_loss_dtype(dt))
         return out
 
 

@@ -14,6 +14,11 @@ input gradients (row 9) as four MFMA GEMMs, instead of autograd through ``eigh``
 
 Inputs must be CUDA tensors: there is no CPU implementation in this package.
 
+``torch.bfloat16`` / ``torch.float16`` inputs (``torch.autocast``) are an input / output FORMAT, not an arithmetic: libccz widens
+an element exactly on load, computes on its float32 routes and rounds every gradient once, after the upstream gradient has been
+applied in float32 (a ``GradScaler`` works).  The loss of such a batch is a float32 0-dim tensor, each gradient has its input's
+dtype and shape, and no ``.float()`` copy of a view is made.  Mixed dtypes follow the first view.
+
 Stream contract (the reference's ``training_step``: cca_zoo/deep/_base.py:78-104).  The loss is an
 ordinary node of the autograd graph: libccz's stream is joined to ``torch.cuda.current_stream()`` on the DEVICE before and
 after the call (``ccz_stream_acquire`` / ``ccz_stream_release``; nothing at all for the default stream, with which the
@@ -65,8 +70,17 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
             f"{what}: expected a CUDA (ROCm) tensor; cca_zoo_amd runs on the MI355X only "
             "and has no CPU fallback"
         )
-    if t.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"{what}: dtype must be float32 or float64, got {t.dtype}")
+    if t.dtype not in (torch.float32, torch.float64, torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: dtype must be float32, float64, bfloat16 or float16, got {t.dtype}")
+
+
+#: the 2-byte formats (``torch.autocast``): an input / output FORMAT -- libccz widens an element exactly on load, computes on its
+#: float32 routes and rounds every gradient once.  The loss of such a batch is a float32 0-dim tensor (autocast's convention).
+_HALF = (torch.bfloat16, torch.float16)
+
+
+def _loss_dtype(dt: torch.dtype) -> torch.dtype:
+    return torch.float32 if dt in _HALF else dt
 
 
 class _ShardedCCALossFn(torch.autograd.Function):
@@ -92,8 +106,7 @@ class _ShardedCCALossFn(torch.autograd.Function):
         mom = torch.empty(D * D + D, dtype=torch.float64, device=dev)
         sp = _stream_ptr(zcat)
         h.acquire(sp)
-        h.moments([(zcat.data_ptr(), D, D)], n_local, _backend.F32 if dt == torch.float32 else _backend.F64, True, mom.data_ptr(),
-                  pilot=True, timed=False)
+        h.moments([(zcat.data_ptr(), D, D)], n_local, _backend.dtype_code(dt), True, mom.data_ptr(), pilot=True, timed=False)
         npk = D * (D + 1) // 2 + D
         packed = torch.empty(npk + 1, dtype=torch.float64, device=dev)
         h.moments_pack(mom.data_ptr(), D, packed.data_ptr())
@@ -110,14 +123,20 @@ class _ShardedCCALossFn(torch.autograd.Function):
                                            C.byref(loss_h), C.c_void_p(gamma.data_ptr()) if need else None,
                                            C.c_void_p(mean.data_ptr()) if need else None))
         if need:
-            g = _project(zcat, mean, gamma)
-            ctx.save_for_backward(g)
+            ctx.lazy = dt in _HALF
+            if ctx.lazy:
+                ctx.save_for_backward(zcat, mean, gamma)       # half rows: the upstream gradient goes INTO the product (one rounding)
+            else:
+                ctx.save_for_backward(_project(zcat, mean, gamma))
             ctx.split = (d1, d2)
             ctx.dtypes = (z1.dtype, z2.dtype)
-        return torch.tensor(loss_h.value, dtype=dt, device=dev)
+        return torch.tensor(loss_h.value, dtype=_loss_dtype(dt), device=dev)
 
     @staticmethod
     def backward(ctx, grad_out):
+        if ctx.lazy:
+            g1, g2 = torch.split(_project_scaled(*ctx.saved_tensors, grad_out), ctx.split, dim=1)
+            return g1.to(ctx.dtypes[0]), g2.to(ctx.dtypes[1]), None
         (g,) = ctx.saved_tensors
         g1, g2 = torch.split(g, ctx.split, dim=1)
         return (grad_out * g1).to(ctx.dtypes[0]), (grad_out * g2).to(ctx.dtypes[1]), None
@@ -144,8 +163,8 @@ class _PairLossFn(torch.autograd.Function):
         h = _backend.handle_for(vs)
         _raise_pending(h)
         need = any(ctx.needs_input_grad[2:])
-        loss = torch.empty((), dtype=dt, device=vs[0].device)
-        code = _backend.F32 if dt == torch.float32 else _backend.F64
+        loss = torch.empty((), dtype=_loss_dtype(dt), device=vs[0].device)
+        code = _backend.dtype_code(dt)
         state = None
         if need:
             dims = (C.c_int64 * m)(*[int(v.shape[1]) for v in vs])
@@ -177,7 +196,7 @@ class _PairLossFn(torch.autograd.Function):
         m = len(vs)
         dt = vs[0].dtype
         h = _backend.handle_for(vs)
-        go = grad_out.detach().to(device=vs[0].device, dtype=dt).reshape(()).contiguous()
+        go = grad_out.detach().to(device=vs[0].device, dtype=_loss_dtype(dt)).reshape(()).contiguous()
         grads = [torch.empty_like(v, memory_format=torch.contiguous_format) if w else None for v, w in zip(vs, ctx.wanted)]
         gp = (C.c_void_p * m)(*[g.data_ptr() if g is not None else None for g in grads])
         ldg = (C.c_int64 * m)(*[int(g.stride(0)) if g is not None else 0 for g in grads])
@@ -185,7 +204,7 @@ class _PairLossFn(torch.autograd.Function):
         sp = _stream_ptr(vs[0])
         h.adopt(sp)
         try:
-            h.check(h.lib.ccz_pair_loss_backward(h.raw, _backend.F32 if dt == torch.float32 else _backend.F64, views, m, int(vs[0].shape[0]),
+            h.check(h.lib.ccz_pair_loss_backward(h.raw, _backend.dtype_code(dt), views, m, int(vs[0].shape[0]),
                                                  C.c_void_p(state.data_ptr()), C.c_void_p(go.data_ptr()), gp, ldg))
         finally:
             h.acquire(sp)
@@ -335,8 +354,7 @@ class _ShardedPairLossFn(torch.autograd.Function):
         mom = torch.empty(D * D + D, dtype=torch.float64, device=dev)
         sp = _stream_ptr(zcat)
         h.acquire(sp)
-        h.moments([(zcat.data_ptr(), D, D)], n_local, _backend.F32 if dt == torch.float32 else _backend.F64, True, mom.data_ptr(),
-                  pilot=True, timed=False)
+        h.moments([(zcat.data_ptr(), D, D)], n_local, _backend.dtype_code(dt), True, mom.data_ptr(), pilot=True, timed=False)
         n_total = n_local
         if _dist.is_sharded():
             npk = D * (D + 1) // 2 + D
@@ -356,16 +374,15 @@ class _ShardedPairLossFn(torch.autograd.Function):
                                             C.byref(loss_h), C.c_void_p(gam.data_ptr()) if need else None,
                                             C.c_void_p(mean.data_ptr()) if need else None))
         if need:
-            ctx.save_for_backward(_project(zcat, mean, gam))
+            _save_projection(ctx, zcat, mean, gam)
             ctx.dims = dims
             ctx.dtypes = [z.dtype for z in zs]
-        return torch.tensor(loss_h.value, dtype=dt, device=dev)
+        return torch.tensor(loss_h.value, dtype=_loss_dtype(dt), device=dev)
 
     @staticmethod
     def backward(ctx, grad_out):
-        (gcat,) = ctx.saved_tensors
-        grads = torch.split(gcat, ctx.dims, dim=1)
-        return (None, *[(grad_out * g).to(t) for g, t in zip(grads, ctx.dtypes)])
+        grads = torch.split(_saved_projection(ctx, grad_out), ctx.dims, dim=1)
+        return (None, *[g.to(t) for g, t in zip(grads, ctx.dtypes)])
 
 
 class MCCALoss(nn.Module):
@@ -405,12 +422,33 @@ def _project(x: torch.Tensor, mean64: torch.Tensor, w64: torch.Tensor) -> torch.
     out = torch.empty((a.shape[0], w64.shape[1]), dtype=a.dtype, device=a.device)
     sp = _stream_ptr(a)
     h.acquire(sp)
-    h.check(h.lib.ccz_transform(h.raw, _backend.F32 if a.dtype == torch.float32 else _backend.F64,
-                                C.c_void_p(a.data_ptr()), a.shape[0], a.shape[1], a.stride(0),
+    h.check(h.lib.ccz_transform(h.raw, _backend.dtype_code(a.dtype), C.c_void_p(a.data_ptr()), a.shape[0], a.shape[1], a.stride(0),
                                 C.c_void_p(mean64.data_ptr()), C.c_void_p(w64.data_ptr()), w64.shape[1],
                                 C.c_void_p(out.data_ptr()), out.stride(0)))
     h.release(sp)
     return out
+
+
+def _project_scaled(x: torch.Tensor, mean64: torch.Tensor, w64: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """``grad_out * (x - mean) @ w`` with the factor applied to ``w`` in float64: half rows are then rounded once."""
+    return _project(x, mean64, (w64 * grad_out.detach().to(device=w64.device, dtype=torch.float64)).contiguous())
+
+
+def _save_projection(ctx, zcat: torch.Tensor, mean64: torch.Tensor, gam64: torch.Tensor) -> None:
+    """What a moments-based loss keeps for its backward: the projection ``(Z - mean) Gamma`` itself, or -- for half rows, whose
+    gradient must be rounded once, AFTER the upstream factor -- its three operands."""
+    ctx.lazy = zcat.dtype in _HALF
+    if ctx.lazy:
+        ctx.save_for_backward(zcat, mean64, gam64)
+    else:
+        ctx.save_for_backward(_project(zcat, mean64, gam64))
+
+
+def _saved_projection(ctx, grad_out: torch.Tensor) -> torch.Tensor:
+    if ctx.lazy:
+        return _project_scaled(*ctx.saved_tensors, grad_out)
+    (gcat,) = ctx.saved_tensors
+    return grad_out * gcat
 
 
 class _GCCALossFn(torch.autograd.Function):
@@ -439,8 +477,7 @@ class _GCCALossFn(torch.autograd.Function):
         h = _backend.handle_for([zcat])
         mom = torch.empty(D * D + D, dtype=torch.float64, device=dev)
         h.acquire(_stream_ptr(zcat))
-        h.moments([(zcat.data_ptr(), D, D)], n, _backend.F32 if dt == torch.float32 else _backend.F64, True, mom.data_ptr(),
-                  pilot=True, timed=False)
+        h.moments([(zcat.data_ptr(), D, D)], n, _backend.dtype_code(dt), True, mom.data_ptr(), pilot=True, timed=False)
         # C, B = blockdiag(C_ii) + eps I, the top-k generalised eigenpairs and Gamma are all built on the device
         # from the moments (ccz_gcca_loss_moments); only the k eigenvalues (as the loss) come back to the host
         need = any(ctx.needs_input_grad[1:])
@@ -451,18 +488,17 @@ class _GCCALossFn(torch.autograd.Function):
         h.check(h.lib.ccz_gcca_loss_moments(h.raw, C.c_void_p(mom.data_ptr()), n, dims_a, len(dims), float(eps), k,
                                             C.byref(loss_h), C.c_void_p(gam.data_ptr()) if need else None,
                                             C.c_void_p(mean.data_ptr()) if need else None))
-        loss = torch.tensor(loss_h.value, dtype=dt, device=dev)
+        loss = torch.tensor(loss_h.value, dtype=_loss_dtype(dt), device=dev)
         if need:
-            ctx.save_for_backward(_project(zcat, mean, gam))
+            _save_projection(ctx, zcat, mean, gam)
             ctx.dims = dims
             ctx.dtypes = [z.dtype for z in zs]
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
-        (gcat,) = ctx.saved_tensors
-        grads = torch.split(gcat, ctx.dims, dim=1)
-        return (None, *[(grad_out * g).to(t) for g, t in zip(grads, ctx.dtypes)])
+        grads = torch.split(_saved_projection(ctx, grad_out), ctx.dims, dim=1)
+        return (None, *[g.to(t) for g, t in zip(grads, ctx.dtypes)])
 
 
 class GCCALoss(nn.Module):
@@ -544,7 +580,7 @@ class _TCCALossFn(torch.autograd.Function):
             ctx.eps = float(eps)
             ctx.dtypes = [z.dtype for z in zs]
             ctx.wanted = list(ctx.needs_input_grad[1:])
-        return (-norm).to(dt)
+        return (-norm).to(_loss_dtype(dt))
 
     @staticmethod
     @once_differentiable
@@ -586,7 +622,7 @@ class _TCCALossFn(torch.autograd.Function):
 class TCCALoss(nn.Module):
     r"""Tensor CCA loss: ``-||M||_F`` with ``M = (1 / n) sum_s H_1[s] (x) .. (x) H_V[s]`` the cross-moment tensor of the
     centred, ridge-whitened representations ``H_i = Z_c (Z_c'Z_c / (n - 1) + eps I)^-1/2`` (eigenvalues clamped at ``eps``).
-    2 to 8 views, ``prod d_i <= 2^24``; float32 batches are computed in float64.
+    2 to 8 views, ``prod d_i <= 2^24``; float32, bfloat16 and float16 batches are widened to float64 on entry and computed there.
 
     Args:
         eps: ridge added to the within-view batch covariances (default 1e-5).

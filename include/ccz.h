@@ -29,6 +29,7 @@ extern "C" {
 
 #define CCZ_VERSION 150 /* 0.1.5: ccz_k1_route (split-bf16 route of K1 and of the loss's large backward), ccz_moments_last_route,
                           * ccz_loss_last_route, ccz_pool_trim; the loss state grew by 2 D doubles (opaque: ccz_pair_loss_state_bytes).
+                          * (Two constants since, no new entry: CCZ_BF16 and CCZ_F16, the 2-byte formats of the deep objectives.)
                           * 0.1.4: ccz_pair_loss_forward / _backward / _state_bytes (the loss as an autograd node in two phases),
                           * ccz_moments_exchange (the whole exchange step), ccz_solve_defer(h, NULL) = await a pending deferral now */
 
@@ -49,6 +50,14 @@ extern "C" {
 
 #define CCZ_F32 0
 #define CCZ_F64 1
+/* The 2-byte formats of the deep objectives' batches (torch.autocast): DEVICE rows only, accepted by ccz_moments / _opts,
+ * ccz_transform, ccz_cca_loss, ccz_pair_loss / _forward / _backward / _state_bytes and ccz_moment_loss_forward /
+ * _state_bytes; every other entry that takes a dtype, and host views, answer CCZ_EUNSUP.  An element is widened exactly to
+ * float32 on load and everything after that is the CCZ_F32 route; rows that are written (gradients, projections) are formed in
+ * float32 and rounded once, to nearest even.  For these dtypes loss_dev and grad_out_dev are ONE float32 element (a bfloat16
+ * scalar has 8 bits), the state has the CCZ_F32 layout, and g_dev / out_dev are of `dtype`. */
+#define CCZ_BF16 2
+#define CCZ_F16 3
 
 typedef struct ccz_ctx* ccz_handle;
 
