@@ -130,6 +130,8 @@ SIGNATURES = {
     "ccz_gcca_loss_moments": (_int, [_vp, _vp, _i64, _pi64, _int, _dbl, _int, C.POINTER(_dbl), _vp, _vp]),
     "ccz_factor_loadings": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "ccz_transform": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
+    "ccz_transform_wide": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
+    "ccz_transform_last_route": (_int, [_vp, _pint]),
     "ccz_pairwise_kernel": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _int, _dbl, _dbl, _dbl,
                                    _vp, _i64]),
     "ccz_kernel_project": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _int, _dbl, _dbl, _dbl,
@@ -507,6 +509,15 @@ class Handle:
         names = {v: k for k, v in self.K1_ROUTES.items()}
         names[0] = "none"
         return names.get(f.value, "none"), names.get(b.value, "none")
+
+    TRANSFORM_ROUTES = {0: "none", 1: "bf16", 2: "adapter"}
+
+    def transform_last_route(self):
+        """What the last ``ccz_transform_wide`` on this handle did: "none" | "bf16" (the MFMA kernel on the rows as they lie) |
+        "adapter" (widened into float32 scratch, then the float32 projection)."""
+        r = C.c_int(0)
+        self.check(self.lib.ccz_transform_last_route(self._h, C.byref(r)))
+        return self.TRANSFORM_ROUTES.get(r.value, "none")
 
     # -- fused solves ----------------------------------------------------------------------
     def _solve_out(self, dims, k):

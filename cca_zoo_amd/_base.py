@@ -33,6 +33,10 @@ class BaseModel(BaseEstimator, ABC):
         "center": ["boolean"],
     }
 
+    #: True on the closed-form family (rCCA / CCA / PLS, MCCA, GCCA and what derives from them): ``torch.bfloat16`` CUDA
+    #: views are read as they lie by K1 and by the projection.  Every other family refuses them in ``validate_views``.
+    _bf16_views: ClassVar[bool] = False
+
     def __init__(self, latent_dimensions: int = 1, center: bool = True) -> None:
         self.latent_dimensions = latent_dimensions
         self.center = center
@@ -49,7 +53,7 @@ class BaseModel(BaseEstimator, ABC):
         by the concrete ``fit`` from the column sums of the moments pass.
         """
         self._validate_params()
-        validated = validate_views(views, check_finite=False)   # checked on the moments (compute_moments)
+        validated = validate_views(views, check_finite=False, allow_bf16=self._bf16_views)   # checked on the moments (compute_moments)
         self.n_views_ = len(validated)
         self.n_features_in_ = [int(v.shape[1]) for v in validated]
         self.n_samples_ = int(validated[0].shape[0])
@@ -88,7 +92,7 @@ class BaseModel(BaseEstimator, ABC):
         """``(X_i - mean_i) @ W_i`` per view.  Host arrays in -> numpy out (device GEMM inside
         libccz); CUDA tensors in -> CUDA tensors out."""
         check_is_fitted(self)
-        validated = validate_views(views, check_finite=False)
+        validated = validate_views(views, check_finite=False, allow_bf16=self._bf16_views)
         out = []
         for v, m, w in zip(validated, self.means_, self.weights_):
             if is_device_tensor(v):
@@ -169,7 +173,7 @@ class BaseModel(BaseEstimator, ABC):
         from cca_zoo_amd._moments import compute_moments
 
         check_is_fitted(self)
-        validated = validate_views(views, check_finite=False)
+        validated = validate_views(views, check_finite=False, allow_bf16=self._bf16_views)
         out = []
         for v, w in zip(validated, self.weights_):
             h = _backend.handle_for([v])
@@ -226,14 +230,20 @@ def _device_project(v, mean, w):
     if v.stride(1) != 1 or v.stride(0) < v.shape[1]:      # expanded / overlapping rows: ld must be >= d
         v = v.contiguous()
     k = int(w.shape[1])
-    out = torch.empty((v.shape[0], k), dtype=v.dtype, device=v.device)
+    bf16 = v.dtype == torch.bfloat16                       # rows as they lie, float32 variates (never rounded to bfloat16)
+    out = torch.empty((v.shape[0], k), dtype=torch.float32 if bf16 else v.dtype, device=v.device)
     md = torch.as_tensor(np.asarray(mean, dtype=np.float64), device=v.device)
     wd = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64), device=v.device)
     sp = int(torch.cuda.current_stream(v.device).cuda_stream)
     h.acquire(sp)                                          # device-side hand-over: the host never waits here
-    h.check(h.lib.ccz_transform(h.raw, _backend.F32 if v.element_size() == 4 else _backend.F64,
-                                C.c_void_p(v.data_ptr()), v.shape[0], v.shape[1], v.stride(0),
-                                C.c_void_p(md.data_ptr()), C.c_void_p(wd.data_ptr()), k,
-                                C.c_void_p(out.data_ptr()), out.stride(0)))
+    if bf16:
+        h.check(h.lib.ccz_transform_wide(h.raw, _backend.BF16, C.c_void_p(v.data_ptr()), v.shape[0], v.shape[1], v.stride(0),
+                                         C.c_void_p(md.data_ptr()), C.c_void_p(wd.data_ptr()), k,
+                                         C.c_void_p(out.data_ptr()), out.stride(0)))
+    else:
+        h.check(h.lib.ccz_transform(h.raw, _backend.F32 if v.element_size() == 4 else _backend.F64,
+                                    C.c_void_p(v.data_ptr()), v.shape[0], v.shape[1], v.stride(0),
+                                    C.c_void_p(md.data_ptr()), C.c_void_p(wd.data_ptr()), k,
+                                    C.c_void_p(out.data_ptr()), out.stride(0)))
     h.release(sp)
     return out

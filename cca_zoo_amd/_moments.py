@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from cca_zoo_amd import _backend, _dist
-from cca_zoo_amd._utils._validation import is_device_tensor
+from cca_zoo_amd._utils._validation import is_bf16_tensor, is_device_tensor
 
 
 class _Last(threading.local):
@@ -40,7 +40,8 @@ def _common_float(views):
     kinds = []
     for v in views:
         if is_device_tensor(v):
-            kinds.append("f32" if v.element_size() == 4 else "f64")
+            # (bfloat16 rows widen exactly to float32: their dtype flow is float32's)
+            kinds.append("f32" if v.element_size() == 4 or is_bf16_tensor(v) else "f64")
         else:
             kinds.append("f32" if v.dtype == np.float32 else "f64")
     return "f32" if all(k == "f32" for k in kinds) else "f64"
@@ -126,12 +127,21 @@ def compute_moments(views, handle=None, defer_offdiag=False):
         keep.append(mom_buf)
         mom_t = None
     descr = []
+    code = _backend.F32 if kind == "f32" else _backend.F64
     if on_device:
         import torch
 
         tdt = torch.float32 if kind == "f32" else torch.float64
+        # all views bfloat16: K1 reads them as they lie (CCZ_BF16: fused into the split pass from 32768 rows on, row chunks through
+        # float32 scratch below that) -- no float32 copy of a view.  Mixed with float32 / float64 views they are widened (exact).
+        all_bf16 = all(is_bf16_tensor(v) for v in views)
+        if all_bf16:
+            code = _backend.BF16
         for v in views:
-            if v.dtype != tdt or v.stride(1) != 1 or v.stride(0) < v.shape[1]:     # (expanded / overlapping rows: ld >= d)
+            if all_bf16:
+                if v.stride(1) != 1 or v.stride(0) < v.shape[1]:
+                    v = v.contiguous()
+            elif v.dtype != tdt or v.stride(1) != 1 or v.stride(0) < v.shape[1]:     # (expanded / overlapping rows: ld >= d)
                 v = v.to(tdt).contiguous()
             keep.append(v)
             descr.append((v.data_ptr(), v.shape[1], v.stride(0)))
@@ -144,7 +154,7 @@ def compute_moments(views, handle=None, defer_offdiag=False):
             keep.append(a)
             descr.append((a, a.shape[1], a.shape[1]))
     t_k1 = time.perf_counter()
-    h.moments(descr, n, _backend.F32 if kind == "f32" else _backend.F64, on_device, mom_ptr, accumulate=False)
+    h.moments(descr, n, code, on_device, mom_ptr, accumulate=False)
     LAST["moments_ms"] = (time.perf_counter() - t_k1) * 1e3
     LAST["allreduce_ms"] = 0.0
     n_total = n

@@ -21,8 +21,16 @@ def _n_rows(v) -> int:
     return int(v.shape[0])
 
 
-def validate_views(views, min_views: int = 2, check_finite: bool = True) -> list:
+def is_bf16_tensor(v: Any) -> bool:
+    """A CUDA tensor of ``torch.bfloat16`` (the only 2-byte view format the closed-form estimators take)."""
+    return is_device_tensor(v) and str(v.dtype) == "torch.bfloat16"
+
+
+def validate_views(views, min_views: int = 2, check_finite: bool = True, allow_bf16: bool = False) -> list:
     """Return the views as 2-D numpy arrays (or untouched 2-D CUDA tensors).
+
+    ``allow_bf16`` (the closed-form family only: rCCA / CCA / PLS, MCCA, GCCA, PartialCCA, GRCCA and the grid search over
+    them) lets 2-D ``torch.bfloat16`` CUDA tensors pass as they lie; ``float16`` device views are refused either way.
 
     ``check_finite=False`` skips sklearn's host-side NaN/inf scan (a single-threaded pass over the
     whole input, 0.2 s per 4 GB): ``fit`` detects non-finite inputs for free from the column sums of
@@ -38,8 +46,10 @@ def validate_views(views, min_views: int = 2, check_finite: bool = True) -> list
         if is_device_tensor(v):
             if v.dim() != 2:
                 raise ValueError(f"Expected 2D tensor, got {v.dim()}D tensor instead.")
-            if not v.dtype.is_floating_point or v.element_size() not in (4, 8):
-                raise ValueError("device views must be float32 or float64 tensors")
+            if allow_bf16 and is_bf16_tensor(v):
+                pass
+            elif not v.dtype.is_floating_point or v.element_size() not in (4, 8):
+                raise ValueError("device views must be float32 or float64 tensors" + (" (or bfloat16)" if allow_bf16 else ""))
             out.append(v)
         else:
             if type(v).__module__.startswith("torch"):

@@ -77,6 +77,32 @@ static void transform_impl(ccz_ctx* c, int dtype, const void* X, int64_t n, int6
   // enqueue-only: `out` is ready in stream order (ccz_sync / ccz_stream_release / ccz_memcpy_d2h for a host consumer)
 }
 
+// the same for 2-byte rows with a float32 result: bf16 rows as they lie on the bf16 matrix pipe (project_bf16.hip), everything else
+// widened in row chunks and multiplied by the float32 projection above, straight into `out` (nothing is narrowed)
+static void transform_wide_impl(ccz_ctx* c, int dtype, const void* X, int64_t n, int64_t d, int64_t ld, const double* mean,
+                                const double* W, int64_t k, float* out, int64_t ldo) {
+  if (!is_half_dtype(dtype)) fail(CCZ_EUNSUP, "transform_wide: dtype must be CCZ_BF16 or CCZ_F16");
+  if (!X || !W || !out || n < 1 || d < 1 || k < 1 || ld < d || ldo < k) fail(CCZ_EINVAL, "transform_wide: bad argument");
+  if (dtype == CCZ_BF16 && project_bf16_eligible(n, d, k, ld, X, ldo)) {
+    DBuf bias(c, k);
+    if (mean) gemm(c, false, false, 1, k, d, 1.0, mean, d, W, k, 0.0, bias, k);
+    project_bf16(c, X, n, d, ld, mean ? bias.get() : nullptr, W, k, out, ldo);
+    c->last_transform_route = 1;
+    return;
+  }
+  const int64_t chunk = half_chunk_rows(half_row_bytes(&d, 1), n);
+  HalfStage xs;
+  half_stage(c, &d, 1, chunk < n ? chunk + 1 : n, &xs);
+  const ccz_view xv{X, d, ld};
+  for (int64_t r0 = 0; r0 < n;) {
+    const int64_t rows = half_next_chunk(r0, chunk, n);
+    half_widen(c, dtype, &xv, 1, r0, rows, xs);
+    transform_impl(c, CCZ_F32, xs.fv[0].data, rows, d, xs.fv[0].ld, mean, W, k, out + r0 * ldo, ldo);
+    r0 += rows;
+  }
+  c->last_transform_route = 2;
+}
+
 }  // namespace ccz
 
 extern "C" {
@@ -461,6 +487,19 @@ int ccz_transform(ccz_handle h, int dtype, const void* X_dev, int64_t n, int64_t
                   const double* W_dev, int64_t k, void* out_dev, int64_t ldo) {
   CCZ_GUARD(h, {
     transform_impl(h, dtype, X_dev, n, d, ld, mean_dev, W_dev, k, out_dev, ldo);
+  })
+}
+
+int ccz_transform_wide(ccz_handle h, int dtype, const void* X_dev, int64_t n, int64_t d, int64_t ld, const double* mean_dev,
+                       const double* W_dev, int64_t k, float* out_dev, int64_t ldo) {
+  CCZ_GUARD(h, {
+    transform_wide_impl(h, dtype, X_dev, n, d, ld, mean_dev, W_dev, k, out_dev, ldo);
+  })
+}
+
+int ccz_transform_last_route(ccz_handle h, int* route) {
+  CCZ_GUARD(h, {
+    if (route) *route = h->last_transform_route;
   })
 }
 

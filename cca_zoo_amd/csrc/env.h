@@ -52,13 +52,14 @@ using STR = const char*;
   X(SPLIT_WALK, INT, 0, LIVE, "1: every XCD walks the SAME row chunk also when ksplit % 8 == 0 -- gram_split.hip split_row_plan: A/B")       \
   X(LOSS_K1_SPLIT, INT, 1, LIVE, "0 never, 1 split-route partial sums from 32768 rows on, 2 and above from 4096 -- gram_split.hip gram_partials_split_f32: knob") \
   X(HALF_SCRATCH_MB, REAL, 256.0, LIVE, "MiB of float32 scratch a row chunk of CCZ_BF16 / CCZ_F16 views may take on the routes that widen them (fractions allowed; at least 4 KiB and 2 rows) -- half_io.hip half_chunk_rows: knob; tests shrink it to get several chunks") \
-  /* ---- loss, projection, fp32 products (loss.hip, gemm_split.hip, project_split.hip, gemm_big.hip) ---- */                                 \
+  /* ---- loss, projection, fp32 products (loss.hip, gemm_split.hip, project_split.hip, project_bf16.hip, gemm_big.hip) ---- */               \
   X(LOSS_FUSED, INT, 1, ONCE, "0: every shape takes the wide route (super-blocked factorization, 128-tile GEMMs) -- loss.hip narrow_ok: test") \
   X(LOSS_SPLITK, INT, 2, ONCE, "split-K factor of the narrow product stages (1 and below: none) -- loss.hip pair_core: A/B")                  \
   X(LOSS_FAST, INT, 1, ONCE, "0: the general route (moments + k_loss_prep) instead of K1's partial sums -- loss.hip forward: A/B")           \
   X(LOSS_BWD_SPLIT, INT, 1, LIVE, "0 never, 1 split-bf16 backward for the metric shape, 2 and above also DCCA batches from 4096 rows on -- gemm_split.hip gemm_split_pair_eligible: knob") \
   X(PROJECT_SPLIT, INT, 1, LIVE, "0: the projection keeps the fp32 kernel even on a CCZ_K1_BF16X2 handle -- project_split.hip project_split_eligible: A/B") \
   X(PROJECT_PLANES, INT, 2, LIVE, "3: three bf16 planes / five products, else two / three -- project_split.hip project_split: A/B")          \
+  X(PROJECT_BF16, INT, 1, LIVE, "0: eligible CCZ_BF16 rows of ccz_transform_wide take the widening adapter, not the bf16 MFMA kernel -- project_bf16.hip project_bf16_eligible: A/B; tests reach the adapter with it") \
   X(TALL_IMPL, INT, 3, LIVE, "projection kernel: 3 whole-line loads with 128 rows per workgroup, 2 (and above 3) with 256 rows, below 2 a row per lane -- gemm_big.hip gemm_f32_big: A/B") \
   X(TALL_NJ1, INT, 1, LIVE, "0: two column tiles also for N <= 32 -- gemm_big.hip gemm_f32_big: A/B")                                        \
   X(GEMM_NN_IMPL, INT, 1, ONCE, "wide fp32 product: 0 staged tile, else LDS-DMA FIFO -- gemm_big.hip gemm_f32_big: A/B")                      \

@@ -255,6 +255,13 @@ void gemm_split_pair(ccz_ctx* c, int64_t M, int64_t N, int64_t K, int64_t K1, fl
 bool project_split_eligible(ccz_ctx* c, int64_t n, int64_t d, int64_t k, int64_t ld, const void* X, int64_t ldo);
 void project_split(ccz_ctx* c, const float* X, int64_t n, int64_t d, int64_t ld, const double* mean, const double* W, int64_t k, float* out,
                    int64_t ldo);
+// the W planes of a projection without the pilot / centring row: planes[k-step s < nsteps_alloc][plane H|M|L][j tile 2][1 KiB], rows >= d zero
+void project_prep_planes3(ccz_ctx* c, const double* W, int64_t d, int64_t k, int64_t nsteps_alloc, char* planes);
+// project_bf16.hip: out (n x k <= 64, fp32) = X W - 1 bias' for bf16 rows X as they lie (the MFMA operand: no conversion, no split of X);
+// bias (k doubles on the device, may be null) = mean' W
+bool project_bf16_eligible(int64_t n, int64_t d, int64_t k, int64_t ld, const void* X, int64_t ldo);
+void project_bf16(ccz_ctx* c, const void* X, int64_t n, int64_t d, int64_t ld, const double* bias, const double* W, int64_t k, float* out,
+                  int64_t ldo);
 bool gram_partials_f32(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, GramPartials* out);
 // gram.hip: exact fp64 column sums of all views + the fp32 pilot (their mean) in ONE launch (k_colsum_pilot); `zero_me` (optional,
 // nzero doubles) is cleared by the same launch.  false: shape not supported (more than 64 column blocks / 8 views), nothing enqueued

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(128) void k_project_prep(const double* __restrict__
   if (nplanes == 3) *reinterpret_cast<sp_v4u32*>(dst + 4096) = lw;
   if (t < 16) {
     const int64_t c = int64_t(s) * 16 + t;
-    if (c < d) pilot[c] = mean ? float(mean[c]) : 0.f;
+    if (pilot && c < d) pilot[c] = mean ? float(mean[c]) : 0.f;
   }
   if (mean && j < k) unsafeAtomicAdd(corr + j, cpart);
 }
@@ -206,6 +206,13 @@ __global__ __launch_bounds__(256, 1) void k_project_split(const float* __restric
         }
       }
   }
+}
+
+// the three planes alone (project_bf16.hip: bf16 rows need no pilot, and its centring row is a fp64 product of its own -- no atomics)
+void project_prep_planes3(ccz_ctx* c, const double* W, int64_t d, int64_t k, int64_t nsteps_alloc, char* planes) {
+  hipLaunchKernelGGL(k_project_prep, dim3((unsigned)nsteps_alloc), dim3(128), 0, stream(c), W, d, int(k), k, static_cast<const double*>(nullptr), planes,
+                     static_cast<float*>(nullptr), static_cast<double*>(nullptr), 3);
+  CCZ_LAUNCH_CHECK();
 }
 
 bool project_split_eligible(ccz_ctx* c, int64_t n, int64_t d, int64_t k, int64_t ld, const void* X, int64_t ldo) {

@@ -41,6 +41,7 @@ class GCCA(BaseModel):
         "c": RIDGE_PARAMETER,
         "eps": POSITIVE_EPS,
     }
+    _bf16_views = True        # bfloat16 CUDA views are read as they lie (float32 dtype flow)
 
     def __init__(self, latent_dimensions: int = 1, center: bool = True, c: float | list[float] = 0.0,
                  view_weights: list[float] | None = None, eps: float = 1e-6) -> None:

@@ -48,6 +48,7 @@ class MCCA(BaseModel):
         "pca": ["boolean"],
         "eps": POSITIVE_EPS,
     }
+    _bf16_views = True        # bfloat16 CUDA views are read as they lie (float32 dtype flow); PartialCCA and GRCCA inherit it
 
     def __init__(self, latent_dimensions: int = 1, center: bool = True, c: float | list[float] = 0.0,
                  pca: bool = True, eps: float = 1e-6) -> None:

@@ -34,6 +34,7 @@ class rCCA(BaseModel):
         **BaseModel._parameter_constraints,
         "c": RIDGE_PARAMETER,
     }
+    _bf16_views = True        # bfloat16 CUDA views are read as they lie (float32 dtype flow)
 
     def __init__(self, latent_dimensions: int = 1, center: bool = True, c: float | list[float] = 0.0) -> None:
         super().__init__(latent_dimensions=latent_dimensions, center=center)

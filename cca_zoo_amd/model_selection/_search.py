@@ -125,7 +125,7 @@ class GridSearchCV:
     # -- public API --------------------------------------------------------------------------
     def fit(self, views, y=None, **fit_params):
         if self.scoring is None and not fit_params and _gram_reusable(self.estimator):
-            validated = validate_views(views, check_finite=False)
+            validated = validate_views(views, check_finite=False, allow_bf16=True)     # (the closed-form family: bfloat16 views pass)
             n = int(validated[0].shape[0])
             splits = list(check_cv(self.cv).split(np.zeros((n, 1))))
             seen = np.zeros(n, dtype=np.int64)

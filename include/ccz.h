@@ -30,6 +30,7 @@ extern "C" {
 #define CCZ_VERSION 150 /* 0.1.5: ccz_k1_route (split-bf16 route of K1 and of the loss's large backward), ccz_moments_last_route,
                           * ccz_loss_last_route, ccz_pool_trim; the loss state grew by 2 D doubles (opaque: ccz_pair_loss_state_bytes).
                           * (Two constants since, no new entry: CCZ_BF16 and CCZ_F16, the 2-byte formats of the deep objectives.)
+                          * (Two entries since: ccz_transform_wide and ccz_transform_last_route, bfloat16 views of the closed-form estimators.)
                           * 0.1.4: ccz_pair_loss_forward / _backward / _state_bytes (the loss as an autograd node in two phases),
                           * ccz_moments_exchange (the whole exchange step), ccz_solve_defer(h, NULL) = await a pending deferral now */
 
@@ -51,7 +52,7 @@ extern "C" {
 #define CCZ_F32 0
 #define CCZ_F64 1
 /* The 2-byte formats of the deep objectives' batches (torch.autocast): DEVICE rows only, accepted by ccz_moments / _opts,
- * ccz_transform, ccz_cca_loss, ccz_pair_loss / _forward / _backward / _state_bytes and ccz_moment_loss_forward /
+ * ccz_transform, ccz_transform_wide (float32 out_dev), ccz_cca_loss, ccz_pair_loss / _forward / _backward / _state_bytes and ccz_moment_loss_forward /
  * _state_bytes; every other entry that takes a dtype, and host views, answer CCZ_EUNSUP.  An element is widened exactly to
  * float32 on load and everything after that is the CCZ_F32 route; rows that are written (gradients, projections) are formed in
  * float32 and rounded once, to nearest even.  For these dtypes loss_dev and grad_out_dev are ONE float32 element (a bfloat16
@@ -376,6 +377,18 @@ CCZ_API int ccz_gcca_loss_moments(ccz_handle h, const double* moments_dev, int64
 CCZ_API int ccz_transform(ccz_handle h, int dtype, const void* X_dev, int64_t n, int64_t d, int64_t ld,
                   const double* mean_dev, const double* W_dev, int64_t k, void* out_dev,
                   int64_t ldo);
+/* The same projection for 2-byte device rows with a FLOAT32 result (the closed-form estimators' transform / score on bfloat16
+ * views: the variates are never rounded to the rows' format).  dtype is CCZ_BF16 or CCZ_F16 (anything else: CCZ_EUNSUP); the
+ * argument checks and the stream semantics are ccz_transform's.  CCZ_BF16 rows with 1 <= k <= 64, d % 16 == 0, ld % 8 == 0 and a
+ * 16-byte aligned X_dev are multiplied as they lie on the bf16 matrix pipe (csrc/project_bf16.hip: a bf16 element is an exact
+ * MFMA operand; W enters as three bf16 planes hi + mid + lo = fl32(W), every product is exact in float32; two calls give the
+ * same bits).  Everything else -- CCZ_F16, other shapes, CCZ_PROJECT_BF16=0 -- is widened exactly into float32 scratch and
+ * takes the CCZ_F32 projection of ccz_transform, written straight into out_dev.  Columns k .. ldo - 1 of out_dev are not
+ * touched. */
+CCZ_API int ccz_transform_wide(ccz_handle h, int dtype, const void* X_dev, int64_t n, int64_t d, int64_t ld,
+                               const double* mean_dev, const double* W_dev, int64_t k, float* out_dev, int64_t ldo);
+/* *route = what the last ccz_transform_wide on this handle did: 0 none yet, 1 the bf16 MFMA kernel, 2 the widening adapter. */
+CCZ_API int ccz_transform_last_route(ccz_handle h, int* route);
 
 /* Batched Cholesky factor + triangular inverse (building block of the loss and of the blocked solves; exported
  * for tests): `count` <= 8 SPD matrices A_dev[b] (d[b] x d[b], ld d[b], destroyed), L_dev[b] <- lower factor (the
