@@ -83,7 +83,7 @@ using STR = const char*;
   X(BJ_GROUP_MIN_TILES, I64, 2048, ONCE, "row tiles from which a workgroup takes four 64-column chunks -- evd_block.hip bj_row_group: A/B")  \
   X(BJ_GRAM_SPLIT, INT, 0, ONCE, "column splits of the pair Gram products (below 1: 1); UNSET: sized to fill the chip -- evd_block.hip jacobi_rows_block: A/B") \
   X(BJ_DEBUG, FLAG, false, ONCE, "clock stamps of the pair kernel's three waves, printed in sweep 2 -- evd_block.hip syev_block: trace")     \
-  X(SYEV_TWOSIDED, INT, 2, ONCE, "small EVD: 2 packed H + replayed V' (d <= 160), 1 fused LDS kernel (d <= 96), else one-sided rows -- ops_hip.hip syev_mode: A/B") \
+  X(SYEV_TWOSIDED, INT, 2, ONCE, "small EVD: 2 packed H + replayed V' (d <= 160), 1 fused LDS kernel (d <= 96), else no one-workgroup kernel: every size takes the block Jacobi of evd_block.hip -- ops_hip.hip syev_mode: A/B") \
   X(SYEV_CHASE, INT, 1, ONCE, "0: the replay of V' is a launch of its own, not a chaser next to the solve -- ops_hip.hip syev_small: A/B")   \
   X(RR1_TOL, REAL, 1e-9, ONCE, "Jacobi threshold of the FIRST Rayleigh-Ritz (at or below 2.2e-16: full accuracy) -- solve.cpp topk_symmetric: A/B") \
   X(CHEB_MARGIN, REAL, 1e3, ONCE, "safety factor on the damping asked of the Chebyshev filter -- solve.cpp topk_symmetric: A/B")             \

@@ -14,9 +14,14 @@ ROW = re.compile(r'^\s*X\((\w+),\s*(INT|I64|REAL|FLAG|STR),\s*([^,]+),\s*(ONCE|L
 # names that Python code reads (the package, the build, the test harness), not libccz
 PYTHON_SIDE = re.compile(r"CCZ_(TORCHLESS|DEVICE|FORCE_BUILD|HOSTSIM_SANITIZE|WRITE_FULLSIZE_GOLDEN|BENCH_\w+)$")
 
-# Read once per process and yet set with monkeypatch.setenv by a test that starts no child: that test's docstring says so
-# itself ("the second variant is only exercised when this test runs first in a fresh process").
-SET_IN_PROCESS_THOUGH_ONCE = {"CCZ_GEMM_NN_IMPL": "test_gpu_ops.py::test_transform_f32_wide_output_kernels"}
+# how a test sets a switch: monkeypatch.setenv / os.environ[...] = / an environment dict of a child / a shell-style assignment
+SETTING = [r"setenv\(\s*[\"'](CCZ_\w+)[\"']", r"environ\[[\"'](CCZ_\w+)[\"']\]\s*=", r"[\"'](CCZ_\w+)[\"']\s*:",
+           r"\b(CCZ_[A-Z0-9_]+)\s*=\s*[\"']"]
+
+# Rows (or the part of a row) that no test sets, each with its reason.  A new row lands either with a test that sets it or here.
+NOT_EXERCISED = {
+    "CCZ_RCCL_LIB": "tests force the not-found path with it; the found path needs an RCCL library and more than one GPU",
+}
 
 
 def _read(path):
@@ -83,14 +88,12 @@ def _test_functions(text):
 
 def test_switches_that_the_tests_set_are_declared_with_the_timing_the_tests_need():
     when = {"CCZ_" + r[0]: r[3] for r in _table()}
-    setting = [r"setenv\(\s*[\"'](CCZ_\w+)[\"']", r"environ\[[\"'](CCZ_\w+)[\"']\]\s*=", r"[\"'](CCZ_\w+)[\"']\s*:",
-               r"\b(CCZ_[A-Z0-9_]+)\s*=\s*[\"']"]
     seen = 0
     for path in sorted(glob.glob(os.path.join(TESTS, "*.py"))):
         if os.path.abspath(path) == os.path.abspath(__file__):
             continue
         text = _read(path)
-        for pat in setting:
+        for pat in SETTING:
             for name in re.findall(pat, text):
                 if PYTHON_SIDE.match(name):
                     continue
@@ -102,10 +105,25 @@ def test_switches_that_the_tests_set_are_declared_with_the_timing_the_tests_need
             for name in re.findall(r"monkeypatch\.setenv\(\s*[\"'](CCZ_\w+)[\"']", body):
                 if PYTHON_SIDE.match(name):
                     continue
-                if name in SET_IN_PROCESS_THOUGH_ONCE:
-                    assert SET_IN_PROCESS_THOUGH_ONCE[name] == "%s::%s" % (os.path.basename(path), fn)
-                    assert when[name] == "ONCE"
-                    continue
                 assert when[name] == "LIVE", "%s::%s sets %s in its own process, but env.h reads it %s" % (
                     os.path.basename(path), fn, name, when[name])
     assert seen >= 20, "the patterns above no longer find the tests' switches (%d)" % seen
+
+
+def test_every_switch_is_set_by_some_test():
+    """The ratchet: every row of the table is set by a test (found with the patterns above) or named in NOT_EXERCISED with its
+    reason -- a switch is a second code path, and a path no test takes can be wrong, read out of bounds or never finish
+    without any run showing it."""
+    declared = ["CCZ_" + r[0] for r in _table()]
+    set_by = {}
+    for path in sorted(glob.glob(os.path.join(TESTS, "*.py"))):
+        if os.path.abspath(path) == os.path.abspath(__file__):
+            continue
+        text = _read(path)
+        for pat in SETTING:
+            for name in re.findall(pat, text):
+                set_by.setdefault(name, os.path.basename(path))
+    assert sorted(n for n in NOT_EXERCISED if n not in declared) == [], "NOT_EXERCISED names rows that env.h does not have"
+    assert all(len(reason.strip()) > 10 for reason in NOT_EXERCISED.values())
+    missing = sorted(n for n in declared if n not in set_by and n not in NOT_EXERCISED)
+    assert missing == [], "switches that no test sets: give each a test, or a line in NOT_EXERCISED: %s" % missing

@@ -280,14 +280,12 @@ def test_transform_f32_projection_kernel_forms(H, monkeypatch, impl, nj1, n, d, 
     assert np.abs(outs[1] - outs[0]).max() < 1e-5 * scale
 
 
-@pytest.mark.parametrize("n,d,k,impl", [(65536, 288, 256, "1"), (65600, 512, 512, "1"), (65536, 256, 256, "0")])
-def test_transform_f32_wide_output_kernels(H, n, d, k, impl, monkeypatch):
-    """(X - mean) W with k a multiple of 256 and >= 256 output tiles: the 256 x 256-tile kernels (wave-private
-    LDS-DMA FIFO by default, register-staged tile with CCZ_GEMM_NN_IMPL=0; the choice is read once per process, so
-    the second variant is only exercised when this test runs first in a fresh process)."""
+@pytest.mark.parametrize("n,d,k", [pytest.param(65536, 288, 256, id="65536-288-256-1"), pytest.param(65600, 512, 512, id="65600-512-512-1")])
+def test_transform_f32_wide_output_kernels(H, n, d, k):
+    """(X - mean) W with k a multiple of 256 and >= 256 output tiles: the 256 x 256-tile kernel (wave-private LDS-DMA FIFO).  The
+    register-staged tile behind CCZ_GEMM_NN_IMPL=0 is chosen once per process: test_gpu_switch_paths.py runs it in a child."""
     from cca_zoo_amd import _backend
 
-    monkeypatch.setenv("CCZ_GEMM_NN_IMPL", impl)
     rng = np.random.default_rng(n + d + k)
     Xp = (rng.standard_normal((n, d)) + 0.3).astype(np.float32)
     mean = rng.standard_normal(d)
