@@ -48,6 +48,14 @@ class View(C.Structure):
     _fields_ = [("data", C.c_void_p), ("cols", C.c_int64), ("ld", C.c_int64)]
 
 
+class SparseView(C.Structure):
+    """``ccz_sparse_view``: both compressed forms of one sparse view on the device."""
+
+    _fields_ = [("csr_val", C.c_void_p), ("csr_col", C.c_void_p), ("csr_ptr", C.c_void_p),
+                ("csc_val", C.c_void_p), ("csc_row", C.c_void_p), ("csc_ptr", C.c_void_p),
+                ("rows", C.c_int64), ("cols", C.c_int64), ("nnz", C.c_int64)]
+
+
 class DevInfo(C.Structure):
     _fields_ = [
         ("name", C.c_char * 128),
@@ -155,6 +163,10 @@ SIGNATURES = {
     "ccz_als_sweeps": (_int, [_vp, _vp, C.POINTER(View), C.POINTER(_vp), _i64, _pi64, _pint]),
     "ccz_als_status": (_int, [_vp, _vp, _pint, _pint, _pi64, _pdbl]),
     "ccz_als_colmeans": (_int, [_vp, _int, C.POINTER(View), _i64, _vp]),
+    "ccz_sparse_group": (_int, [_i64, _i64]),
+    "ccz_als_set_sparse": (_int, [_vp, _vp, _int, C.POINTER(SparseView)]),
+    "ccz_sparse_colmeans": (_int, [_vp, _int, C.POINTER(SparseView), _vp]),
+    "ccz_sparse_project": (_int, [_vp, _int, C.POINTER(SparseView), _vp, _vp, _int, _vp]),
     "ccz_als_peek": (_int, [_vp, _vp, _int, _int, _pdbl]),
     "ccz_als_get_weights": (_int, [_vp, _vp, _pdbl]),
     "ccz_gfa_create": (_int, [_vp, _int, _int, _pi64, _i64, _i64, _dbl, _i64, _int, _i64, C.POINTER(_vp)]),

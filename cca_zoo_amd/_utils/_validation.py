@@ -26,8 +26,38 @@ def is_bf16_tensor(v: Any) -> bool:
     return is_device_tensor(v) and str(v.dtype) == "torch.bfloat16"
 
 
-def validate_views(views, min_views: int = 2, check_finite: bool = True, allow_bf16: bool = False) -> list:
+def is_sparse_view(v: Any) -> bool:
+    """A ``scipy.sparse`` matrix or array of any format (never a torch sparse tensor)."""
+    return type(v).__module__.startswith("scipy.sparse") and hasattr(v, "tocsr")
+
+
+def _stored_values(v) -> np.ndarray:
+    """The stored entries of a sparse view as one array (formats without a flat ``data`` go through COO)."""
+    return v.data if v.format in ("csr", "csc", "coo", "bsr", "dia") else v.tocoo().data
+
+
+def _validate_sparse(v):
+    """The host-side checks of one sparse view, format untouched: 2-D, a real numeric dtype (anything but float32 /
+    float64 becomes float64), no NaN or infinity among the stored entries."""
+    if v.ndim != 2:
+        raise ValueError(f"Expected 2D sparse view, got {v.ndim}D instead.")
+    if v.dtype.kind not in "buif":
+        raise ValueError(f"sparse views must have a real numeric dtype, got {v.dtype}")
+    if v.dtype not in (np.float32, np.float64):
+        v = v.astype(np.float64)
+    if not np.all(np.isfinite(_stored_values(v))):
+        raise ValueError("Input contains NaN or infinity.")
+    return v
+
+
+def validate_views(views, min_views: int = 2, check_finite: bool = True, allow_bf16: bool = False,
+                   allow_sparse: bool = False) -> list:
     """Return the views as 2-D numpy arrays (or untouched 2-D CUDA tensors).
+
+    ``allow_sparse`` (the four plain ALS models only: PLS_ALS, SCCA_PMD, ParkhomenkoCCA, SCCA_Span, and ``transform`` of
+    a model fitted on sparse views) lets ``scipy.sparse`` matrices and arrays of any format pass in their own format;
+    their stored entries are always checked for NaN / infinity (a pass over nnz numbers).  Without it they fail as any
+    other unsupported input does (sklearn's ``TypeError``).
 
     ``allow_bf16`` (the closed-form family only: rCCA / CCA / PLS, MCCA, GCCA, PartialCCA, GRCCA and the grid search over
     them) lets 2-D ``torch.bfloat16`` CUDA tensors pass as they lie; ``float16`` device views are refused either way.
@@ -51,6 +81,8 @@ def validate_views(views, min_views: int = 2, check_finite: bool = True, allow_b
             elif not v.dtype.is_floating_point or v.element_size() not in (4, 8):
                 raise ValueError("device views must be float32 or float64 tensors" + (" (or bfloat16)" if allow_bf16 else ""))
             out.append(v)
+        elif allow_sparse and is_sparse_view(v):
+            out.append(_validate_sparse(v))
         else:
             if type(v).__module__.startswith("torch"):
                 v = v.detach().cpu().numpy()

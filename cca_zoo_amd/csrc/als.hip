@@ -25,6 +25,10 @@
 // All reductions run in a fixed order (per-thread strided sums, wave butterflies, waves and workgroups in index order):
 // two fits of the same inputs give the same bits.
 //
+// A view marked sparse (ccz_als_set_sparse, these four rules only) lies in CSR and CSC form and is centred implicitly:
+// k_als_score becomes k_als_sparse_dot (mu' w) + k_als_score_csr, k_als_xt becomes k_als_sparse_dot (1' t~) + k_als_xt_csc,
+// which writes the one chunk the fold sums; every other kernel of the sweep is unchanged (see "sparse views" below).
+//
 // SCCA_ADMM (cca_zoo/linear/_iterative.py:388-514) runs on the same buffers with its own ordering (Jacobi in the scores: the
 // targets of ALL views come from the vectors the iteration started with) and its own rule.  One iteration:
 //   M x  k_als_score          first iteration of a dimension only, as above
@@ -1093,6 +1097,160 @@ __global__ void __launch_bounds__(256) k_als_colmeans(const T* __restrict__ X, i
   mean[f] = acc / T(n);
 }
 
+// ---- sparse views: CSR for the score pass, CSC for X' t~ and the means -------------------------------------------------
+// A sparse view is never densified and never rewritten; centring is implicit, (X - 1 mu') w = X w - (mu' w) 1 and
+// (X - 1 mu')' t = X' t - mu (1' t), so no x - mu element is formed and nothing is rounded in the values' precision: a value
+// is widened exactly, every product and sum is fp64, and float32 and float64 values holding the same numbers give the same
+// bits.  A LINE is a row of the CSR form or a column of the CSC form.  A group of G lanes (a power of two in [4, 64], chosen
+// once per view and form from the mean line length: sparse_group) owns a line: lane l takes the entries l, l + G, ... of the
+// line in order and the lanes combine by an xor butterfly, so the order of summation depends on the matrix and on G alone.
+// The indices are trusted: the caller has checked them (include/ccz.h).
+__device__ __forceinline__ double group_sum(double v, int G) {
+  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the line a thread works on (-1 past the last), its lane within the group; 256 threads = 256 / G lines per workgroup
+__device__ __forceinline__ int64_t sparse_line(int64_t nlines, int G, int* lane) {
+  *lane = threadIdx.x & (G - 1);
+  const int64_t l = int64_t(blockIdx.x) * (256 / G) + threadIdx.x / G;
+  return l < nlines ? l : -1;
+}
+
+// sum_e val[e] x[idx[e]] over the entries of line l (0 for l = -1: the lanes still take part in the butterfly)
+template <typename V>
+__device__ __forceinline__ double sparse_line_dot(const V* __restrict__ val, const int32_t* __restrict__ idx,
+                                                  const int64_t* __restrict__ ptr, int64_t l, int lane, int G,
+                                                  const double* __restrict__ x) {
+  int64_t e0 = 0, e1 = 0;
+  if (l >= 0) { e0 = ptr[l]; e1 = ptr[l + 1]; }
+  double acc = 0.0;
+#pragma unroll 4
+  for (int64_t e = e0 + lane; e < e1; e += G) acc += double(val[e]) * x[idx[e]];
+  return group_sum(acc, G);
+}
+
+// per-workgroup partial sums of sum_f a[f] b[f] (b = NULL: of sum_f a[f]): mu' w for the score, 1' t~ for X' t~.  The readers
+// add the partials as als_fold_totals does.  first_only as in k_als_score.
+__global__ void __launch_bounds__(256) k_als_sparse_dot(const double* __restrict__ a, const double* __restrict__ b, int64_t len,
+                                                       double* __restrict__ part, int first_only, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  if (first_only && (st->sweep != 0 || st->view != 0 || st->phase != 0)) return;
+  __shared__ double sh[4];
+  double acc = 0.0;
+  for (int64_t f = int64_t(blockIdx.x) * 256 + threadIdx.x; f < len; f += int64_t(gridDim.x) * 256) acc += b ? a[f] * b[f] : a[f];
+  acc = block_sum<4>(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// score of a sparse view: spart[r] = sum_e val[e] w[col[e]] - mu' w, an empty row gets -mu' w.  part: the npart partials of
+// mu' w (NULL without centring).  Entry conditions as k_als_score.
+template <typename V>
+__global__ void __launch_bounds__(256) k_als_score_csr(const V* __restrict__ val, const int32_t* __restrict__ col,
+                                                      const int64_t* __restrict__ ptr, int n, int G, const double* __restrict__ w,
+                                                      const double* __restrict__ part, int npart, double* __restrict__ spart,
+                                                      int first_only, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  if (first_only && (st->sweep != 0 || st->view != 0 || st->phase != 0)) return;
+  __shared__ double sh[4];
+  const double muw = part ? block_sum<4>(int(threadIdx.x) < npart ? part[threadIdx.x] : 0.0, sh) : 0.0;
+  int lane;
+  const int64_t r = sparse_line(n, G, &lane);
+  const double s = sparse_line_dot<V>(val, col, ptr, r, lane, G, w);
+  if (r >= 0 && lane == 0) spart[r] = s - muw;
+}
+
+// X' t~ of a sparse view: out[f] = sum_e val[e] t~[row[e]] - mu[f] (1' t~), the one chunk k_als_fold then sums.  part: the
+// npart partials of 1' t~ (read only when mu is given).
+template <typename V>
+__global__ void __launch_bounds__(256) k_als_xt_csc(const V* __restrict__ val, const int32_t* __restrict__ row,
+                                                   const int64_t* __restrict__ ptr, int64_t p, int G, const double* __restrict__ tt,
+                                                   const double* __restrict__ mu, const double* __restrict__ part, int npart,
+                                                   double* __restrict__ out, const AlsStatus* st) {
+  if (fit_stopped(st)) return;
+  __shared__ double sh[4];
+  const double tsum = mu ? block_sum<4>(int(threadIdx.x) < npart ? part[threadIdx.x] : 0.0, sh) : 0.0;
+  int lane;
+  const int64_t f = sparse_line(p, G, &lane);
+  const double s = sparse_line_dot<V>(val, row, ptr, f, lane, G, tt);
+  if (f >= 0 && lane == 0) out[f] = mu ? s - mu[f] * tsum : s;
+}
+
+// float64 column means from the CSC form: the stored entries of a column in the group's order, over n
+template <typename V>
+__global__ void __launch_bounds__(256) k_sparse_colmeans(const V* __restrict__ val, const int64_t* __restrict__ ptr, int64_t p, int G,
+                                                        int64_t n, double* __restrict__ mean) {
+  int lane;
+  const int64_t f = sparse_line(p, G, &lane);
+  int64_t e0 = 0, e1 = 0;
+  if (f >= 0) { e0 = ptr[f]; e1 = ptr[f + 1]; }
+  double acc = 0.0;
+  for (int64_t e = e0 + lane; e < e1; e += G) acc += double(val[e]);
+  acc = group_sum(acc, G);
+  if (f >= 0 && lane == 0) mean[f] = acc / double(n);
+}
+
+// muW[c] = sum_f mu[f] W[f][c]: workgroup c, strided sums and block_sum
+__global__ void __launch_bounds__(256) k_sparse_muw(const double* __restrict__ mu, const double* __restrict__ W, int64_t p, int k,
+                                                   double* __restrict__ muW) {
+  __shared__ double sh[4];
+  const int c = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t f = threadIdx.x; f < p; f += 256) acc += mu[f] * W[f * k + c];
+  acc = block_sum<4>(acc, sh);
+  if (threadIdx.x == 0) muW[c] = acc;
+}
+
+// out (rows x k) = X W - 1 muW' from the CSR form, 8 right-hand sides per pass over a row (muW NULL: no centring)
+constexpr int SPARSE_KB = 8;
+template <typename V>
+__global__ void __launch_bounds__(256) k_sparse_project(const V* __restrict__ val, const int32_t* __restrict__ col,
+                                                       const int64_t* __restrict__ ptr, int64_t n, int G, const double* __restrict__ W,
+                                                       int k, const double* __restrict__ muW, double* __restrict__ out) {
+  int lane;
+  const int64_t r = sparse_line(n, G, &lane);
+  int64_t e0 = 0, e1 = 0;
+  if (r >= 0) { e0 = ptr[r]; e1 = ptr[r + 1]; }
+  for (int c0 = 0; c0 < k; c0 += SPARSE_KB) {
+    const int kb = min(SPARSE_KB, k - c0);
+    double acc[SPARSE_KB];
+#pragma unroll
+    for (int q = 0; q < SPARSE_KB; ++q) acc[q] = 0.0;
+    for (int64_t e = e0 + lane; e < e1; e += G) {
+      const double v = double(val[e]);
+      const double* wr = W + int64_t(col[e]) * k + c0;
+#pragma unroll
+      for (int q = 0; q < SPARSE_KB; ++q)
+        if (q < kb) acc[q] += v * wr[q];
+    }
+#pragma unroll
+    for (int q = 0; q < SPARSE_KB; ++q) {
+      const double s = group_sum(acc[q], G);
+      if (r >= 0 && lane == 0 && q < kb) out[r * k + c0 + q] = s - (muW ? muW[c0 + q] : 0.0);
+    }
+  }
+}
+
+// G for lines of nnz / nlines stored entries on average: the smallest power of two that is not below the mean, in [4, 64]
+inline int sparse_group(int64_t nnz, int64_t nlines) {
+  int g = 4;
+  while (g < 64 && int64_t(g) * nlines < nnz) g *= 2;
+  return g;
+}
+
+inline unsigned sparse_grid(int64_t nlines, int G) { return unsigned((nlines + 256 / G - 1) / (256 / G)); }
+
+// what a call needs of a ccz_sparse_view; the indices themselves are the caller's to check
+void check_sparse(const ccz_sparse_view* v, bool csr, bool csc) {
+  if (!v) fail(CCZ_EINVAL, "sparse: null view");
+  const int64_t lim = int64_t(1) << 31;
+  if (v->rows < 1 || v->cols < 1 || v->nnz < 0 || v->rows >= lim || v->cols >= lim || v->nnz >= lim)
+    fail(CCZ_EINVAL, "sparse: rows and cols must be in [1, 2^31), nnz in [0, 2^31); got %lld x %lld with %lld entries",
+         (long long)v->rows, (long long)v->cols, (long long)v->nnz);
+  if (csr && (!v->csr_ptr || (v->nnz > 0 && (!v->csr_val || !v->csr_col)))) fail(CCZ_EINVAL, "sparse: the CSR form is missing");
+  if (csc && (!v->csc_ptr || (v->nnz > 0 && (!v->csc_val || !v->csc_row)))) fail(CCZ_EINVAL, "sparse: the CSC form is missing");
+}
+
 // ---- host driver ----------------------------------------------------------------------------------------------------
 struct AlsState : FitState<AlsStatus> {
   int rule, max_iter;
@@ -1110,18 +1268,35 @@ struct AlsState : FitState<AlsStatus> {
   double ea[ALS_MAXV] = {}, eb[ALS_MAXV] = {};
   int eridge[ALS_MAXV] = {};
   int enet_all = 0, enet_post = 0;
+  // sparse views (ccz_als_set_sparse): the two forms, G of the rows and of the columns, the partials of mu' w / 1' t~
+  bool sparse[ALS_MAXV] = {};
+  bool any_sparse = false;
+  ccz_sparse_view sp[ALS_MAXV] = {};
+  int grow[ALS_MAXV] = {}, gcol[ALS_MAXV] = {};
+  double* sdot = nullptr;          // ALS_MAXG
 };
 
 AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const* means) {
   AlsViews vw;
   memset(&vw, 0, sizeof(vw));
-  fill_views("als", vw, views, means, S.p);
+  if (S.any_sparse && views) {     // a sparse view's data and ld are ignored, its cols must still match
+    ccz_view seen[ALS_MAXV];
+    for (int i = 0; i < S.M; ++i) {
+      seen[i] = views[i];
+      if (S.sparse[i]) { seen[i].data = &S; seen[i].ld = seen[i].cols; }
+    }
+    fill_views("als", vw, seen, means, S.p);
+    for (int i = 0; i < S.M; ++i)
+      if (S.sparse[i]) vw.X[i] = nullptr;
+  } else {
+    fill_views("als", vw, views, means, S.p);
+  }
   int64_t off = 0;
   for (int i = 0; i < S.M; ++i) {
     vw.p[i] = S.p[i];
     vw.off[i] = off;
     off += S.p[i];
-    vw.cs[i] = column_splits(S.n, ALS_SROWS, S.p[i], S.B.csmax);
+    vw.cs[i] = S.sparse[i] ? 1 : column_splits(S.n, ALS_SROWS, S.p[i], S.B.csmax);
     vw.ng[i] = int(std::max<int64_t>(1, std::min<int64_t>(ALS_MAXG, (S.p[i] + 2047) / 2048)));
     vw.par[i] = S.par[i];
     vw.rule[i] = (S.rule == RULE_TOP_S && S.par[i] >= double(S.p[i])) ? int(RULE_NORMALISE) : S.rule;
@@ -1129,8 +1304,50 @@ AlsViews make_views(const AlsState& S, const ccz_view* views, const void* const*
   return vw;
 }
 
+// workgroups of k_als_sparse_dot over a vector of len entries (the grids depend on the shapes and on G alone)
+inline int sparse_dot_groups(int64_t len) { return int(std::max<int64_t>(1, std::min<int64_t>(ALS_MAXG, (len + 2047) / 2048))); }
+
+// the score of sparse view i: mu' w first (when centring), then the rows
+void launch_score_sparse(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only) {
+  const ccz_sparse_view& v = S.sp[i];
+  const double* w = S.B.w + vw.off[i];
+  const double* mu = static_cast<const double*>(vw.mu[i]);
+  const int nd = sparse_dot_groups(vw.p[i]);
+  if (mu) {
+    hipLaunchKernelGGL(k_als_sparse_dot, dim3(nd), dim3(256), 0, stream(c), mu, w, vw.p[i], S.sdot, first_only, S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+  by_dtype(S.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_score_csr<T>), dim3(sparse_grid(S.n, S.grow[i])), dim3(256), 0, stream(c),
+                       static_cast<const T*>(v.csr_val), v.csr_col, v.csr_ptr, int(S.n), S.grow[i], w, mu ? S.sdot : nullptr, nd,
+                       S.B.spart + int64_t(i) * S.B.csmax * S.n, first_only, S.drv.dev);
+  });
+  CCZ_LAUNCH_CHECK();
+}
+
+// X' t~ of sparse view i into the first chunk of xpart: 1' t~ first (when centring), then the columns
+void launch_xt_sparse(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
+  const ccz_sparse_view& v = S.sp[i];
+  const double* mu = static_cast<const double*>(vw.mu[i]);
+  const int nd = sparse_dot_groups(S.n);
+  if (mu) {
+    hipLaunchKernelGGL(k_als_sparse_dot, dim3(nd), dim3(256), 0, stream(c), S.B.tt, static_cast<const double*>(nullptr), S.n, S.sdot, 0,
+                       S.drv.dev);
+    CCZ_LAUNCH_CHECK();
+  }
+  by_dtype(S.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_xt_csc<T>), dim3(sparse_grid(vw.p[i], S.gcol[i])), dim3(256), 0, stream(c),
+                       static_cast<const T*>(v.csc_val), v.csc_row, v.csc_ptr, vw.p[i], S.gcol[i], S.B.tt, mu, S.sdot, nd, S.B.xpart,
+                       S.drv.dev);
+  });
+  CCZ_LAUNCH_CHECK();
+}
+
 // vec: the p-vectors scored (B.w unless given); gate: see k_als_score
 void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int first_only, const double* vec = nullptr, int gate = -1) {
+  if (S.sparse[i]) return launch_score_sparse(c, S, vw, i, first_only);     // the plain rules only: no vec, no gate
   const dim3 grid(unsigned((S.n + ALS_SROWS - 1) / ALS_SROWS), unsigned(vw.cs[i]));
   by_dtype(S.dtype, [&](auto t) {
     using T = decltype(t);
@@ -1142,6 +1359,7 @@ void launch_score(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int 
 }
 
 void launch_xt(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i, int gate = -1) {
+  if (S.sparse[i]) return launch_xt_sparse(c, S, vw, i);
   const dim3 grid(unsigned((vw.p[i] + ALS_STRIP - 1) / ALS_STRIP), unsigned(S.B.nchunk));
   by_dtype(S.dtype, [&](auto t) {
     using T = decltype(t);
@@ -1158,7 +1376,8 @@ void launch_rule(ccz_ctx* c, const AlsState& S, const AlsViews& vw, int i) {
   const int64_t p = vw.p[i];
   double* raw = B.raw + vw.off[i];
   double* fstat = B.fstat + size_t(i) * ALS_MAXG * 3;
-  hipLaunchKernelGGL(k_als_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, B.nchunk, p, raw, rule, vw.par[i], fstat, S.drv.dev);
+  const int nchunk = S.sparse[i] ? 1 : B.nchunk;     // k_als_xt_csc writes the one chunk
+  hipLaunchKernelGGL(k_als_fold, dim3(ng), dim3(256), 0, stream(c), B.xpart, nchunk, p, raw, rule, vw.par[i], fstat, S.drv.dev);
   CCZ_LAUNCH_CHECK();
   if (rule == RULE_SOFT_L1 || rule == RULE_TOP_S) {
     const int passes = rule == RULE_SOFT_L1 ? ALS_PMD_PASSES : ALS_SPAN_PASSES;
@@ -1375,6 +1594,7 @@ AlsState* als_create(ccz_ctx* c, int dtype, int M, const int64_t* p, int64_t n, 
     B.nstat = S.get(c, ALS_MAXG);
     B.thr = S.get(c, size_t(M) * 2);
     B.dpart = S.get(c, size_t(M) * ALS_MAXG);
+    S.sdot = S.get(c, ALS_MAXG);
     if (rule == RULE_ADMM) {
       B.eta = S.get(c, size_t(B.ptot));
       B.tt2 = S.get(c, size_t(n));
@@ -1608,6 +1828,66 @@ int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_ro
       using T = decltype(t);
       hipLaunchKernelGGL((ccz::k_als_colmeans<T>), grid, dim3(256), 0, ccz::stream(h), static_cast<const T*>(view->data), view->ld,
                          view->cols, n_rows, static_cast<T*>(mean_dev));
+    });
+    CCZ_LAUNCH_CHECK();
+  })
+}
+
+int ccz_sparse_group(int64_t nnz, int64_t lines) { return (nnz < 0 || lines < 1) ? CCZ_EINVAL : ccz::sparse_group(nnz, lines); }
+
+int ccz_als_set_sparse(ccz_handle h, void* state, int view, const ccz_sparse_view* sparse) {
+  CCZ_GUARD(h, {
+    ccz::AlsState& S = *ccz::as_state<ccz::AlsState>("als", state);
+    if (view < 0 || view >= S.M) ccz::fail(CCZ_EINVAL, "als: no view %d", view);
+    if (S.rule == ccz::RULE_ADMM || S.rule == ccz::RULE_ENET)
+      ccz::fail(CCZ_EUNSUP, "als: the ADMM and elastic-net rules need the Gram of a view and take no sparse views");
+    if (sparse) {
+      ccz::check_sparse(sparse, true, true);
+      if (sparse->rows != S.n || sparse->cols != S.p[view])
+        ccz::fail(CCZ_EINVAL, "als: sparse view %d is %lld x %lld, the fit state %lld x %lld", view, (long long)sparse->rows,
+                  (long long)sparse->cols, (long long)S.n, (long long)S.p[view]);
+      S.sp[view] = *sparse;
+      S.grow[view] = ccz::sparse_group(sparse->nnz, sparse->rows);
+      S.gcol[view] = ccz::sparse_group(sparse->nnz, sparse->cols);
+    }
+    S.sparse[view] = sparse != nullptr;
+    S.any_sparse = false;
+    for (int i = 0; i < S.M; ++i) S.any_sparse = S.any_sparse || S.sparse[i];
+  })
+}
+
+int ccz_sparse_colmeans(ccz_handle h, int dtype, const ccz_sparse_view* view, double* mean_dev) {
+  CCZ_GUARD(h, {
+    ccz::check_dtype("sparse", dtype);
+    ccz::check_sparse(view, false, true);
+    if (!mean_dev) ccz::fail(CCZ_EINVAL, "sparse: null argument");
+    const int G = ccz::sparse_group(view->nnz, view->cols);
+    ccz::by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((ccz::k_sparse_colmeans<T>), dim3(ccz::sparse_grid(view->cols, G)), dim3(256), 0, ccz::stream(h),
+                         static_cast<const T*>(view->csc_val), view->csc_ptr, view->cols, G, view->rows, mean_dev);
+    });
+    CCZ_LAUNCH_CHECK();
+  })
+}
+
+int ccz_sparse_project(ccz_handle h, int dtype, const ccz_sparse_view* view, const double* mean_dev, const double* W_dev, int k,
+                       double* out_dev) {
+  CCZ_GUARD(h, {
+    ccz::check_dtype("sparse", dtype);
+    ccz::check_sparse(view, true, false);
+    if (!W_dev || !out_dev) ccz::fail(CCZ_EINVAL, "sparse: null argument");
+    if (k < 1 || k > ccz::ALS_MAXK) ccz::fail(CCZ_EUNSUP, "sparse: 1 to %d columns are supported, got %d", ccz::ALS_MAXK, k);
+    ccz::DBuf muW(h, mean_dev ? k : 0);
+    if (mean_dev) {
+      hipLaunchKernelGGL(ccz::k_sparse_muw, dim3(k), dim3(256), 0, ccz::stream(h), mean_dev, W_dev, view->cols, k, muW.get());
+      CCZ_LAUNCH_CHECK();
+    }
+    const int G = ccz::sparse_group(view->nnz, view->rows);
+    ccz::by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((ccz::k_sparse_project<T>), dim3(ccz::sparse_grid(view->rows, G)), dim3(256), 0, ccz::stream(h),
+                         static_cast<const T*>(view->csr_val), view->csr_col, view->csr_ptr, view->rows, G, W_dev, k, muW.get(), out_dev);
     });
     CCZ_LAUNCH_CHECK();
   })

@@ -70,6 +70,17 @@ class _BaseIterative(BaseModel):
     As in the reference, everything after centring is float64 for float32 views too: ``weights_`` are float64,
     ``means_`` keep the input dtype.
 
+    **Sparse views** (not in the reference, which refuses them).  PLS_ALS, SCCA_PMD, ParkhomenkoCCA and SCCA_Span take
+    ``scipy.sparse`` matrices and arrays of any format, alone or next to dense host arrays (not next to CUDA tensors).  A
+    sparse view is never densified and never rewritten: it is uploaded once in canonical CSR and CSC form (after scipy's
+    full format check) and centring is implicit, ``(X - 1 mu') w = X w - (mu' w) 1`` and ``(X - 1 mu')' t = X' t - mu (1' t)``.
+    No ``x - mu`` element is formed, so there is no float32 rounding of ``x - mu`` on this path (the difference from dense
+    float32 views): stored values are widened exactly, every product and sum is float64, and float32 and float64 sparse
+    views holding the same numbers give the same bits.  ``means_`` of a sparse view are float64.  The comparator of a
+    sparse fit is the dense float64 fit of ``toarray()``.  ``transform``, ``score`` and the correlations take sparse views
+    and return dense float64 variates; ``get_factor_loadings`` needs a view's p x p moments and raises ``ValueError`` on
+    a sparse view.  SCCA_ADMM, SCCA_IPLS and ElasticCCA need the Gram of a view and raise ``ValueError``.
+
     ``n_iter_`` (not in the reference) lists the sweeps taken per latent dimension; ``last_delta_`` the largest weight
     change of each dimension's last sweep.
     """
@@ -81,6 +92,8 @@ class _BaseIterative(BaseModel):
         "random_state": [Integral, None],
     }
     _rule = RULE_NORMALISE
+    #: False on the models whose rule needs the Gram of a view (SCCA_ADMM, SCCA_IPLS, ElasticCCA)
+    _sparse_views = True
 
     def __init__(
         self,
@@ -118,7 +131,10 @@ class _BaseIterative(BaseModel):
         self._validate_params()
         # the means of device rows in NumPy's own order of summation (ccz_als_colmeans): torch's tree-ordered float32 mean
         # differs from v.mean(axis=0) in the last bits, and with it the whole trajectory
-        res = ResidentViews(views, self.center, MEANS_COLMEANS)
+        res = ResidentViews(views, self.center, MEANS_COLMEANS, allow_sparse=True)
+        if any(res.sparse) and not self._sparse_views:
+            raise ValueError(f"{type(self).__name__} needs the Gram matrix of every view and takes no scipy.sparse views; "
+                             "PLS_ALS, SCCA_PMD, ParkhomenkoCCA and SCCA_Span do")
         m, n, p = len(res.p), res.n, res.p
         k = int(self.latent_dimensions)
         check_limits(k, m, MAX_DIMS, MAX_VIEWS)
@@ -134,6 +150,9 @@ class _BaseIterative(BaseModel):
             with fit_state(h, "als", res.code, m, (C.c_int64 * m)(*p), n, k, int(self._rule),
                            (C.c_double * m)(*[float(x) for x in par]), float(self.tol), int(self.max_iter), chunk) as state:
                 self._setup_state(h, state, res)
+                for i, sv in enumerate(res.sarr):
+                    if sv is not None:
+                        h.check(h.lib.ccz_als_set_sparse(h.raw, state, i, C.byref(sv.view)))
                 w0 = np.ascontiguousarray(initial_vectors(self.random_state, p, k))
                 h.check(h.lib.ccz_als_set_init(h.raw, state, w0.ctypes.data_as(C.POINTER(C.c_double))))
                 known, stopped = C.c_int64(-1), C.c_int(0)
@@ -155,7 +174,7 @@ class _BaseIterative(BaseModel):
         self.n_iter_ = [int(x) for x in iters]
         self.last_delta_ = [float(x) for x in deltas]
         weights = np.split(wflat.reshape(-1, k), np.cumsum(p)[:-1])
-        self._store(weights, res.means_host(), "f32" if res.f32 else "f64", weights_like_input=False)
+        self._store(weights, res.means_host(), "f32" if res.f32 else "f64", weights_like_input=False, sparse=res.sparse)
         return self
 
 class PLS_ALS(_BaseIterative):
@@ -339,6 +358,7 @@ class SCCA_ADMM(_BaseIterative):
         "mu": [Interval(Real, 0, None, closed="neither")],
     }
     _rule = RULE_ADMM
+    _sparse_views = False
 
     def __init__(
         self,
@@ -415,6 +435,7 @@ class _BaseElasticNet(_BaseIterative):
         "l1_ratio": [Interval(Real, 0, 1, closed="both"), list],
     }
     _rule = RULE_ENET
+    _sparse_views = False
     _l1_default = 1.0
     _target_all = False
     _post_std = False

@@ -590,6 +590,53 @@ CCZ_API int ccz_als_status(ccz_handle h, void* state, int* dims_done, int* stopp
  * centred rows and with them the trajectory.  Asynchronous on the handle's stream. */
 CCZ_API int ccz_als_colmeans(ccz_handle h, int dtype, const ccz_view* view, int64_t n_rows, void* mean_dev);
 
+/* ---- sparse views of the four plain rules (CCZ_ALS_NORMALISE .. CCZ_ALS_TOP_S) ------------------------------------------
+ * A sparse view lives on the device in BOTH compressed forms, because the two passes of an update want opposite
+ * orientations and a scatter would need floating-point atomics: CSR for the score X w, CSC for X' t and the means.  Each form
+ * holds the values in the fit's dtype (CCZ_F32 / CCZ_F64), int32 minor indices and int64 pointers (rows + 1 / cols + 1
+ * entries).  Both must be CANONICAL: indices sorted within a line, no duplicates.  The indices are trusted: the caller checks
+ * them before the upload (the Python side runs scipy's full format check); an out-of-range index is an out-of-range read.
+ * A form that a call does not read may be left NULL; with nnz = 0 the value and index arrays may be NULL.
+ *
+ * Semantics.  A sparse view is never densified and never rewritten.  Centring is implicit:
+ *   (X - 1 mu') w = X w - (mu' w) 1        (X - 1 mu')' t = X' t - mu (1' t)
+ * so no x - mu element is formed and there is NO fl32(x - mu) rounding on this path (the stated difference from dense
+ * float32 views): a stored value is widened exactly on load, every product and sum is float64, and a CCZ_F32 and a CCZ_F64
+ * sparse view holding the same numbers give the same bits.  The means of a sparse view are float64,
+ * mu_j = (sum_i x_ij) / n_rows over the stored entries of column j.  A line (a row of the CSR form, a column of the CSC
+ * form) is summed by a group of G lanes, G = ccz_sparse_group(nnz, lines): lane l takes entries l, l + G, ... in order and
+ * the lanes combine by a fixed butterfly; mu' w and 1' t are summed in a fixed order too.  No floating-point atomics: two
+ * fits give the same bits whatever the chunk length.  The comparator of a sparse fit is the dense float64 fit of the same
+ * numbers. */
+typedef struct ccz_sparse_view {
+  const void* csr_val;    /* nnz values, the row-major order of the entries   */
+  const int32_t* csr_col; /* nnz column indices                                */
+  const int64_t* csr_ptr; /* rows + 1                                          */
+  const void* csc_val;    /* nnz values, the column-major order of the entries */
+  const int32_t* csc_row; /* nnz row indices                                   */
+  const int64_t* csc_ptr; /* cols + 1                                          */
+  int64_t rows, cols, nnz; /* each below 2^31                                  */
+} ccz_sparse_view;
+
+/* The lanes per line for `lines` lines holding nnz stored entries in all: the smallest power of two that is not below
+ * nnz / lines, within [4, 64].  A function of the matrix alone.  Host only; CCZ_EINVAL for nnz < 0 or lines < 1. */
+CCZ_API int ccz_sparse_group(int64_t nnz, int64_t lines);
+
+/* Mark view `view` of a fit state as sparse (device arrays, both forms; they must outlive the fit), or as dense again with
+ * sparse = NULL.  rows / cols must be the state's n_rows / p[view].  CCZ_EUNSUP for CCZ_ALS_ADMM and CCZ_ALS_ENET, which
+ * need the Gram of a view.  Afterwards ccz_als_sweeps ignores views[view].data and .ld (cols must still match) and reads
+ * means_dev[view] as FLOAT64 whatever the fit's dtype; the other views keep their arithmetic bit for bit. */
+CCZ_API int ccz_als_set_sparse(ccz_handle h, void* state, int view, const ccz_sparse_view* sparse);
+
+/* mean_dev (device, float64, cols entries) = the column means of a sparse view from its CSC form.  Asynchronous on the
+ * handle's stream. */
+CCZ_API int ccz_sparse_colmeans(ccz_handle h, int dtype, const ccz_sparse_view* view, double* mean_dev);
+
+/* out_dev (device, rows x k row-major float64) = X W - 1 (mu' W) from the CSR form: W_dev cols x k row-major float64,
+ * k <= 32, mean_dev float64 or NULL for no centring.  Asynchronous on the handle's stream. */
+CCZ_API int ccz_sparse_project(ccz_handle h, int dtype, const ccz_sparse_view* view, const double* mean_dev, const double* W_dev,
+                               int k, double* out_dev);
+
 /* Copy one working buffer of view `view` to the host (float64) -- what the kernel tests compare with NumPy one kernel at
  * a time: the current vector w_i (p_i), raw_i = X_d' t of its last update (p_i), its uncorrected score (X_i - mu_i) w_i
  * (n_rows), the corrected target t~ of the LAST update of any view (n_rows), Q_i (k x n_rows, column a at a n_rows:
