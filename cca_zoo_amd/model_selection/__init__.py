@@ -1,5 +1,6 @@
-"""Model selection for multiview models (surface of cca_zoo/model_selection/__init__.py)."""
+"""Model selection for multiview models (surface of cca_zoo/model_selection/__init__.py) and permutation inference."""
 
+from cca_zoo_amd.model_selection._permutation import PermutationTestResult, permutation_test
 from cca_zoo_amd.model_selection._search import GridSearchCV
 
-__all__ = ["GridSearchCV"]
+__all__ = ["GridSearchCV", "permutation_test", "PermutationTestResult"]

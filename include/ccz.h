@@ -1087,6 +1087,22 @@ CCZ_API int ccz_tree_predict(ccz_handle h, int dtype, const ccz_view* view, int6
                              int64_t k, int64_t n_trees, int64_t max_depth, const int* feature_dev, const float* threshold_dev,
                              const float* leaf_dev, double* out_dev, int64_t ldo);
 
+/* ---- permutation null of the two-view singular values (csrc/perm.hip) ------
+ * sv_dev[b, :] (nperm x r, r = min(p1, p2), float64, descending) = the singular values of
+ *   scale * Z_1' Z_2[pi_b]        Z_i: n x p_i float64, row-major, ld = p_i, device;
+ * pi_b = perms_dev[b * n .. b * n + n) (int32, device), perms_dev NULL = the identity (nperm must then be 1).  The rows of
+ * Z_1 are read in order, those of Z_2 gathered by index; many permutations share one launch (grid: row split x permutation).
+ * The rows are cut into splits of CCZ_PERM_ROWS -- a function of n alone -- whose partial products (fp64 MFMA) go to pooled
+ * scratch and are folded in split order, then one workgroup per permutation runs a one-sided Jacobi SVD.  No floating-point
+ * atomics: the bits of sv_dev[b, :] depend on (Z_1, Z_2, pi_b, scale) only -- not on nperm, on b, or on how a caller cuts
+ * its permutations into calls.  Indices are trusted like sparse indices (an index outside [0, n) reads row 0 or n - 1).
+ * A row of NaN in sv_dev: the Jacobi sweeps did not settle (non-finite input).  Enqueue-only on the handle's stream.
+ * CCZ_EUNSUP: p_i > 64 or n >= 2^31;  CCZ_EINVAL: n, p_i, nperm < 1, a null pointer, or nperm != 1 without perms_dev. */
+#define CCZ_PERM_ROWS 4096
+#define CCZ_PERM_MAXP 64
+CCZ_API int ccz_perm_singular_values(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* Z1_dev, const double* Z2_dev,
+                                     const int32_t* perms_dev, int64_t nperm, double scale, double* sv_dev);
+
 #ifdef __cplusplus
 }
 #endif
