@@ -1,0 +1,280 @@
+"""bootstrap -- resampled weights and canonical correlations of two views, whole refits on the device.
+
+The reference has no counterpart: there, as with the estimators here, the bootstrap is a Python loop of ``B`` refits on
+``[X1[idx], X2[idx]]``.  A resample changes every block of the covariance and the means, so nothing can be whitened once (as
+:func:`~cca_zoo_amd.model_selection.permutation_test` does).  But a resample is fully described by its multiplicity vector
+``m_b`` (``m_b[s]`` = how often row ``s`` was drawn), and its second moments are weighted sums over the rows in their stored order,
+
+    G_b = sum_s m_b[s] x_s x_s',   s_b = sum_s m_b[s] x_s,   x_s = [x1_s, x2_s],
+
+with no gather.  Everything after that is a (p1 + p2)-sized problem per resample:
+
+    C = (G_b - s_b s_b' / n) / (n - 1),  R_i = (1 - c_i) C_ii + c_i I = L_i L_i',  T = L_1^-1 C_12 L_2^-T = U S V',
+    W_1 = L_1^-T U_k,  W_2 = L_2^-T V_k.
+
+``tests/boot_restatement.py`` is the float64 NumPy form the device is held to.
+
+Device side: the full-sample column means in a fixed order of summation (``ccz_als_colmeans``), ``ccz_transform`` with an identity
+weight matrix for the shifted views ``X_i - 1 mu_i'`` (covariances do not change under a shift, and the shift removes the
+cancellation in ``G - s s' / n``), then ``ccz_boot_rcca`` (``csrc/boot.hip``): weighted moments on the fp64 matrix pipe and, per resample, one
+workgroup that factors, solves and runs a one-sided Jacobi SVD with vectors.  The host draws the indices with NumPy and counts
+them (``np.bincount``), one chunk ahead of the device, the arrangement of ``_permutation.py``.  Signs and summaries are the
+host's: a sign flip is exact.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from numbers import Integral, Real
+from typing import Any
+
+import numpy as np
+
+from cca_zoo_amd import _backend
+from cca_zoo_amd._utils._resident import acquire, as_float, refuse_row_sharded, release
+from cca_zoo_amd._utils._validation import is_device_tensor, is_sparse_view, perview_parameter, validate_views
+
+#: resamples per upload and ``ccz_boot_rcca`` call (fewer when a chunk's counts would exceed ``CHUNK_COUNT_BYTES``); the
+#: result does not depend on it by a bit
+CHUNK_RESAMPLES = 64
+CHUNK_COUNT_BYTES = 64 << 20
+#: limits of the device path (``include/ccz.h``: CCZ_PERM_MAXP, CCZ_PERM_ROWS).  ``ROWS_PER_SPLIT`` rows of one resample go to
+#: one workgroup of the weighted moments: the row split is a function of ``n`` alone
+MAX_WIDTH = 64
+ROWS_PER_SPLIT = 4096
+MAX_ROWS = 2 ** 31
+#: ``info`` of ``ccz_boot_rcca`` (``include/ccz.h``: CCZ_BOOT_INFO_*)
+INFO_CAUSES = {
+    1: "R_1 = (1 - c_1) C_11 + c_1 I has a non-positive or non-finite pivot: the resample's view 1 is rank deficient; use c > 0",
+    2: "R_2 = (1 - c_2) C_22 + c_2 I has a non-positive or non-finite pivot: the resample's view 2 is rank deficient; use c > 0",
+    3: "the resample holds fewer than 2 rows",
+    4: "the Jacobi sweeps of the singular value decomposition did not settle",
+}
+
+
+@dataclass
+class BootstrapResult:
+    """What :func:`bootstrap` returns; ``r = min(p1, p2)``, ``k = min(latent_dimensions, r)``, ``B = n_resamples``."""
+
+    singular_values: np.ndarray         # (r,)    observed values (the device path with all multiplicities 1), descending
+    singular_values_boot: np.ndarray    # (B, r)  the same for each resample
+    singular_values_se: np.ndarray      # (r,)    std over the resamples, ddof = 1
+    singular_values_ci: np.ndarray      # (2, r)  percentile interval
+    weights: list                       # two (p_i, k): observed weights, largest stacked entry of each column positive
+    weights_boot: list                  # two (B, p_i, k): per resample, each column aligned in sign with the observed one
+    weights_se: list                    # two (p_i, k)
+    weights_ci: list                    # two (2, p_i, k)
+    bootstrap_ratio: list               # two (p_i, k): weights / weights_se
+    estimator: Any                      # the clone fitted on the full views by its ordinary fit
+
+
+def draw_counts(rng, n, count):
+    """``count`` x ``n`` multiplicities (int32): row ``b`` counts the ``b``-th ``rng.integers(0, n, size=n)``."""
+    out = np.empty((count, n), dtype=np.int32)
+    for b in range(count):
+        out[b] = np.bincount(rng.integers(0, n, size=n), minlength=n)
+    return out
+
+
+def count_chunks(rng, n, total, chunk):
+    """The ``total`` resamples of :func:`draw_counts` in chunks of at most ``chunk``, drawn as they are asked for."""
+    done = 0
+    while done < total:
+        step = min(int(chunk), total - done)
+        yield draw_counts(rng, n, step)
+        done += step
+
+
+def chunk_length(n):
+    """Resamples per upload: ``CHUNK_RESAMPLES``, fewer when their counts would exceed ``CHUNK_COUNT_BYTES``."""
+    return max(1, min(int(CHUNK_RESAMPLES), CHUNK_COUNT_BYTES // (4 * n)))
+
+
+def orient_observed(W):
+    """Flip each column of the stacked weights ``W`` ((p1 + p2) x k) so that its entry of largest magnitude (ties: the first) is
+    positive; the two views of a column flip together."""
+    W = np.array(W, dtype=np.float64)
+    if W.size:
+        lead = W[np.argmax(np.abs(W), axis=0), np.arange(W.shape[1])]
+        W[:, lead < 0] *= -1.0
+    return W
+
+
+def orient_to(Wb, W):
+    """Flip each column of every resample of ``Wb`` (B x (p1 + p2) x k) whose dot product with the observed column is < 0."""
+    Wb = np.array(Wb, dtype=np.float64)
+    Wb *= np.where(np.einsum("bij,ij->bj", Wb, W) < 0, -1.0, 1.0)[:, None, :]
+    return Wb
+
+
+def summaries(boot, confidence_level):
+    """``(se, ci)``: ``std(axis=0, ddof=1)`` and the percentile interval ``quantile([(1 - cl) / 2, (1 + cl) / 2], axis=0)``."""
+    boot = np.asarray(boot, dtype=np.float64)
+    q = [(1.0 - confidence_level) / 2.0, (1.0 + confidence_level) / 2.0]
+    return np.std(boot, axis=0, ddof=1), np.quantile(boot, q, axis=0)
+
+
+def _is_half(v):
+    if type(v).__module__.startswith("torch"):
+        return bool(v.dtype.is_floating_point) and v.element_size() == 2
+    return getattr(getattr(v, "dtype", None), "itemsize", 0) == 2 and getattr(v.dtype, "kind", "") == "f"
+
+
+def check_limits(n, p, n_resamples, confidence_level):
+    """``ValueError`` for what the device path excludes, before the device is touched."""
+    if isinstance(n_resamples, bool) or not isinstance(n_resamples, Integral) or n_resamples < 2:
+        raise ValueError(f"n_resamples must be an integer >= 2 (a standard error needs two), got {n_resamples!r}")
+    if isinstance(confidence_level, bool) or not isinstance(confidence_level, Real) or not 0.0 < confidence_level < 1.0:
+        raise ValueError(f"confidence_level must be a number in (0, 1), got {confidence_level!r}")
+    if max(p) > MAX_WIDTH:
+        raise ValueError(f"bootstrap: views of at most {MAX_WIDTH} columns are supported, got {list(p)}; reduce wider "
+                         "views first (e.g. to their leading principal components)")
+    if n >= MAX_ROWS:
+        raise ValueError(f"bootstrap: fewer than 2^31 rows are supported, got {n}")
+    if n - 1 <= 0:
+        raise ValueError("at least 2 samples are required")
+
+
+def _shifted(h, xptr, n, d, center):
+    """The device float64 view minus its full-sample column means (``center``) as a device buffer, or ``None`` for the view as
+    it is; raises for non-finite input."""
+    vp = C.c_void_p
+    view = _backend.View()
+    view.data, view.cols, view.ld = int(xptr), d, d
+    mu_d = h.alloc(d * 8)
+    # the rows added in order, one thread per column: the same bits on every call (the K1 pass, ``ccz_moments``, folds its row
+    # chunks with atomics, and a mean that moves in its last bit moves every bit after it)
+    h.check(h.lib.ccz_als_colmeans(h.raw, _backend.F64, C.byref(view), n, vp(mu_d.ptr)))
+    if not np.all(np.isfinite(h.to_host(mu_d, (d,)))):      # a NaN or an infinity anywhere in a column shows in its mean
+        raise ValueError("Input contains NaN or infinity.")
+    if not center:
+        return None
+    w_d, z_d = h.to_device(np.eye(d)), h.alloc(n * d * 8)
+    # (x - mu) I: the other products of a row are exact zeros, so z is the correctly rounded x - mu in any order of summation
+    h.check(h.lib.ccz_transform(h.raw, _backend.F64, vp(xptr), n, d, d, vp(mu_d.ptr), vp(w_d.ptr), d, vp(z_d.ptr), d))
+    return z_d
+
+
+def boot_rcca(h, n, p1, p2, x1_ptr, x2_ptr, counts_ptr, nboot, c1, c2, center, k, sv_ptr, w_ptr, info_ptr):
+    """One ``ccz_boot_rcca`` call (enqueue-only); ``counts_ptr`` None = all multiplicities 1."""
+    vp = C.c_void_p
+    h.check(h.lib.ccz_boot_rcca(h.raw, int(n), int(p1), int(p2), vp(int(x1_ptr)), vp(int(x2_ptr)),
+                                vp(int(counts_ptr)) if counts_ptr else None, int(nboot), float(c1), float(c2), int(bool(center)),
+                                int(k), vp(int(sv_ptr)), vp(int(w_ptr)), vp(int(info_ptr))))
+
+
+def raise_for_info(info):
+    """``np.linalg.LinAlgError`` for the first non-zero ``info`` (``info[0]``: the observed sample, ``info[1 + b]``: resample b)."""
+    for i in np.flatnonzero(info):
+        which = "the observed sample" if i == 0 else f"resample {i - 1}"
+        code = int(info[i])
+        raise np.linalg.LinAlgError(f"bootstrap: {which}: {INFO_CAUSES.get(code, f'info = {code}')}")
+
+
+def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_state=None):
+    r"""Non-parametric bootstrap of the weights and singular values of a two-view CCA, rCCA or PLS.
+
+    The rows are drawn with replacement ``n_resamples`` times (n out of n); every resample is refitted on the device from
+    its multiplicity-weighted moments, without gathering rows (see the module docstring).  The observed values come from
+    the same device path with all multiplicities 1.
+
+    Args:
+        estimator: an unfitted :class:`~cca_zoo_amd.linear.CCA`, :class:`~cca_zoo_amd.linear.rCCA` or
+            :class:`~cca_zoo_amd.linear.PLS` (or a subclass of ``rCCA``); its ridge ``c``, ``center`` and
+            ``latent_dimensions`` define the problem, ``k = min(latent_dimensions, p1, p2)`` weight columns are kept.  The
+            object itself is not changed (a clone is fitted).
+        views: two (n, p_i) host ``float32`` / ``float64`` arrays, or two 2-D CUDA tensors of those dtypes.  float32 views
+            are widened to float64 once; everything after that is float64.
+        n_resamples: ``B >= 2``.
+        confidence_level: level of the percentile intervals, in (0, 1).
+        random_state: seed of ``np.random.default_rng``; resample ``b`` is the ``b``-th ``rng.integers(0, n, size=n)``.
+
+    Returns:
+        :class:`BootstrapResult`.  ``se = std(axis=0, ddof=1)``, ``ci = quantile(boot, [(1 - cl) / 2, (1 + cl) / 2], axis=0)``,
+        ``bootstrap_ratio = weights / weights_se``.  Each observed weight column is signed so that the entry of largest
+        magnitude of the stacked column ``[w1; w2]`` is positive; each resampled column so that its stacked dot product with
+        the observed column is >= 0 (the two views of a column always flip together).
+
+    Limits of this first cut (``ValueError`` before the device is touched): ``max(p1, p2) <= 64`` -- wider views are reduced
+    first (e.g. to their leading principal components); ``n < 2^31``; ``n >= 2``.  Sparse views and half-precision views raise
+    ``TypeError``; a call inside :func:`cca_zoo_amd.row_sharded` raises ``NotImplementedError``.  A resample whose regularised
+    covariance cannot be factored (with ``c = 0``: fewer distinct rows than columns) raises ``np.linalg.LinAlgError`` that
+    names the resample and the remedy ``c > 0``.
+    """
+    from sklearn.base import clone
+
+    from cca_zoo_amd.linear import rCCA
+
+    if not isinstance(estimator, rCCA):
+        raise TypeError(f"bootstrap takes a CCA, rCCA or PLS estimator, got {type(estimator).__name__}")
+    refuse_row_sharded("bootstrap refits on all rows of one device, which this build does not shard by rows")
+    if not isinstance(views, (list, tuple)):
+        raise TypeError("views must be a list of two arrays or CUDA tensors")
+    for v in views:
+        if is_sparse_view(v):
+            raise TypeError("bootstrap: sparse views are not supported; pass dense arrays")
+        if _is_half(v):
+            raise TypeError("bootstrap: half-precision views are not supported; pass float32 or float64")
+    est = clone(estimator)
+    est._validate_params()
+    views_ = [as_float(v) for v in validate_views(list(views), check_finite=False)]
+    if len(views_) != 2:
+        raise ValueError(f"bootstrap requires exactly 2 views, got {len(views_)}")
+    n, p = int(views_[0].shape[0]), [int(v.shape[1]) for v in views_]
+    check_limits(n, p, n_resamples, confidence_level)
+    dev = [is_device_tensor(v) for v in views_]
+    if any(dev) and not all(dev):
+        raise ValueError("views must be all host arrays or all CUDA tensors")
+    c_ = [float(v) for v in perview_parameter("c", est.c, 0.0, 2)]
+    center, B, r = bool(est.center), int(n_resamples), min(p)
+    k, pt = min(int(est.latent_dimensions), r), p[0] + p[1]
+    rng = np.random.default_rng(random_state)
+
+    h = _backend.handle_for(views_)
+    # float64 copies for K1 and the shift, made before the handle's stream takes over (CUDA: on the caller's stream)
+    if all(dev):
+        import torch
+
+        x64 = [v.to(torch.float64).contiguous() for v in views_]
+        xptr = [int(x.data_ptr()) for x in x64]
+    else:
+        x64 = [h.to_device(np.ascontiguousarray(v, dtype=np.float64)) for v in views_]
+        xptr = [int(b.ptr) for b in x64]
+    sp = acquire(h, views_)
+    try:
+        Z = [_shifted(h, xptr[i], n, p[i], center) for i in range(2)]
+        zptr = [int(z.ptr) if z is not None else xptr[i] for i, z in enumerate(Z)]
+        sv, W, info = h.alloc((B + 1) * r * 8), h.alloc((B + 1) * pt * k * 8), h.alloc((B + 1) * 4)
+        boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], None, 1, c_[0], c_[1], center, k, sv.ptr, W.ptr, info.ptr)
+        chunk = chunk_length(n)
+        slots = [h.alloc(min(chunk, B) * n * 4) for _ in range(2)]
+        done = 0
+        # the next chunk is drawn while the device works on this one; the upload is ordered behind it on the handle's stream
+        for i, counts in enumerate(count_chunks(rng, n, B, chunk)):
+            slot = slots[i & 1]
+            h.h2d(slot.ptr, counts)
+            boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], slot.ptr, counts.shape[0], c_[0], c_[1], center, k,
+                      sv.ptr + (1 + done) * r * 8, W.ptr + (1 + done) * pt * k * 8, info.ptr + (1 + done) * 4)
+            done += counts.shape[0]
+        sv_h, W_h = h.to_host(sv, (B + 1, r)), h.to_host(W, (B + 1, pt, k))
+        info_h = h.to_host(info, (B + 1,), dtype=np.int32)
+    finally:
+        release(h, sp)
+    del x64, Z, slots
+    raise_for_info(info_h)
+    if not np.all(np.isfinite(sv_h)) or not np.all(np.isfinite(W_h)):
+        raise np.linalg.LinAlgError("bootstrap: the resampled solutions are not finite")
+    W_obs = orient_observed(W_h[0])
+    W_boot = orient_to(W_h[1:], W_obs)
+    sv_se, sv_ci = summaries(sv_h[1:], confidence_level)
+    w_se, w_ci = summaries(W_boot, confidence_level)
+    cut = [slice(0, p[0]), slice(p[0], pt)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = W_obs / w_se
+    est.fit(list(views))
+    return BootstrapResult(singular_values=sv_h[0].copy(), singular_values_boot=sv_h[1:].copy(), singular_values_se=sv_se,
+                           singular_values_ci=sv_ci, weights=[W_obs[s].copy() for s in cut],
+                           weights_boot=[np.ascontiguousarray(W_boot[:, s]) for s in cut], weights_se=[w_se[s].copy() for s in cut],
+                           weights_ci=[np.ascontiguousarray(w_ci[:, s]) for s in cut], bootstrap_ratio=[ratio[s].copy() for s in cut],
+                           estimator=est)

@@ -1103,6 +1103,31 @@ CCZ_API int ccz_tree_predict(ccz_handle h, int dtype, const ccz_view* view, int6
 CCZ_API int ccz_perm_singular_values(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* Z1_dev, const double* Z2_dev,
                                      const int32_t* perms_dev, int64_t nperm, double scale, double* sv_dev);
 
+/* ---- bootstrap refits of the two-view ridge CCA (csrc/boot.hip) -----------
+ * Resample b is its multiplicity vector m_b = counts_dev[b * n .. b * n + n) (int32, device: how often row s was drawn);
+ * counts_dev NULL = all ones (nboot must then be 1).  With x_s = [x1_s, x2_s] (X_i: n x p_i float64, row-major, ld = p_i,
+ * device) and N_b = sum_s m_b[s]:
+ *   G_b = sum_s m_b[s] x_s x_s',  s_b = sum_s m_b[s] x_s,  C = (G_b - s_b s_b' / N_b) / (N_b - 1)  (center = 0: G_b / (N_b - 1))
+ *   R_i = (1 - c_i) C_ii + c_i I = L_i L_i',   T = L_1^-1 C_12 L_2^-T = U S V',   W_1 = L_1^-T U_k,  W_2 = L_2^-T V_k.
+ * sv_dev[b, :] (nboot x r, r = min(p1, p2), descending) = S;  W_dev[b] ((p1 + p2) x k row-major, the rows of view 1 first) =
+ * [W_1; W_2], column j in the coupled sign of the pair (u_j, v_j) -- no other sign rule;  info_dev[b]: 0, or CCZ_BOOT_INFO_*
+ * (the resample's rows of sv_dev and W_dev are then NaN).  The divisor is N_b, not n: 0/1 counts give subsampling.  The rows
+ * are read in their stored order (no gather; a staged chunk whose counts are all zero is skipped), in splits of CCZ_PERM_ROWS
+ * rows -- a function of n alone -- whose partial moments (fp64 MFMA; the 11 and 22 blocks on and above the diagonal only) go
+ * to pooled scratch and are folded in split order; one workgroup per resample then factors, solves and runs a one-sided
+ * Jacobi SVD that accumulates the right vectors.  No floating-point atomics: the bits of resample b depend on (X, m_b, c, center, k)
+ * only -- not on nboot, on b, or on how a caller cuts its resamples into calls.  Counts are trusted (nothing is dereferenced
+ * through them).  With center set, pass views whose column means are near zero (the covariance does not change under a shift;
+ * G_b - s_b s_b' / N_b cancels otherwise).  Enqueue-only on the handle's stream.
+ * CCZ_EUNSUP: p_i > 64 or n >= 2^31;  CCZ_EINVAL: n, p_i, nboot, k < 1, k > r, a null pointer, or nboot != 1 without counts_dev. */
+#define CCZ_BOOT_INFO_R1 1       /* R_1 has a non-positive or non-finite pivot */
+#define CCZ_BOOT_INFO_R2 2       /* R_2 has a non-positive or non-finite pivot */
+#define CCZ_BOOT_INFO_N 3        /* N_b < 2 */
+#define CCZ_BOOT_INFO_JACOBI 4   /* the Jacobi sweeps did not settle */
+CCZ_API int ccz_boot_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* X1_dev, const double* X2_dev,
+                          const int32_t* counts_dev, int64_t nboot, double c1, double c2, int center, int64_t k, double* sv_dev,
+                          double* W_dev, int32_t* info_dev);
+
 #ifdef __cplusplus
 }
 #endif
