@@ -5,51 +5,32 @@
 //   G_b = sum_s m_b[s] x_s x_s',  s_b = sum_s m_b[s] x_s,  N_b = sum_s m_b[s]          x_s = [x1_s, x2_s], p_i <= 64.
 // No gather: the reads are contiguous and a row with m = 0 is not read at all.
 //
+// The block product, the Jacobi and the batch loop are those of resample_dev.h.
+//
 //   k_boot_moments  grid (row split, resample, block in {11, 12, 22}), 256 threads.  A workgroup owns rows
 //                   [z * CCZ_PERM_ROWS, (z + 1) * CCZ_PERM_ROWS) of ONE resample and one block A' diag(m) B of G_b (11: A = B = X_1,
-//                   12: A = X_1, B = X_2, 22: A = B = X_2).  Staging and lane maps are those of perm.hip: chunks of 32 rows, LDS
-//                   stride 80, v_mfma_f64_16x16x4f64 with A operand block row (= A column) = lane & 15, sample = lane >> 4; B operand
-//                   sample = lane >> 4, block column = lane & 15; C/D column = lane & 15, row = (lane >> 4) + 4 reg.  The A operand is
-//                   multiplied by double(m_b[s]) (exact) while it is staged; a chunk whose 32 multiplicities are all zero is
-//                   skipped.  The 11 and 22 blocks compute only the tiles on or above the diagonal.  The 11 and 22 workgroups also
-//                   sum the weighted columns (s_b; 4 row groups of 8 per chunk, added in group order at the end) and the 11
-//                   workgroup the multiplicities (N_b, an integer sum).  Partials: part[resample][split][PER].
+//                   12: A = X_1, B = X_2, 22: A = B = X_2).  The A operand is multiplied by double(m_b[s]) (exact) while it is
+//                   staged; a chunk whose 32 multiplicities are all zero is skipped.  The 11 and 22 blocks compute only the
+//                   tiles on or above the diagonal.  The 11 and 22 workgroups also sum the weighted columns (s_b; 4 row groups
+//                   of 8 per chunk, added in group order at the end) and the 11 workgroup the multiplicities (N_b, an integer
+//                   sum).  Partials: part[resample][split][PER].
 //   k_boot_fold     grid (entries / 256, resample), only when there is more than one split: the partials of a resample added
 //                   in split order, one thread per entry.
 //   k_boot_solve    grid (resample), 256 threads, four 64 x 65 LDS blocks (R_1 -> L_1, R_2 -> L_2, C_12 -> T -> U S, V).  Takes
 //                   the folded moments (one split: the partial itself), C = (G - s s' / N_b) / (N_b - 1) (center = 0: G / (N_b - 1)),
 //                   R_i = (1 - c_i) C_ii + c_i I = L_i L_i' (left-looking Cholesky in place, both views side by side, 2 lanes per
-//                   row), T = L_1^-1 C_12 L_2^-T (two substitutions, 4 lanes per column / row), then the one-sided Jacobi of
-//                   k_perm_fold_svd (narrower side as columns, 8 lanes per pair, stop at 4 eps, at most 30 sweeps) with the right
-//                   rotations accumulated in V.  Singular values = column norms ranked descending, left vectors = normalised
-//                   columns (norm 0: zeros), W_1 = L_1^-T U_k, W_2 = L_2^-T V_k by back substitution (roles swapped for
-//                   p1 < p2); the pair (u_j, v_j) keeps its coupled sign.  info: see include/ccz.h; non-zero -> NaN rows.
-// The split of the rows is a function of n alone and every sum has a fixed order: no floating-point atomics, and the bits of
-// resample b do not depend on how many resamples a call holds.  A call with more resamples than the scratch budget allows runs
-// as several launch groups.  Nothing is dereferenced through a count, so a bad count cannot fault.
-#include <algorithm>
-#include <cstdint>
-
+//                   row), T = L_1^-1 C_12 L_2^-T (two substitutions, 4 lanes per column / row), then the Jacobi sweeps on T
+//                   (narrower side as columns) with the right rotations accumulated in V.  Singular values = ranked column
+//                   norms, left vectors = normalised columns (norm 0: zeros), W_1 = L_1^-T U_k, W_2 = L_2^-T V_k by back
+//                   substitution (roles swapped for p1 < p2); the pair (u_j, v_j) keeps its coupled sign.  info: see
+//                   include/ccz.h; non-zero -> NaN rows.
+// Nothing is dereferenced through a count, so a bad count cannot fault.
 #include "abi_guard.h"
-#include "hip_common.h"
-#include "jacobi_dev.h"
+#include "resample_dev.h"
 
 namespace ccz {
 
 namespace {
-
-constexpr int BOOT_ROWS = CCZ_PERM_ROWS;             // rows per split
-constexpr int BOOT_MAXP = CCZ_PERM_MAXP;             // widest view
-constexpr int BOOT_S = 32;                           // rows per staged chunk
-constexpr int BOOT_LW = 80;                          // LDS row stride of a staged chunk (80 % 32 == 16, as perm.hip)
-constexpr int BOOT_LDA = BOOT_MAXP + 1;              // LDS stride of the solve's blocks
-constexpr int BOOT_SWEEPS = 30;
-constexpr int64_t BOOT_SCRATCH = int64_t(1) << 25;   // doubles of partials per launch (256 MiB)
-constexpr int64_t BOOT_MAXBATCH = 65535;             // gridDim.y
-
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double boot_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // partial of one (resample, split): G11 [P1][P1] | G12 [P1][P2] | G22 [P2][P2] | s1 [P1] | s2 [P2] | N     (P_i = p_i rounded up to 16)
 __host__ __device__ inline int boot_per(int P1, int P2) { return P1 * P1 + P1 * P2 + P2 * P2 + P1 + P2 + 1; }
@@ -57,10 +38,10 @@ __host__ __device__ inline int boot_per(int P1, int P2) { return P1 * P1 + P1 * 
 __global__ void __launch_bounds__(256) k_boot_moments(const double* __restrict__ X1, const double* __restrict__ X2,
                                                       const int* __restrict__ counts, int64_t n, int p1, int p2,
                                                       double* __restrict__ part) {
-  __shared__ double lds[2 * BOOT_S * BOOT_LW];
+  __shared__ double lds[2 * RS_S * RS_LW];
   __shared__ long long cnt_s[16];
   double* As = lds;
-  double* Bs = lds + BOOT_S * BOOT_LW;
+  double* Bs = lds + RS_S * RS_LW;
   const int kind = blockIdx.z;                           // 0: block 11, 1: block 12, 2: block 22
   const bool diag = kind != 1;
   const double* XA = kind == 2 ? X2 : X1;
@@ -68,11 +49,10 @@ __global__ void __launch_bounds__(256) k_boot_moments(const double* __restrict__
   const int pa = kind == 2 ? p2 : p1, pb = kind == 0 ? p1 : p2;
   const int nrt = (pa + 15) >> 4, nct = (pb + 15) >> 4, PA = 16 * nrt, PB = 16 * nct;
   const int P1 = 16 * ((p1 + 15) >> 4), P2 = 16 * ((p2 + 15) >> 4);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-  const int G = 4 / nrt, rt = wave % nrt, grp = wave / nrt;
-  const bool active = grp < G;
-  const int64_t sb = int64_t(blockIdx.x) * BOOT_ROWS;
-  const int64_t se = sb + BOOT_ROWS < n ? sb + BOOT_ROWS : n;
+  const mma_lanes L(nrt);
+  const int tid = threadIdx.x;
+  const int64_t sb = int64_t(blockIdx.x) * RS_ROWS;
+  const int64_t se = sb + RS_ROWS < n ? sb + RS_ROWS : n;
   const int* mb = counts ? counts + int64_t(blockIdx.y) * n : nullptr;
   const int sr = tid >> 4, sc = tid & 15;
   const int scol = tid & 63, sq = tid >> 6;              // column sums: column scol, rows 8 sq .. 8 sq + 7 of a chunk
@@ -81,7 +61,7 @@ __global__ void __launch_bounds__(256) k_boot_moments(const double* __restrict__
   for (int ct = 0; ct < 4; ++ct) acc[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
   double ssum = 0.0;
   long long cnt = 0;
-  for (int64_t s0 = sb; s0 < se; s0 += BOOT_S) {
+  for (int64_t s0 = sb; s0 < se; s0 += RS_S) {
     int m[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -97,55 +77,22 @@ __global__ void __launch_bounds__(256) k_boot_moments(const double* __restrict__
       const double w = double(m[j]);
       const double* a = XA + s * pa;
       const double* b = XB + s * pb;
-      for (int cc = sc; cc < PA; cc += 16) As[sl * BOOT_LW + cc] = (ok && cc < pa) ? w * a[cc] : 0.0;
-      for (int cc = sc; cc < PB; cc += 16) Bs[sl * BOOT_LW + cc] = (ok && cc < pb) ? b[cc] : 0.0;
+      for (int cc = sc; cc < PA; cc += 16) As[sl * RS_LW + cc] = (ok && cc < pa) ? w * a[cc] : 0.0;
+      for (int cc = sc; cc < PB; cc += 16) Bs[sl * RS_LW + cc] = (ok && cc < pb) ? b[cc] : 0.0;
     }
     if (sc == 0) cnt += (long long)m[0] + (long long)m[1];
     __syncthreads();
-    if (active) {
-      for (int k4 = 4 * grp; k4 < BOOT_S; k4 += 4 * G) {
-        const double av = As[(k4 + lg) * BOOT_LW + 16 * rt + li];
-        const double* br = Bs + (k4 + lg) * BOOT_LW + li;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          if (ct < nct && (!diag || ct >= rt)) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, br[16 * ct], acc[ct], 0, 0, 0);
-      }
-    }
+    mma_chunk(As, Bs, L, diag, nct, acc);
     if (diag && scol < PA) {
       double t = 0.0;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) t += As[(8 * sq + i) * BOOT_LW + scol];
+      for (int i = 0; i < 8; ++i) t += As[(8 * sq + i) * RS_LW + scol];
       ssum += t;
     }
   }
-  if (G > 1) {                                           // nrt <= 2: every wave is active; add the k-step groups in wave order
-    __syncthreads();
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) lds[((wave * 4 + ct) * 4 + g) * 64 + lane] = acc[ct][g];
-    __syncthreads();
-    if (grp == 0) {
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          double s = lds[((rt * 4 + ct) * 4 + g) * 64 + lane];
-          for (int q = 1; q < G; ++q) s += lds[(((rt + nrt * q) * 4 + ct) * 4 + g) * 64 + lane];
-          acc[ct][g] = s;
-        }
-    }
-  }
+  fold_kgroups(lds, L, acc);
   double* base = part + (int64_t(blockIdx.y) * gridDim.x + blockIdx.x) * int64_t(boot_per(P1, P2));
-  if (grp == 0) {
-    double* out = base + (kind == 0 ? 0 : (kind == 1 ? P1 * P1 : P1 * P1 + P1 * P2));
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      if (ct >= nct || (diag && ct < rt)) continue;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) out[(16 * rt + lg + 4 * g) * PB + 16 * ct + li] = acc[ct][g];
-    }
-  }
+  store_tiles(base + (kind == 0 ? 0 : (kind == 1 ? P1 * P1 : P1 * P1 + P1 * P2)), PB, L, diag, nct, acc);
   if (!diag) return;                                     // (uniform: kind is the workgroup's)
   __syncthreads();
   lds[sq * 64 + scol] = ssum;
@@ -172,39 +119,27 @@ __global__ void __launch_bounds__(256) k_boot_fold(const double* __restrict__ pa
   folded[int64_t(blockIdx.y) * PER + e] = s;
 }
 
-__device__ __forceinline__ double sum8(double v) {       // every lane of an aligned group of 8 gets the same bits
-  v += __shfl_xor(v, 4, 8);
-  v += __shfl_xor(v, 2, 8);
-  v += __shfl_xor(v, 1, 8);
-  return v;
-}
-__device__ __forceinline__ double sum4(double v) {
-  v += __shfl_xor(v, 2, 4);
-  v += __shfl_xor(v, 1, 4);
-  return v;
-}
-
 __device__ void boot_refuse(int64_t b, int r, int p1, int p2, int k, int code, double* __restrict__ sv, double* __restrict__ W,
                             int* __restrict__ info) {
   const int tid = threadIdx.x;
-  for (int e = tid; e < r; e += 256) sv[b * r + e] = boot_nan();
+  for (int e = tid; e < r; e += 256) sv[b * r + e] = rs_nan();
   const int nw = (p1 + p2) * k;
-  for (int e = tid; e < nw; e += 256) W[b * nw + e] = boot_nan();
+  for (int e = tid; e < nw; e += 256) W[b * nw + e] = rs_nan();
   if (tid == 0) info[b] = code;
 }
 
 __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ part, int nsplit, int p1, int p2, double c1, double c2,
                                                     int center, int k, double* __restrict__ sv, double* __restrict__ W,
                                                     int* __restrict__ info) {
-  __shared__ double B11[BOOT_MAXP * BOOT_LDA];           // R_1, then L_1 (row i at B11 + i * BOOT_LDA, lower triangle)
-  __shared__ double B22[BOOT_MAXP * BOOT_LDA];           // R_2, then L_2
-  __shared__ double TA[BOOT_MAXP * BOOT_LDA];            // C_12, then T, then U S: the narrower side's index has stride BOOT_LDA
-  __shared__ double VV[BOOT_MAXP * BOOT_LDA];            // the accumulated right rotations, column j at VV + j * BOOT_LDA
-  __shared__ double svec[2 * BOOT_MAXP];
-  __shared__ double nrm[BOOT_MAXP];
+  __shared__ double B11[RS_MAXP * RS_LDA];               // R_1, then L_1 (row i at B11 + i * RS_LDA, lower triangle)
+  __shared__ double B22[RS_MAXP * RS_LDA];               // R_2, then L_2
+  __shared__ double TA[RS_MAXP * RS_LDA];                // C_12, then T, then U S: the narrower side's index has stride RS_LDA
+  __shared__ double VV[RS_MAXP * RS_LDA];                // the accumulated right rotations, column j at VV + j * RS_LDA
+  __shared__ double svec[2 * RS_MAXP];
+  __shared__ double nrm[RS_MAXP];
   __shared__ double piv[2];
   __shared__ double Nsh;
-  __shared__ int inv[BOOT_MAXP];
+  __shared__ int inv[RS_MAXP];
   __shared__ int bad[2];
   __shared__ int moved;
   const int tid = threadIdx.x;
@@ -212,7 +147,7 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
   const int P1 = 16 * ((p1 + 15) >> 4), P2 = 16 * ((p2 + 15) >> 4), PER = boot_per(P1, P2);
   const bool tr = p1 < p2;                               // the narrower side of T gives the Jacobi columns
   const int m = tr ? p2 : p1, r = tr ? p1 : p2;
-  const int si = tr ? BOOT_LDA : 1, sj = tr ? 1 : BOOT_LDA;   // T(i, j) = TA[i * si + j * sj]
+  const int si = tr ? RS_LDA : 1, sj = tr ? 1 : RS_LDA;   // T(i, j) = TA[i * si + j * sj]
   const double* src = part + b * int64_t(nsplit) * PER;
   const int o12 = P1 * P1, o22 = o12 + P1 * P2, os = o22 + P2 * P2;
 
@@ -222,7 +157,7 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
     if (i > j || j >= p1) continue;
     double s = 0.0;
     for (int z = 0; z < nsplit; ++z) s += src[int64_t(z) * PER + e];
-    B11[i * BOOT_LDA + j] = s;
+    B11[i * RS_LDA + j] = s;
   }
   for (int e = tid; e < P1 * P2; e += 256) {
     const int i = e / P2, j = e - i * P2;
@@ -236,7 +171,7 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
     if (i > j || j >= p2) continue;
     double s = 0.0;
     for (int z = 0; z < nsplit; ++z) s += src[int64_t(z) * PER + o22 + e];
-    B22[i * BOOT_LDA + j] = s;
+    B22[i * RS_LDA + j] = s;
   }
   if (tid < p1 + p2) {
     const int e = tid < p1 ? tid : P1 + (tid - p1);
@@ -262,20 +197,20 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
   for (int e = tid; e < p1 * p1; e += 256) {
     const int i = e / p1, j = e - i * p1;
     if (i > j) continue;
-    double g = B11[i * BOOT_LDA + j];
+    double g = B11[i * RS_LDA + j];
     if (center) g -= svec[i] * (svec[j] / N);
     g = (1.0 - c1) * (g / dn) + (i == j ? c1 : 0.0);
-    B11[i * BOOT_LDA + j] = g;
-    B11[j * BOOT_LDA + i] = g;
+    B11[i * RS_LDA + j] = g;
+    B11[j * RS_LDA + i] = g;
   }
   for (int e = tid; e < p2 * p2; e += 256) {
     const int i = e / p2, j = e - i * p2;
     if (i > j) continue;
-    double g = B22[i * BOOT_LDA + j];
+    double g = B22[i * RS_LDA + j];
     if (center) g -= svec[p1 + i] * (svec[p1 + j] / N);
     g = (1.0 - c2) * (g / dn) + (i == j ? c2 : 0.0);
-    B22[i * BOOT_LDA + j] = g;
-    B22[j * BOOT_LDA + i] = g;
+    B22[i * RS_LDA + j] = g;
+    B22[j * RS_LDA + i] = g;
   }
   for (int e = tid; e < p1 * p2; e += 256) {
     const int i = e / p2, j = e - i * p2;
@@ -285,7 +220,7 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
   }
   for (int e = tid; e < r * r; e += 256) {
     const int i = e / r, j = e - i * r;
-    VV[j * BOOT_LDA + i] = i == j ? 1.0 : 0.0;
+    VV[j * RS_LDA + i] = i == j ? 1.0 : 0.0;
   }
   // ---- R_i = L_i L_i' in place, left-looking: threads [0, 128) view 1, [128, 256) view 2, 2 lanes per row
   {
@@ -298,9 +233,9 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
       double v = 0.0;
       if (mine) {
         double d = 0.0;
-        for (int q = ln; q < j; q += 2) d = fma(L[row * BOOT_LDA + q], L[j * BOOT_LDA + q], d);
+        for (int q = ln; q < j; q += 2) d = fma(L[row * RS_LDA + q], L[j * RS_LDA + q], d);
         d += __shfl_xor(d, 1, 2);
-        v = L[row * BOOT_LDA + j] - d;
+        v = L[row * RS_LDA + j] - d;
         if (row == j && ln == 0) piv[half] = v;
       }
       __syncthreads();
@@ -309,7 +244,7 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
         if (!(d > 0.0) || !(d <= 1.7976931348623157e308)) {
           if (row == j && ln == 0) bad[half] = 1;
         }
-        if (ln == 0) L[row * BOOT_LDA + j] = row == j ? sqrt(d) : v / sqrt(d);
+        if (ln == 0) L[row * RS_LDA + j] = row == j ? sqrt(d) : v / sqrt(d);
       }
     }
   }
@@ -324,75 +259,29 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
     for (int i = 0; i < p1; ++i) {
       if (g < p2) {
         double d = 0.0;
-        for (int q = l; q < i; q += 4) d = fma(B11[i * BOOT_LDA + q], TA[q * si + g * sj], d);
+        for (int q = l; q < i; q += 4) d = fma(B11[i * RS_LDA + q], TA[q * si + g * sj], d);
         d = sum4(d);
-        if (l == 0) TA[i * si + g * sj] = (TA[i * si + g * sj] - d) / B11[i * BOOT_LDA + i];
+        if (l == 0) TA[i * si + g * sj] = (TA[i * si + g * sj] - d) / B11[i * RS_LDA + i];
       }
       __syncthreads();
     }
     for (int j = 0; j < p2; ++j) {
       if (g < p1) {
         double d = 0.0;
-        for (int q = l; q < j; q += 4) d = fma(TA[g * si + q * sj], B22[j * BOOT_LDA + q], d);
+        for (int q = l; q < j; q += 4) d = fma(TA[g * si + q * sj], B22[j * RS_LDA + q], d);
         d = sum4(d);
-        if (l == 0) TA[g * si + j * sj] = (TA[g * si + j * sj] - d) / B22[j * BOOT_LDA + j];
+        if (l == 0) TA[g * si + j * sj] = (TA[g * si + j * sj] - d) / B22[j * RS_LDA + j];
       }
       __syncthreads();
     }
   }
-  // ---- one-sided Jacobi on the m x r matrix whose column j is TA + j * BOOT_LDA; V takes the same rotations
-  const int g8 = tid >> 3, t8 = tid & 7;
-  const int re = (r + 1) & ~1, m1 = re - 1, np = re >> 1;
-  const double tol = 4.0 * 2.220446049250313e-16;
-  bool settled = false;
-  for (int sweep = 0; sweep < BOOT_SWEEPS && !settled; ++sweep) {
-    __syncthreads();
-    if (tid == 0) moved = 0;
-    for (int round = 0; round < m1; ++round) {
-      __syncthreads();
-      int p = re, q = re;
-      if (g8 < np) pair_of(round, g8, m1, p, q);
-      if (p < r && q < r) {
-        double* ap = TA + p * BOOT_LDA;
-        double* aq = TA + q * BOOT_LDA;
-        double hpp = 0.0, hqq = 0.0, hpq = 0.0;
-        for (int i = t8; i < m; i += 8) {
-          const double x = ap[i], y = aq[i];
-          hpp = fma(x, x, hpp); hqq = fma(y, y, hqq); hpq = fma(x, y, hpq);
-        }
-        hpp = sum8(hpp); hqq = sum8(hqq); hpq = sum8(hpq);
-        if (fabs(hpq) > tol * sqrt(hpp * hqq)) {          // (false for NaN: a non-finite matrix never "moves" and is caught below)
-          const jac_cs cs = jac_rotation(hpp, hqq, hpq, 1.0 / fmax(fmax(hpp, hqq), fabs(hpq)));
-          for (int i = t8; i < m; i += 8) {
-            const double x = ap[i], y = aq[i];
-            ap[i] = cs.x * x - cs.y * y;
-            aq[i] = cs.y * x + cs.x * y;
-          }
-          double* vp = VV + p * BOOT_LDA;
-          double* vq = VV + q * BOOT_LDA;
-          for (int i = t8; i < r; i += 8) {
-            const double x = vp[i], y = vq[i];
-            vp[i] = cs.x * x - cs.y * y;
-            vq[i] = cs.y * x + cs.x * y;
-          }
-          if (t8 == 0) moved = 1;
-        }
-      }
-    }
-    __syncthreads();
-    settled = moved == 0;
-  }
-  __syncthreads();
-  for (int j = g8; j < r; j += 32) {
-    double s = 0.0;
-    for (int i = t8; i < m; i += 8) s = fma(TA[j * BOOT_LDA + i], TA[j * BOOT_LDA + i], s);
-    s = sum8(s);
-    if (t8 == 0) {
-      const bool fine = settled && s == s && s <= 1.7976931348623157e308;
-      nrm[j] = fine ? sqrt(s) : boot_nan();
-      if (!fine) bad[0] = 1;
-    }
-  }
+  // ---- one-sided Jacobi on the m x r matrix whose column j is TA + j * RS_LDA; V takes the same rotations
+  const bool settled = hestenes_sweeps<true>(TA, VV, RS_LDA, m, r, RS_SWEEPS, &moved);
+  column_norms(TA, RS_LDA, m, r, [&](int j, double s) {
+    const bool fine = settled && s == s && s <= 1.7976931348623157e308;
+    nrm[j] = fine ? sqrt(s) : rs_nan();
+    if (!fine) bad[0] = 1;
+  });
   __syncthreads();
   if (bad[0]) {
     boot_refuse(b, r, p1, p2, k, CCZ_BOOT_INFO_JACOBI, sv, W, info);
@@ -400,15 +289,13 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
   }
   // ---- rank descending; the left vectors are the normalised columns (norm 0: zeros)
   if (tid < r) {
-    const double v = nrm[tid];
-    int rank = 0;
-    for (int q = 0; q < r; ++q) rank += (nrm[q] > v || (nrm[q] == v && q < tid)) ? 1 : 0;
-    sv[b * r + rank] = v;
+    const int rank = rank_desc(nrm, r, tid);
+    sv[b * r + rank] = nrm[tid];
     inv[rank] = tid;
   }
-  for (int j = g8; j < r; j += 32) {
+  for (int j = tid >> 3, t8 = tid & 7; j < r; j += 32) {
     const double v = nrm[j];
-    for (int i = t8; i < m; i += 8) TA[j * BOOT_LDA + i] = v > 0.0 ? TA[j * BOOT_LDA + i] / v : 0.0;
+    for (int i = t8; i < m; i += 8) TA[j * RS_LDA + i] = v > 0.0 ? TA[j * RS_LDA + i] / v : 0.0;
   }
   __syncthreads();
   // ---- W_i = L_i^-T [top k columns], back substitution in place: 4 lanes per (view, column)
@@ -421,13 +308,13 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
       const bool wide = (view == 0) != tr;               // this view is the wider side: its vectors are the columns of TA
       const double* L = view ? B22 : B11;
       const int p = view ? p2 : p1;
-      double* z = (wide ? TA : VV) + col * BOOT_LDA;
+      double* z = (wide ? TA : VV) + col * RS_LDA;
       for (int i = m - 1; i >= 0; --i) {
         if (valid && i < p) {
           double d = 0.0;
-          for (int q = i + 1 + l; q < p; q += 4) d = fma(L[q * BOOT_LDA + i], z[q], d);
+          for (int q = i + 1 + l; q < p; q += 4) d = fma(L[q * RS_LDA + i], z[q], d);
           d = sum4(d);
-          if (l == 0) z[i] = (z[i] - d) / L[i * BOOT_LDA + i];
+          if (l == 0) z[i] = (z[i] - d) / L[i * RS_LDA + i];
         }
         __syncthreads();
       }
@@ -438,42 +325,35 @@ __global__ void __launch_bounds__(256) k_boot_solve(const double* __restrict__ p
     const int row = e / k, j = e - row * k;
     const int view = row >= p1 ? 1 : 0, i = view ? row - p1 : row;
     const bool wide = (view == 0) != tr;
-    W[b * nw + e] = ((wide ? TA : VV) + inv[j] * BOOT_LDA)[i];
+    W[b * nw + e] = ((wide ? TA : VV) + inv[j] * RS_LDA)[i];
   }
   if (tid == 0) info[b] = 0;
 }
 
 void boot_rcca_impl(ccz_ctx* c, int64_t n, int64_t p1, int64_t p2, const double* X1, const double* X2, const int32_t* counts,
                     int64_t nboot, double c1, double c2, int center, int64_t k, double* sv, double* W, int32_t* info) {
-  if (n < 1 || p1 < 1 || p2 < 1 || nboot < 1 || k < 1) fail(CCZ_EINVAL, "boot_rcca: n, p1, p2, nboot and k must be positive");
-  if (!X1 || !X2 || !sv || !W || !info) fail(CCZ_EINVAL, "boot_rcca: null pointer");
-  if (!counts && nboot != 1) fail(CCZ_EINVAL, "boot_rcca: all ones (counts_dev = NULL) is one resample, got nboot = %lld", (long long)nboot);
-  if (p1 > BOOT_MAXP || p2 > BOOT_MAXP) fail(CCZ_EUNSUP, "boot_rcca: views of at most %d columns, got %lld and %lld", BOOT_MAXP, (long long)p1, (long long)p2);
-  if (n >= (int64_t(1) << 31)) fail(CCZ_EUNSUP, "boot_rcca: fewer than 2^31 rows, got %lld", (long long)n);
+  check_two_views("boot_rcca", "n, p1, p2, nboot and k", k >= 1, X1 && X2 && sv && W && info, "all ones (counts_dev = NULL) is one resample",
+                  "nboot", counts != nullptr, nboot, n, p1, p2);
   const int r = int(std::min(p1, p2));
   if (k > r) fail(CCZ_EINVAL, "boot_rcca: k = %lld exceeds min(p1, p2) = %d", (long long)k, r);
-  const int P1 = 16 * (int(p1 + 15) / 16), P2 = 16 * (int(p2 + 15) / 16);
-  const int64_t nsplit = (n + BOOT_ROWS - 1) / BOOT_ROWS;
-  const int64_t per = nsplit * int64_t(boot_per(P1, P2));
-  const int64_t nb_max = std::max<int64_t>(1, std::min<int64_t>(BOOT_SCRATCH / per, BOOT_MAXBATCH));
+  const int PER = boot_per(16 * (int(p1 + 15) / 16), 16 * (int(p2 + 15) / 16));
+  const int64_t nsplit = (n + RS_ROWS - 1) / RS_ROWS;
   const int64_t nw = (p1 + p2) * k;
-  const int PER = boot_per(P1, P2);
-  DBuf part(c, std::min(nboot, nb_max) * per);
-  DBuf folded(c, nsplit > 1 ? std::min(nboot, nb_max) * PER : 0);
-  for (int64_t b0 = 0; b0 < nboot; b0 += nb_max) {
-    const int64_t nb = std::min(nb_max, nboot - b0);
+  DBuf folded;                                           // with more than one split: one folded partial per resample of a batch
+  for_batches(c, nboot, nsplit * PER, [&](double* part, int64_t b0, int64_t nb, int64_t cap) {
     hipLaunchKernelGGL(k_boot_moments, dim3(unsigned(nsplit), unsigned(nb), 3), dim3(256), 0, stream(c), X1, X2,
-                       counts ? counts + b0 * n : nullptr, n, int(p1), int(p2), part.get());
+                       counts ? counts + b0 * n : nullptr, n, int(p1), int(p2), part);
     CCZ_LAUNCH_CHECK();
     if (nsplit > 1) {
-      hipLaunchKernelGGL(k_boot_fold, dim3(unsigned((PER + 255) / 256), unsigned(nb)), dim3(256), 0, stream(c), part.get(), int(nsplit), PER,
+      if (!folded.get()) folded = DBuf(c, cap * PER);
+      hipLaunchKernelGGL(k_boot_fold, dim3(unsigned((PER + 255) / 256), unsigned(nb)), dim3(256), 0, stream(c), part, int(nsplit), PER,
                          folded.get());
       CCZ_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_boot_solve, dim3(unsigned(nb)), dim3(256), 0, stream(c), nsplit > 1 ? folded.get() : part.get(),
+    hipLaunchKernelGGL(k_boot_solve, dim3(unsigned(nb)), dim3(256), 0, stream(c), nsplit > 1 ? folded.get() : part,
                        nsplit > 1 ? 1 : int(nsplit), int(p1), int(p2), c1, c2, center, int(k), sv + b0 * r, W + b0 * nw, info + b0);
     CCZ_LAUNCH_CHECK();
-  }
+  });
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 // Device-side helpers shared by the Jacobi kernels (ops_hip.hip: the one-workgroup eigen-solvers of the Rayleigh-Ritz
-// steps; evd_block.hip: the blocked two-sided / one-sided Jacobi for d > 160).
+// steps; evd_block.hip: the blocked two-sided / one-sided Jacobi for d > 160; resample_dev.h: the one-sided Jacobi SVD of
+// permutation_test and bootstrap).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -18,8 +18,8 @@ Device side: the full-sample column means in a fixed order of summation (``ccz_a
 weight matrix for the shifted views ``X_i - 1 mu_i'`` (covariances do not change under a shift, and the shift removes the
 cancellation in ``G - s s' / n``), then ``ccz_boot_rcca`` (``csrc/boot.hip``): weighted moments on the fp64 matrix pipe and, per resample, one
 workgroup that factors, solves and runs a one-sided Jacobi SVD with vectors.  The host draws the indices with NumPy and counts
-them (``np.bincount``), one chunk ahead of the device, the arrangement of ``_permutation.py``.  Signs and summaries are the
-host's: a sign flip is exact.
+them (``np.bincount``), one chunk ahead of the device (``_resample.py``, shared with ``_permutation.py``).  Signs and
+summaries are the host's: a sign flip is exact.
 """
 
 from __future__ import annotations
@@ -32,18 +32,14 @@ from typing import Any
 import numpy as np
 
 from cca_zoo_amd import _backend
-from cca_zoo_amd._utils._resident import acquire, as_float, refuse_row_sharded, release
-from cca_zoo_amd._utils._validation import is_device_tensor, is_sparse_view, perview_parameter, validate_views
+from cca_zoo_amd._utils._resident import acquire, release
+from cca_zoo_amd.model_selection import _resample
+from cca_zoo_amd.model_selection._resample import MAX_ROWS, MAX_WIDTH, ROWS_PER_SPLIT  # noqa: F401  (the limits, for callers)
 
 #: resamples per upload and ``ccz_boot_rcca`` call (fewer when a chunk's counts would exceed ``CHUNK_COUNT_BYTES``); the
 #: result does not depend on it by a bit
 CHUNK_RESAMPLES = 64
 CHUNK_COUNT_BYTES = 64 << 20
-#: limits of the device path (``include/ccz.h``: CCZ_PERM_MAXP, CCZ_PERM_ROWS).  ``ROWS_PER_SPLIT`` rows of one resample go to
-#: one workgroup of the weighted moments: the row split is a function of ``n`` alone
-MAX_WIDTH = 64
-ROWS_PER_SPLIT = 4096
-MAX_ROWS = 2 ** 31
 #: ``info`` of ``ccz_boot_rcca`` (``include/ccz.h``: CCZ_BOOT_INFO_*)
 INFO_CAUSES = {
     1: "R_1 = (1 - c_1) C_11 + c_1 I has a non-positive or non-finite pivot: the resample's view 1 is rank deficient; use c > 0",
@@ -79,16 +75,12 @@ def draw_counts(rng, n, count):
 
 def count_chunks(rng, n, total, chunk):
     """The ``total`` resamples of :func:`draw_counts` in chunks of at most ``chunk``, drawn as they are asked for."""
-    done = 0
-    while done < total:
-        step = min(int(chunk), total - done)
-        yield draw_counts(rng, n, step)
-        done += step
+    return _resample.chunks(draw_counts, rng, n, total, chunk)
 
 
 def chunk_length(n):
     """Resamples per upload: ``CHUNK_RESAMPLES``, fewer when their counts would exceed ``CHUNK_COUNT_BYTES``."""
-    return max(1, min(int(CHUNK_RESAMPLES), CHUNK_COUNT_BYTES // (4 * n)))
+    return _resample.chunk_length(n, CHUNK_RESAMPLES, CHUNK_COUNT_BYTES)
 
 
 def orient_observed(W):
@@ -115,25 +107,13 @@ def summaries(boot, confidence_level):
     return np.std(boot, axis=0, ddof=1), np.quantile(boot, q, axis=0)
 
 
-def _is_half(v):
-    if type(v).__module__.startswith("torch"):
-        return bool(v.dtype.is_floating_point) and v.element_size() == 2
-    return getattr(getattr(v, "dtype", None), "itemsize", 0) == 2 and getattr(v.dtype, "kind", "") == "f"
-
-
 def check_limits(n, p, n_resamples, confidence_level):
     """``ValueError`` for what the device path excludes, before the device is touched."""
     if isinstance(n_resamples, bool) or not isinstance(n_resamples, Integral) or n_resamples < 2:
         raise ValueError(f"n_resamples must be an integer >= 2 (a standard error needs two), got {n_resamples!r}")
     if isinstance(confidence_level, bool) or not isinstance(confidence_level, Real) or not 0.0 < confidence_level < 1.0:
         raise ValueError(f"confidence_level must be a number in (0, 1), got {confidence_level!r}")
-    if max(p) > MAX_WIDTH:
-        raise ValueError(f"bootstrap: views of at most {MAX_WIDTH} columns are supported, got {list(p)}; reduce wider "
-                         "views first (e.g. to their leading principal components)")
-    if n >= MAX_ROWS:
-        raise ValueError(f"bootstrap: fewer than 2^31 rows are supported, got {n}")
-    if n - 1 <= 0:
-        raise ValueError("at least 2 samples are required")
+    _resample.check_shape("bootstrap", n, p)
 
 
 def _shifted(h, xptr, n, d, center):
@@ -202,45 +182,15 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
     covariance cannot be factored (with ``c = 0``: fewer distinct rows than columns) raises ``np.linalg.LinAlgError`` that
     names the resample and the remedy ``c > 0``.
     """
-    from sklearn.base import clone
-
-    from cca_zoo_amd.linear import rCCA
-
-    if not isinstance(estimator, rCCA):
-        raise TypeError(f"bootstrap takes a CCA, rCCA or PLS estimator, got {type(estimator).__name__}")
-    refuse_row_sharded("bootstrap refits on all rows of one device, which this build does not shard by rows")
-    if not isinstance(views, (list, tuple)):
-        raise TypeError("views must be a list of two arrays or CUDA tensors")
-    for v in views:
-        if is_sparse_view(v):
-            raise TypeError("bootstrap: sparse views are not supported; pass dense arrays")
-        if _is_half(v):
-            raise TypeError("bootstrap: half-precision views are not supported; pass float32 or float64")
-    est = clone(estimator)
-    est._validate_params()
-    views_ = [as_float(v) for v in validate_views(list(views), check_finite=False)]
-    if len(views_) != 2:
-        raise ValueError(f"bootstrap requires exactly 2 views, got {len(views_)}")
-    n, p = int(views_[0].shape[0]), [int(v.shape[1]) for v in views_]
-    check_limits(n, p, n_resamples, confidence_level)
-    dev = [is_device_tensor(v) for v in views_]
-    if any(dev) and not all(dev):
-        raise ValueError("views must be all host arrays or all CUDA tensors")
-    c_ = [float(v) for v in perview_parameter("c", est.c, 0.0, 2)]
-    center, B, r = bool(est.center), int(n_resamples), min(p)
+    est, views_, n, p, c_, center, on_device = _resample.prepare(
+        "bootstrap", "refits on all rows of one device", estimator, views,
+        lambda n, p: check_limits(n, p, n_resamples, confidence_level))
+    B, r = int(n_resamples), min(p)
     k, pt = min(int(est.latent_dimensions), r), p[0] + p[1]
     rng = np.random.default_rng(random_state)
 
     h = _backend.handle_for(views_)
-    # float64 copies for K1 and the shift, made before the handle's stream takes over (CUDA: on the caller's stream)
-    if all(dev):
-        import torch
-
-        x64 = [v.to(torch.float64).contiguous() for v in views_]
-        xptr = [int(x.data_ptr()) for x in x64]
-    else:
-        x64 = [h.to_device(np.ascontiguousarray(v, dtype=np.float64)) for v in views_]
-        xptr = [int(b.ptr) for b in x64]
+    x64, xptr = _resample.stage_f64(h, views_, on_device)  # for the column means and the shift
     sp = acquire(h, views_)
     try:
         Z = [_shifted(h, xptr[i], n, p[i], center) for i in range(2)]
@@ -248,15 +198,10 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
         sv, W, info = h.alloc((B + 1) * r * 8), h.alloc((B + 1) * pt * k * 8), h.alloc((B + 1) * 4)
         boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], None, 1, c_[0], c_[1], center, k, sv.ptr, W.ptr, info.ptr)
         chunk = chunk_length(n)
-        slots = [h.alloc(min(chunk, B) * n * 4) for _ in range(2)]
-        done = 0
-        # the next chunk is drawn while the device works on this one; the upload is ordered behind it on the handle's stream
-        for i, counts in enumerate(count_chunks(rng, n, B, chunk)):
-            slot = slots[i & 1]
-            h.h2d(slot.ptr, counts)
-            boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], slot.ptr, counts.shape[0], c_[0], c_[1], center, k,
-                      sv.ptr + (1 + done) * r * 8, W.ptr + (1 + done) * pt * k * 8, info.ptr + (1 + done) * 4)
-            done += counts.shape[0]
+        slots = _resample.run_chunks(
+            h, count_chunks(rng, n, B, chunk), min(chunk, B) * n * 4,
+            lambda ptr, count, done: boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], ptr, count, c_[0], c_[1], center, k, sv.ptr + (1 + done) * r * 8,
+                                               W.ptr + (1 + done) * pt * k * 8, info.ptr + (1 + done) * 4))
         sv_h, W_h = h.to_host(sv, (B + 1, r)), h.to_host(W, (B + 1, pt, k))
         info_h = h.to_host(info, (B + 1,), dtype=np.int32)
     finally:

@@ -11,8 +11,8 @@ covariances for ``PLS``.  ``tests/perm_restatement.py`` is the float64 NumPy for
 
 Device side: one float64 K1 pass per view (``ccz_moments``), ``ccz_cholinv`` for both ``L_i^-1``, ``ccz_transform`` in float64 for
 ``Z_i``, then ``ccz_perm_singular_values`` (``csrc/perm.hip``): a gathered cross-moment product on the fp64 matrix pipe and a
-one-sided Jacobi SVD, many permutations per launch.  The host draws the permutations with NumPy, one chunk ahead of the device,
-the arrangement of the EY models' mini-batch indices (``linear/gradient/_base.py``).
+one-sided Jacobi SVD, many permutations per launch.  The host draws the permutations with NumPy, one chunk ahead of the device
+(``_resample.py``, shared with :func:`~cca_zoo_amd.model_selection.bootstrap`).
 """
 
 from __future__ import annotations
@@ -25,18 +25,14 @@ from typing import Any
 import numpy as np
 
 from cca_zoo_amd import _backend
-from cca_zoo_amd._utils._resident import acquire, as_float, is_f32, refuse_row_sharded, release
-from cca_zoo_amd._utils._validation import is_device_tensor, is_sparse_view, perview_parameter, validate_views
+from cca_zoo_amd._utils._resident import acquire, release
+from cca_zoo_amd.model_selection import _resample
+from cca_zoo_amd.model_selection._resample import MAX_ROWS, MAX_WIDTH, ROWS_PER_SPLIT  # noqa: F401  (the limits, for callers)
 
 #: permutations per upload and ``ccz_perm_singular_values`` call (fewer when a chunk's indices would exceed
 #: ``CHUNK_INDEX_BYTES``); the result does not depend on it by a bit
 CHUNK_PERMS = 64
 CHUNK_INDEX_BYTES = 64 << 20
-#: limits of the device path (``include/ccz.h``: CCZ_PERM_MAXP, CCZ_PERM_ROWS).  ``ROWS_PER_SPLIT`` rows of one permutation go
-#: to one workgroup of the gathered product: the row split is a function of ``n`` alone
-MAX_WIDTH = 64
-ROWS_PER_SPLIT = 4096
-MAX_ROWS = 2 ** 31
 
 
 @dataclass
@@ -62,16 +58,12 @@ def draw_permutations(rng, n, count):
 
 def permutation_chunks(rng, n, total, chunk):
     """The ``total`` permutations of :func:`draw_permutations` in chunks of at most ``chunk``, drawn as they are asked for."""
-    done = 0
-    while done < total:
-        step = min(int(chunk), total - done)
-        yield draw_permutations(rng, n, step)
-        done += step
+    return _resample.chunks(draw_permutations, rng, n, total, chunk)
 
 
 def chunk_length(n):
     """Permutations per upload: ``CHUNK_PERMS``, fewer when their indices would exceed ``CHUNK_INDEX_BYTES``."""
-    return max(1, min(int(CHUNK_PERMS), CHUNK_INDEX_BYTES // (4 * n)))
+    return _resample.chunk_length(n, CHUNK_PERMS, CHUNK_INDEX_BYTES)
 
 
 def tails(sv):
@@ -86,23 +78,11 @@ def count_pvalues(statistic, null):
     return (1.0 + np.sum(null >= np.asarray(statistic)[None, :], axis=0)) / (null.shape[0] + 1.0)
 
 
-def _is_half(v):
-    if type(v).__module__.startswith("torch"):
-        return bool(v.dtype.is_floating_point) and v.element_size() == 2
-    return getattr(getattr(v, "dtype", None), "itemsize", 0) == 2 and getattr(v.dtype, "kind", "") == "f"
-
-
 def check_limits(n, p, n_permutations):
     """``ValueError`` for what the device path excludes, before the device is touched."""
     if isinstance(n_permutations, bool) or not isinstance(n_permutations, Integral) or n_permutations < 1:
         raise ValueError(f"n_permutations must be an integer >= 1, got {n_permutations!r}")
-    if max(p) > MAX_WIDTH:
-        raise ValueError(f"permutation_test: views of at most {MAX_WIDTH} columns are supported, got {list(p)}; reduce wider "
-                         "views first (e.g. to their leading principal components), as is customary for permutation inference")
-    if n >= MAX_ROWS:
-        raise ValueError(f"permutation_test: fewer than 2^31 rows are supported, got {n}")
-    if n - 1 <= 0:
-        raise ValueError("at least 2 samples are required")
+    _resample.check_shape("permutation_test", n, p, ", as is customary for permutation inference")
 
 
 def _whiten(h, xptr, n, d, c, center):
@@ -165,44 +145,13 @@ def permutation_test(estimator, views, n_permutations=1000, random_state=None):
     distribution.  It is NOT a stepwise (deflating) test: the null of component ``j`` still contains the signal of the
     components before it.  ``tail_pvalues[0]`` (all squared singular values summed) is the omnibus test.
     """
-    from sklearn.base import clone
-
-    from cca_zoo_amd.linear import rCCA
-
-    if not isinstance(estimator, rCCA):
-        raise TypeError(f"permutation_test takes a CCA, rCCA or PLS estimator, got {type(estimator).__name__}")
-    refuse_row_sharded("permutation_test whitens all rows on one device, which this build does not shard by rows")
-    if not isinstance(views, (list, tuple)):
-        raise TypeError("views must be a list of two arrays or CUDA tensors")
-    for v in views:
-        if is_sparse_view(v):
-            raise TypeError("permutation_test: sparse views are not supported; pass dense arrays")
-        if _is_half(v):
-            raise TypeError("permutation_test: half-precision views are not supported; pass float32 or float64")
-    est = clone(estimator)
-    est._validate_params()
-    views_ = [as_float(v) for v in validate_views(list(views), check_finite=False)]
-    if len(views_) != 2:
-        raise ValueError(f"permutation_test requires exactly 2 views, got {len(views_)}")
-    n, p = int(views_[0].shape[0]), [int(v.shape[1]) for v in views_]
-    check_limits(n, p, n_permutations)
-    dev = [is_device_tensor(v) for v in views_]
-    if any(dev) and not all(dev):
-        raise ValueError("views must be all host arrays or all CUDA tensors")
-    c_ = [float(v) for v in perview_parameter("c", est.c, 0.0, 2)]
-    center, B, r = bool(est.center), int(n_permutations), min(p)
+    est, views_, n, p, c_, center, on_device = _resample.prepare(
+        "permutation_test", "whitens all rows on one device", estimator, views, lambda n, p: check_limits(n, p, n_permutations))
+    B, r = int(n_permutations), min(p)
     rng = np.random.default_rng(random_state)
 
     h = _backend.handle_for(views_)
-    # float64 copies for K1 and the whitening, made before the handle's stream takes over (CUDA: on the caller's stream)
-    if all(dev):
-        import torch
-
-        x64 = [v.to(torch.float64).contiguous() for v in views_]
-        xptr = [int(x.data_ptr()) for x in x64]
-    else:
-        x64 = [h.to_device(np.ascontiguousarray(v, dtype=np.float64)) for v in views_]
-        xptr = [int(b.ptr) for b in x64]
+    x64, xptr = _resample.stage_f64(h, views_, on_device)  # for K1 and the whitening
     sp = acquire(h, views_)
     try:
         Z, keep = [], []
@@ -212,14 +161,9 @@ def permutation_test(estimator, views, n_permutations=1000, random_state=None):
         sv = h.alloc((B + 1) * r * 8)
         singular_values(h, n, p[0], p[1], Z[0].ptr, Z[1].ptr, None, 1, sv.ptr)
         chunk = chunk_length(n)
-        slots = [h.alloc(min(chunk, B) * n * 4) for _ in range(2)]
-        done = 0
-        # the next chunk is drawn while the device works on this one; the upload is ordered behind it on the handle's stream
-        for i, idx in enumerate(permutation_chunks(rng, n, B, chunk)):
-            slot = slots[i & 1]
-            h.h2d(slot.ptr, idx)
-            singular_values(h, n, p[0], p[1], Z[0].ptr, Z[1].ptr, slot.ptr, idx.shape[0], sv.ptr + (1 + done) * r * 8)
-            done += idx.shape[0]
+        slots = _resample.run_chunks(h, permutation_chunks(rng, n, B, chunk), min(chunk, B) * n * 4,
+                                     lambda ptr, count, done: singular_values(h, n, p[0], p[1], Z[0].ptr, Z[1].ptr, ptr, count,
+                                                                              sv.ptr + (1 + done) * r * 8))
         out = h.to_host(sv, (B + 1, r))
     finally:
         release(h, sp)

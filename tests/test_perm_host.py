@@ -200,7 +200,7 @@ def test_row_sharded_is_refused(monkeypatch, no_device):
 
 def test_limits_raise_value_errors(monkeypatch, no_device):
     from cca_zoo_amd.linear import CCA, rCCA
-    from cca_zoo_amd.model_selection import _permutation as pm
+    from cca_zoo_amd.model_selection import _resample
     from cca_zoo_amd.model_selection import permutation_test
 
     X = [np.zeros((20, 3)), np.zeros((20, 4))]
@@ -234,7 +234,7 @@ def test_limits_raise_value_errors(monkeypatch, no_device):
         def __init__(self, d):
             self.shape = (2 ** 31, d)
 
-    monkeypatch.setattr(pm, "validate_views", lambda views, **kw: list(views))
+    monkeypatch.setattr(_resample, "validate_views", lambda views, **kw: list(views))
     with pytest.raises(ValueError, match="2\\^31"):
         permutation_test(CCA(), [Tall(3), Tall(4)])
 
