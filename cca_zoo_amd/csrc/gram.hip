@@ -923,6 +923,66 @@ __global__ void k_pilot_on_grid(const double* __restrict__ s, const double* __re
   pilot[j] = float(p);
 }
 
+// Which columns of a FLOAT32 row sample lie on a coarse grid: per column, over the sampled rows, the exponent of the LOWEST set bit any
+// nonzero value has (the finest power of two all of them are multiples of) and the MOST significant bits any value has (8: the
+// column was up-cast from bfloat16).  Kept as maxima for one zero-filled buffer: code[j] = max(200 - exponent) (0: no nonzero value
+// seen, 1000: a non-finite one), bits[j] = max(significant bits).  Integer atomics: the result does not depend on their order.
+__global__ __launch_bounds__(256) void k_sample_grid(const float* __restrict__ X, int64_t n, int64_t cols, int64_t ld, int* __restrict__ code,
+                                                     int* __restrict__ bits, int64_t rows_per_block) {
+  const int64_t col = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (col >= cols) return;
+  const int64_t r0 = int64_t(blockIdx.y) * rows_per_block;
+  const int64_t r1 = min(n, r0 + rows_per_block);
+  int cmax = 0, bmax = 0;
+  for (int64_t r = r0; r < r1; ++r) {
+    const unsigned b = __builtin_bit_cast(unsigned, X[r * ld + col]) & 0x7fffffffu;
+    if (b == 0u) continue;
+    int e = int(b >> 23);
+    unsigned m = b & 0x7fffffu;
+    if (e == 255) { cmax = 1000; continue; }
+    if (e) m |= 0x800000u; else e = 1;
+    const int tz = __builtin_ctz(m);
+    cmax = max(cmax, 200 - (e - 150 + tz));
+    bmax = max(bmax, 32 - __builtin_clz(m) - tz);
+  }
+  if (cmax) atomicMax(code + col, cmax);
+  if (bmax) atomicMax(bits + col, bmax);
+}
+
+// The pilot of FLOAT32 rows on the split route.  float32 views often lie on a coarse grid (0/1 features, one-hot blocks, pixel
+// values, counts, integer measurements, values up-cast from bfloat16): with the plain mean as the pilot, mid is nearly the same number
+// on every row that holds the same value, sum_k mid_ik mid_jk adds up coherently and the error stops falling with the row count (0/1
+// columns: 3e-6 in tests/test_gpu_k1_split.py's measure at 4099, 5000 and 33000 rows alike, where the fp32 kernel is exact).  For
+// such a column the pilot is the candidate near the sample mean with the FEWEST significant bits -- the mean rounded to a multiple of
+// u = 2^(ilogb(sd) - 3), sd the sample's standard deviation, so |p - mean| <= sd / 8 and the centring is as good as the mean's.
+// x - p then keeps the rows' grid: hi holds such columns exactly, mid = 0, and their moments are exact (tests/split_emulation.py
+// states the rule on the host, tests/test_gpu_k1_split_structured.py holds the device to it bit for bit).  The unit follows the
+// SPREAD, not the magnitude as k_pilot_on_grid's does: a unit at the rms scale would move the pilot of a column whose mean is 1000
+// sigma by up to hundreds of sigma.
+// "Such a column" (k_sample_grid): every sampled value is a multiple of u / 8 (with |x - p| < 32 u that is 8 bits: hi alone), or has at
+// most 8 significant bits.  Every OTHER column -- generic float32 values, ReLU outputs -- keeps pilot = fl32(s / nsamp), the sample
+// mean as before: a coarse pilot would gain nothing for Gaussian columns, but it would be another rounding of every product, and the
+// moments (and every weight computed from them) of inputs that were served well would no longer be the bits they were.
+// sd == 0 or anything non-finite: the mean as well.
+__global__ void k_pilot_coarse(const double* __restrict__ s, const double* __restrict__ sq, const int* __restrict__ code, const int* __restrict__ bits,
+                               int64_t D, double nsamp, double inv_n, float* __restrict__ pilot) {
+#pragma clang fp contract(off)                   // (mean^2 and the subtraction round separately, as the host statement of the rule does)
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= D) return;
+  double p = s[j] * inv_n;                       // k_pilot_from_sums' value
+  const double mean = s[j] / nsamp, var = sq[j] / nsamp - mean * mean;
+  const int cj = code[j];
+  if (cj > 0 && cj < 1000 && isfinite(mean) && isfinite(var) && var > 0.0) {
+    const int eu = ilogb(sqrt(var)) - 3;         // u = 2^eu
+    if (200 - cj >= eu - 3 || bits[j] <= 8) {
+      const double u = ldexp(1.0, eu);
+      const double r = rint(mean / u) * u;
+      if (isfinite(r)) p = r;
+    }
+  }
+  pilot[j] = float(p);
+}
+
 // Undo the pilot shift on the d x d side, in fp64, and fold the launch's column sums into the running ones:
 //   sum x_i x_j = sum (x_i - p_i)(x_j - p_j) + p_i s_j + p_j s_i - n p_i p_j      (s = column sums of these rows)
 // Only elements on or above the diagonal are authoritative (every consumer reads G through its upper triangle).
@@ -1318,25 +1378,43 @@ bool launch_moments(ccz_ctx* c, const ccz_view* views, int n_views, int64_t n, d
   if (split) {
     // Split route: the exact column sums ride in the split pass (one read of the rows instead of two), so the pilot cannot be
     // their mean -- it is the mean of a strided sample of <= 2048 rows spread over the whole launch (sorted / drifting inputs
-    // included).  Any pilot near the mean serves: the fix-up  sum x x' = sum (x-p)(x-p)' + p s' + s p' - n p p'  is exact in p.
+    // included).  Any pilot near the mean serves: the fix-up  sum x x' = sum (x-p)(x-p)' + p s' + s p' - n p p'  is exact in p -- so
+    // it is a COARSE one: on the rows' own grid for half rows (k_pilot_on_grid), of few bits at the scale of the spread for float32
+    // rows (k_pilot_coarse); both take the sample's sums of squares too.
     const int64_t nsamp = std::min<int64_t>(n, 2048), stride = n / nsamp;
-    PoolBuf<double> samp(c, is16 ? 2 * D : D);                 // half rows: the sample's sums of squares too (k_pilot_on_grid)
-    zero(c, samp, size_t(is16 ? 2 * D : D) * 8);
+    PoolBuf<double> samp(c, 2 * D);
+    zero(c, samp, size_t(2 * D) * 8);
     for (int v = 0; v < n_views; ++v) {
       const int64_t colblocks = (views[v].cols + 255) / 256;
       int64_t rpb = 256;
       while (rpb > 16 && colblocks * ((nsamp + rpb - 1) / rpb) < 2 * int64_t(ncu)) rpb /= 2;
       dim3 grid((unsigned)colblocks, (unsigned)((nsamp + rpb - 1) / rpb));
-      hipLaunchKernelGGL((k_colsum<T, is16>), grid, dim3(256), 0, st, static_cast<const T*>(views[v].data), nsamp, views[v].cols,
-                         views[v].ld * stride, samp.get() + off, is16 ? samp.get() + D + off : static_cast<double*>(nullptr), rpb);
+      hipLaunchKernelGGL((k_colsum<T, true>), grid, dim3(256), 0, st, static_cast<const T*>(views[v].data), nsamp, views[v].cols,
+                         views[v].ld * stride, samp.get() + off, samp.get() + D + off, rpb);
       off += views[v].cols;
     }
     pilot = pilot_own = PoolBuf<float>(c, D);
+    PoolBuf<int> grid;                                          // float32 rows: which columns lie on a coarse grid (k_sample_grid)
+    if constexpr (std::is_same<T, float>::value) {
+      grid = PoolBuf<int>(c, 2 * D);
+      zero(c, grid, size_t(2 * D) * sizeof(int));
+      off = 0;
+      for (int v = 0; v < n_views; ++v) {
+        const int64_t colblocks = (views[v].cols + 255) / 256;
+        int64_t rpb = 256;
+        while (rpb > 16 && colblocks * ((nsamp + rpb - 1) / rpb) < 2 * int64_t(ncu)) rpb /= 2;
+        hipLaunchKernelGGL(k_sample_grid, dim3((unsigned)colblocks, (unsigned)((nsamp + rpb - 1) / rpb)), dim3(256), 0, st,
+                           static_cast<const float*>(views[v].data), nsamp, views[v].cols, views[v].ld * stride, grid.get() + off,
+                           grid.get() + D + off, rpb);
+        off += views[v].cols;
+      }
+    }
     if (is16)
       hipLaunchKernelGGL(k_pilot_on_grid, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), samp.get() + D, D, 1.0 / double(nsamp),
                          std::is_same<T, bf16_t>::value ? 7 : 10, pilot);
     else
-      hipLaunchKernelGGL(k_pilot_from_sums, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), D, 1.0 / double(nsamp), pilot);
+      hipLaunchKernelGGL(k_pilot_coarse, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, samp.get(), samp.get() + D, grid.get(), grid.get() + D, D,
+                         double(nsamp), 1.0 / double(nsamp), pilot);
     samp.reset();
   }
   for (int v = 0; v < n_views && !split; ++v) {

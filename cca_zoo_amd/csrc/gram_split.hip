@@ -1,7 +1,11 @@
 // K1 on the bf16 matrix pipe: fp32 second moments from TWO bf16 planes ("bf16 split-accumulate ... only if
 // it holds the 1e-3 bar").
 //
-//   d = fl32(x - p)            p: the launch's pilot (fp32 column mean), subtracted once, undone in fp64 (k_pilot_fixup)
+//   d = fl32(x - p)            p: the launch's pilot, subtracted once, undone in fp64 (k_pilot_fixup).  Near the column mean and COARSE:
+//                              for float32 columns that lie on a grid the mean of a row sample rounded to 2^(ilogb(sd) - 3)
+//                              (gram.hip k_sample_grid, k_pilot_coarse; every other float32 column: the sample mean), for half
+//                              rows a point of their own grid (k_pilot_on_grid) -- x - p then keeps the grid of grid-valued
+//                              columns (0/1, one-hot, pixels, counts, integers), hi holds it exactly and mid = 0
 //   d = hi + mid + lo          hi = bf16(d), mid = bf16(d - hi)  (d - hi is exact in fp32), |mid| <= 2^-8 |d|, |lo| <= 2^-16 |d|
 //   d_i d_j = hi_i hi_j + hi_i mid_j + mid_i hi_j  [+ mid_i mid_j + hi_i lo_j + lo_i hi_j + ...]
 //
@@ -11,6 +15,13 @@
 // from sum_k mid_ik^2, which the split pass accumulates on the side.  The rest are zero-mean at 2^-16 per product and
 // average out over the rows like the fp32 kernel's own accumulation error (measured in bench.py: k1_rel_err of both routes).
 // Accumulation is unchanged from the fp32 kernel: fp32 inside a row chunk (<= 16384 rows), fp64 across chunks.
+// A DELIBERATE DIFFERENCE from float64 moments: sum mid^2 is added where i == j in G only (k_split_reduce).  Two IDENTICAL columns
+// at different positions -- a view passed twice, columns shared between views -- give an off-diagonal entry whose dropped
+// sum_k mid_ki mid_kj is the same sum of squares, and that entry lacks it: about 3e-6 of the entry, flat in the row count (rCCA on
+// [X, X]: canonical correlations of 1 - 2.5e-6).  Heavy-tailed rows (Student-t, one row at 1e4 sigma) and an input whose period
+// matches the pilot sample's stride keep errors of that order too.  tests/split_emulation.py restates this arithmetic on the host;
+// tests/test_gpu_k1_split_structured.py holds the kernels to it: bit for bit on grid-valued inputs, within the float32 accumulation
+// allowance elsewhere, these pinned effects included.
 //
 // Data layout.  The MFMA operand of v_mfma_f32_32x32x16_bf16 is 8 consecutive k (= ROWS of a view) of one column per lane,
 // which row-major views cannot deliver coalesced -- so the split pass also transposes, into the exact LDS image the Gram

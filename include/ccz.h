@@ -213,7 +213,13 @@ CCZ_API int ccz_moments_last_pilot(ccz_handle h, int* used);
  *   CCZ_K1_BF16X2  x - pilot = hi + mid (two bf16 planes, written by one transposing pass over the rows), the
  *                  products hi'hi + hi'mid + mid'hi as three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator,
  *                  diag(sum mid^2) added back exactly -- 3 bf16 MFMAs for each fp32 one at 16x the rate; agreement
- *                  with float64 moments is measured beside the fp32 route's in bench.py (k1_rel_err);
+ *                  with float64 moments is measured beside the fp32 route's in bench.py (k1_rel_err).  The pilot of a float32
+ *                  column is the mean of a row sample; where the sampled values lie on a grid (0/1, one-hot, pixel values,
+ *                  counts, integers, values up-cast from bfloat16) that mean rounded to few bits (2^(ilogb(sd) - 3)), so
+ *                  that such columns keep their grid and their moments are exact.  Deliberately NOT
+ *                  float64's result: an off-diagonal entry of two identical columns (a view passed twice, columns shared
+ *                  between views) lacks sum mid^2, about 3e-6 of the entry whatever the row count -- rCCA on [X, X] reports
+ *                  canonical correlations of 1 - 2.5e-6 (tests/test_gpu_k1_split_structured.py pins it);
  *   CCZ_K1_AUTO    (default) CCZ_K1_BF16X2 where it pays AND is at least as accurate as the fp32 kernel (n >= 32768 rows,
  *                  n D (D+1) >= 1e11, D >= 256), else CCZ_K1_FP32.
  * The environment variable CCZ_K1_ROUTE = fp32 | bf16x2 overrides AUTO.  route = -1 only queries; *previous (may be
