@@ -18,8 +18,9 @@ Device side: the full-sample column means in a fixed order of summation (``ccz_a
 weight matrix for the shifted views ``X_i - 1 mu_i'`` (covariances do not change under a shift, and the shift removes the
 cancellation in ``G - s s' / n``), then ``ccz_boot_rcca`` (``csrc/boot.hip``): weighted moments on the fp64 matrix pipe and, per resample, one
 workgroup that factors, solves and runs a one-sided Jacobi SVD with vectors.  The host draws the indices with NumPy and counts
-them (``np.bincount``), one chunk ahead of the device (``_resample.py``, shared with ``_permutation.py``).  Signs and
-summaries are the host's: a sign flip is exact.
+them (``np.bincount``), one chunk ahead of the device (``_resample.py``, shared with ``_permutation.py``); with
+``draws="device"`` the multiplicities are drawn on the device instead (``ccz_draw_counts``, ``csrc/draw.hip``), straight into the
+slot the moments read.  Signs and summaries are the host's: a sign flip is exact.
 """
 
 from __future__ import annotations
@@ -152,7 +153,7 @@ def raise_for_info(info):
         raise np.linalg.LinAlgError(f"bootstrap: {which}: {INFO_CAUSES.get(code, f'info = {code}')}")
 
 
-def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_state=None):
+def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_state=None, *, draws="numpy"):
     r"""Non-parametric bootstrap of the weights and singular values of a two-view CCA, rCCA or PLS.
 
     The rows are drawn with replacement ``n_resamples`` times (n out of n); every resample is refitted on the device from
@@ -169,6 +170,12 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
         n_resamples: ``B >= 2``.
         confidence_level: level of the percentile intervals, in (0, 1).
         random_state: seed of ``np.random.default_rng``; resample ``b`` is the ``b``-th ``rng.integers(0, n, size=n)``.
+        draws: ``"numpy"`` (default): the resamples are drawn and counted on the host as above and uploaded.  ``"device"``:
+            they are drawn on the device and no count array is built or uploaded by the host -- draw ``j`` of resample ``b`` picks
+            row ``(splitmix64(stream(seed, b) ^ splitmix64(j)) * n) >> 64`` (``include/ccz.h``: ``ccz_draw_counts``) with
+            ``seed = np.random.default_rng(random_state).integers(0, 2**64, dtype=np.uint64)``.  The two settings give
+            different, equally valid random resamples: the observed values are the same bits, standard errors and intervals
+            differ by Monte Carlo error only.  Either setting is reproducible from ``random_state``.
 
     Returns:
         :class:`BootstrapResult`.  ``se = std(axis=0, ddof=1)``, ``ci = quantile(boot, [(1 - cl) / 2, (1 + cl) / 2], axis=0)``,
@@ -177,17 +184,16 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
         the observed column is >= 0 (the two views of a column always flip together).
 
     Limits of this first cut (``ValueError`` before the device is touched): ``max(p1, p2) <= 64`` -- wider views are reduced
-    first (e.g. to their leading principal components); ``n < 2^31``; ``n >= 2``.  Sparse views and half-precision views raise
+    first (e.g. to their leading principal components); ``n < 2^31``; ``n >= 2``; ``draws`` is one of the two names.  Sparse views and half-precision views raise
     ``TypeError``; a call inside :func:`cca_zoo_amd.row_sharded` raises ``NotImplementedError``.  A resample whose regularised
     covariance cannot be factored (with ``c = 0``: fewer distinct rows than columns) raises ``np.linalg.LinAlgError`` that
     names the resample and the remedy ``c > 0``.
     """
     est, views_, n, p, c_, center, on_device = _resample.prepare(
         "bootstrap", "refits on all rows of one device", estimator, views,
-        lambda n, p: check_limits(n, p, n_resamples, confidence_level))
+        lambda n, p: check_limits(n, p, n_resamples, confidence_level), draws)
     B, r = int(n_resamples), min(p)
     k, pt = min(int(est.latent_dimensions), r), p[0] + p[1]
-    rng = np.random.default_rng(random_state)
 
     h = _backend.handle_for(views_)
     x64, xptr = _resample.stage_f64(h, views_, on_device)  # for the column means and the shift
@@ -198,8 +204,12 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
         sv, W, info = h.alloc((B + 1) * r * 8), h.alloc((B + 1) * pt * k * 8), h.alloc((B + 1) * 4)
         boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], None, 1, c_[0], c_[1], center, k, sv.ptr, W.ptr, info.ptr)
         chunk = chunk_length(n)
+        if draws == "device":
+            source = _resample.device_chunks(h, "counts", n, _resample.device_seed(random_state), B, chunk)
+        else:
+            source = count_chunks(np.random.default_rng(random_state), n, B, chunk)
         slots = _resample.run_chunks(
-            h, count_chunks(rng, n, B, chunk), min(chunk, B) * n * 4,
+            h, source, min(chunk, B) * n * 4,
             lambda ptr, count, done: boot_rcca(h, n, p[0], p[1], zptr[0], zptr[1], ptr, count, c_[0], c_[1], center, k, sv.ptr + (1 + done) * r * 8,
                                                W.ptr + (1 + done) * pt * k * 8, info.ptr + (1 + done) * 4))
         sv_h, W_h = h.to_host(sv, (B + 1, r)), h.to_host(W, (B + 1, pt, k))

@@ -12,7 +12,9 @@ covariances for ``PLS``.  ``tests/perm_restatement.py`` is the float64 NumPy for
 Device side: one float64 K1 pass per view (``ccz_moments``), ``ccz_cholinv`` for both ``L_i^-1``, ``ccz_transform`` in float64 for
 ``Z_i``, then ``ccz_perm_singular_values`` (``csrc/perm.hip``): a gathered cross-moment product on the fp64 matrix pipe and a
 one-sided Jacobi SVD, many permutations per launch.  The host draws the permutations with NumPy, one chunk ahead of the device
-(``_resample.py``, shared with :func:`~cca_zoo_amd.model_selection.bootstrap`).
+(``_resample.py``, shared with :func:`~cca_zoo_amd.model_selection.bootstrap`); with ``draws="device"`` they are drawn on the
+device instead (``ccz_draw_permutations``, ``csrc/draw.hip``: the argsort of hashed 64-bit keys), straight into the slot the
+product reads.
 """
 
 from __future__ import annotations
@@ -116,7 +118,7 @@ def singular_values(h, n, p1, p2, z1_ptr, z2_ptr, perms_ptr, nperm, sv_ptr):
                                            vp(int(perms_ptr)) if perms_ptr else None, int(nperm), 1.0 / (n - 1), vp(int(sv_ptr))))
 
 
-def permutation_test(estimator, views, n_permutations=1000, random_state=None):
+def permutation_test(estimator, views, n_permutations=1000, random_state=None, *, draws="numpy"):
     r"""Row-permutation test of the canonical correlations of two views.
 
     The rows of view 2 are shuffled ``n_permutations`` times; every shuffle gives all ``r = min(p1, p2)`` singular values
@@ -132,13 +134,19 @@ def permutation_test(estimator, views, n_permutations=1000, random_state=None):
             are widened to float64 once; every product after that is float64.
         n_permutations: ``B >= 1``.
         random_state: seed of ``np.random.default_rng``; permutation ``b`` is the ``b``-th ``rng.permutation(n)``.
+        draws: ``"numpy"`` (default): the permutations are drawn on the host as above and uploaded.  ``"device"``: they are
+            drawn on the device and no index array is built or uploaded by the host -- permutation ``b`` is the argsort of the
+            ``n`` keys ``splitmix64(stream(seed, b) ^ splitmix64(j))`` (``include/ccz.h``: ``ccz_draw_permutations``) with
+            ``seed = np.random.default_rng(random_state).integers(0, 2**64, dtype=np.uint64)``.  The two settings give
+            different, equally valid random permutations: ``statistic`` is the same bits, ``null`` and the p-values differ by
+            Monte Carlo error only.  Either setting is reproducible from ``random_state``.
 
     Returns:
         :class:`PermutationTestResult`.
 
     Limits of this first cut (``ValueError`` before the device is touched): ``max(p1, p2) <= 64`` -- wider views are
     reduced first (e.g. to their leading principal components), as is customary for permutation inference; ``n < 2^31``;
-    ``n >= 2``.  Sparse views and half-precision views raise ``TypeError``; a call inside
+    ``n >= 2``; ``draws`` is one of the two names.  Sparse views and half-precision views raise ``TypeError``; a call inside
     :func:`cca_zoo_amd.row_sharded` raises ``NotImplementedError``.
 
     ``pvalues[j]`` for ``j > 0`` is the plain comparison of the ``j``-th order statistic with its permutation
@@ -146,9 +154,9 @@ def permutation_test(estimator, views, n_permutations=1000, random_state=None):
     components before it.  ``tail_pvalues[0]`` (all squared singular values summed) is the omnibus test.
     """
     est, views_, n, p, c_, center, on_device = _resample.prepare(
-        "permutation_test", "whitens all rows on one device", estimator, views, lambda n, p: check_limits(n, p, n_permutations))
+        "permutation_test", "whitens all rows on one device", estimator, views, lambda n, p: check_limits(n, p, n_permutations),
+        draws)
     B, r = int(n_permutations), min(p)
-    rng = np.random.default_rng(random_state)
 
     h = _backend.handle_for(views_)
     x64, xptr = _resample.stage_f64(h, views_, on_device)  # for K1 and the whitening
@@ -161,7 +169,11 @@ def permutation_test(estimator, views, n_permutations=1000, random_state=None):
         sv = h.alloc((B + 1) * r * 8)
         singular_values(h, n, p[0], p[1], Z[0].ptr, Z[1].ptr, None, 1, sv.ptr)
         chunk = chunk_length(n)
-        slots = _resample.run_chunks(h, permutation_chunks(rng, n, B, chunk), min(chunk, B) * n * 4,
+        if draws == "device":
+            source = _resample.device_chunks(h, "permutations", n, _resample.device_seed(random_state), B, chunk)
+        else:
+            source = permutation_chunks(np.random.default_rng(random_state), n, B, chunk)
+        slots = _resample.run_chunks(h, source, min(chunk, B) * n * 4,
                                      lambda ptr, count, done: singular_values(h, n, p[0], p[1], Z[0].ptr, Z[1].ptr, ptr, count,
                                                                               sv.ptr + (1 + done) * r * 8))
         out = h.to_host(sv, (B + 1, r))

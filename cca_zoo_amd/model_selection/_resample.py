@@ -1,6 +1,7 @@
 """The host half of what :func:`permutation_test` and :func:`bootstrap` share (the device half is ``csrc/resample_dev.h``): the
 checks before the device is touched, the float64 staging, and the loop that draws one chunk of resamples ahead of the device,
-the arrangement of the EY models' mini-batch indices (``linear/gradient/_base.py``).
+the arrangement of the EY models' mini-batch indices (``linear/gradient/_base.py``) -- or, with ``draws="device"``, has the
+device draw each chunk itself (``csrc/draw.hip``), in the same loop.
 """
 
 from __future__ import annotations
@@ -15,6 +16,8 @@ from cca_zoo_amd._utils._validation import is_device_tensor, is_sparse_view, per
 MAX_WIDTH = 64
 ROWS_PER_SPLIT = 4096
 MAX_ROWS = 2 ** 31
+#: where a resample is drawn: by NumPy on the host, one chunk ahead of the device, or by ``csrc/draw.hip`` in the slot itself
+DRAWS = ("numpy", "device")
 
 
 def is_half(v):
@@ -34,7 +37,12 @@ def check_shape(name, n, p, advice=""):
         raise ValueError("at least 2 samples are required")
 
 
-def prepare(name, one_device, estimator, views, check):
+def device_seed(random_state):
+    """The 64-bit seed of the device draws: one rule for ``None``, ints, ``SeedSequence`` s and ``Generator`` s."""
+    return int(np.random.default_rng(random_state).integers(0, 2 ** 64, dtype=np.uint64))
+
+
+def prepare(name, one_device, estimator, views, check, draws="numpy"):
     """Every refusal that needs no device, in a fixed order; ``check(n, p)`` is the caller's own (its counts and levels, then
     :func:`check_shape`).  Returns ``est, views_, n, p, c_, center, on_device``: ``est`` is a validated clone."""
     from sklearn.base import clone
@@ -51,6 +59,8 @@ def prepare(name, one_device, estimator, views, check):
             raise TypeError(f"{name}: sparse views are not supported; pass dense arrays")
         if is_half(v):
             raise TypeError(f"{name}: half-precision views are not supported; pass float32 or float64")
+    if not (isinstance(draws, str) and draws in DRAWS):
+        raise ValueError(f"{name}: draws must be one of {list(DRAWS)}, got {draws!r}")
     est = clone(estimator)
     est._validate_params()
     views_ = [as_float(v) for v in validate_views(list(views), check_finite=False)]
@@ -91,15 +101,42 @@ def chunks(draw, rng, n, total, chunk):
         done += step
 
 
+def device_chunks(h, what, n, seed, total, chunk):
+    """The ``total`` resamples of ``csrc/draw.hip`` in chunks of at most ``chunk``, as device producers ``(count, write)``:
+    ``write(ptr)`` enqueues the draw of resamples ``[done, done + count)`` into ``ptr``.  ``what``: ``"permutations"`` (row
+    ``b`` = the argsort of stream ``b``'s keys) or ``"counts"`` (row ``b`` = the multiplicities of stream ``b``'s ``n`` draws);
+    a row is a function of ``(seed, b, n)`` only, so the chunk length does not change a bit."""
+    import ctypes as C
+
+    def write(ptr, count, first):
+        if what == "permutations":
+            h.check(h.lib.ccz_draw_permutations(h.raw, int(n), count, seed, first, 0, C.c_void_p(int(ptr))))
+        else:
+            h.check(h.lib.ccz_draw_counts(h.raw, int(n), count, seed, first, C.c_void_p(int(ptr))))
+
+    done = 0
+    while done < total:
+        step = min(int(chunk), total - done)
+        yield step, (lambda ptr, step=step, done=done: write(ptr, step, done))
+        done += step
+
+
 def run_chunks(h, chunks, slot_bytes, call):
-    """``call(ptr, count, done)`` for every chunk, uploaded to one of two slots of ``slot_bytes``: the next chunk is drawn while
-    the device works on this one, and its upload is ordered behind that work on the handle's stream.  Returns the slots, which
-    the caller keeps until it has read the results."""
+    """``call(ptr, count, done)`` for every chunk, in one of two slots of ``slot_bytes``.  A host chunk (an array of
+    :func:`chunks`) is uploaded: the next one is drawn while the device works on this one, and its upload is ordered behind that
+    work on the handle's stream.  A device chunk (``(count, write)`` of :func:`device_chunks`) is drawn into the slot by
+    ``write(ptr)``, in stream order, and nothing is built or uploaded by the host.  Returns the slots, which the caller keeps
+    until it has read the results."""
     slots = [h.alloc(slot_bytes) for _ in range(2)]
     done = 0
     for i, block in enumerate(chunks):
         slot = slots[i & 1]
-        h.h2d(slot.ptr, block)
-        call(slot.ptr, block.shape[0], done)
-        done += block.shape[0]
+        if isinstance(block, np.ndarray):
+            count = block.shape[0]
+            h.h2d(slot.ptr, block)
+        else:
+            count, write = block
+            write(slot.ptr)
+        call(slot.ptr, count, done)
+        done += count
     return slots

@@ -1134,6 +1134,34 @@ CCZ_API int ccz_boot_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const
                           const int32_t* counts_dev, int64_t nboot, double c1, double c2, int center, int64_t k, double* sv_dev,
                           double* W_dev, int32_t* info_dev);
 
+/* ---- the draws of the two routines above, made on the device (csrc/draw.hip) ---
+ * Pure functions of (seed, b, n), b = the resample's index in the whole call (row i of a call is resample first + i), on
+ * the stream convention of the ccz_svi_* and ccz_nuts_* sections (all arithmetic uint64, wrapping):
+ *   stream(seed, b, site) = splitmix64(splitmix64(splitmix64(seed) + b) + site)
+ *   key(seed, b, site, j) = splitmix64(stream(seed, b, site) ^ splitmix64(j))                            j = 0 .. n - 1
+ * ccz_draw_permutations: perms_dev (nperm x n, int32) row i = pi_{first + i} = argsort_j key(seed, first + i, CCZ_DRAW_SITE_PERM, j),
+ *   i.e. pi[rank] = j.  splitmix64 is a bijection of the 64-bit words, so the n keys of one stream are pairwise distinct:
+ *   the order is total and no tie rule exists.  The keys are never stored: a one-level bucket sort (count, scan, scatter,
+ *   sort in LDS) recomputes them from j.  bucket_rows = expected rows per bucket (0: CCZ_DRAW_BUCKET_ROWS); the result does
+ *   not depend on it by a bit -- it exists so that tests reach the scan over many buckets and, with more than
+ *   CCZ_DRAW_SORT_CAP rows in a bucket, the slower path that ranks an oversize bucket by counting.
+ * ccz_draw_counts: counts_dev (nboot x n, int32) row i = m_{first + i}, m_b[s] = #{j < n : idx_j = s} with
+ *   idx_j = (key(seed, b, CCZ_DRAW_SITE_BOOT, j) * n) >> 64, the high word of the 128-bit product (multiply-shift, no
+ *   rejection): a row is drawn with probability within n / 2^64 of 1 / n (some rows own one more of the 2^64 keys than
+ *   others), below 1.2e-10 relative at n = 2^31 and below anything a test can see.
+ * Integer arithmetic and integer atomics only: the bits depend on (seed, first + i, n) alone -- not on nperm / nboot, on
+ * how a caller cuts its resamples into calls, or on bucket_rows.  Scratch (bucket cursors, rows in bucket order) is pooled
+ * in the handle and sized per launch group.  Enqueue-only on the handle's stream.
+ * CCZ_EINVAL: n < 1, nperm / nboot < 1, first < 0, bucket_rows < 0 or a null pointer;  CCZ_EUNSUP: n >= 2^31.  A refused call
+ * writes nothing. */
+#define CCZ_DRAW_SITE_PERM 0x5045524Dull   /* "PERM" */
+#define CCZ_DRAW_SITE_BOOT 0x424F4F54ull   /* "BOOT" */
+#define CCZ_DRAW_BUCKET_ROWS 1024
+#define CCZ_DRAW_SORT_CAP 2048             /* rows of one bucket that the sort pass holds in LDS */
+CCZ_API int ccz_draw_permutations(ccz_handle h, int64_t n, int64_t nperm, uint64_t seed, int64_t first, int64_t bucket_rows,
+                                  int32_t* perms_dev);
+CCZ_API int ccz_draw_counts(ccz_handle h, int64_t n, int64_t nboot, uint64_t seed, int64_t first, int32_t* counts_dev);
+
 #ifdef __cplusplus
 }
 #endif

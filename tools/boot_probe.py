@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Measure ``bootstrap`` (csrc/boot.hip) on one GPU and print one JSON object (``--out`` also writes it).
 
-    python tools/boot_probe.py [--out profiles/boot_probe.json] [--B 1000] [--parts device,public,refit,numpy] [--shapes all]
+    python tools/boot_probe.py [--out profiles/boot_probe.json] [--B 1000] [--parts device,draw,public,refit,numpy] [--shapes all]
 
-Shapes: n = 16384 / 1048576, (p1, p2) = (16, 16) and (64, 64), float32 host views (planted rank 2 plus noise), k = 2.
+Shapes: n = 16384 / 131072 / 1048576, (p1, p2) = (16, 16) and (64, 64), float32 host views (planted rank 2 plus noise), k = 2.
 
 - ``device``: the shift (column means, ``ccz_transform`` with an identity; host clock around a stream synchronise, second of
   two rounds) and the resamples through the C ABI: ``B`` resamples as calls of ``CHUNK`` resamples each (the public function's
@@ -14,9 +14,13 @@ Shapes: n = 16384 / 1048576, (p1, p2) = (16, 16) and (64, 64), float32 host view
   workgroups -- and the rate it gives.  The split between ``k_boot_moments`` and ``k_boot_solve`` comes from a kernel
   trace of ``--parts device`` taken in a run of its own (``rocprofv3 --kernel-trace --stats``, summarised by
   tools/rocpd_stats.py into ``profiles/boot_kernel_stats.md``).
-- ``public``: ``bootstrap(rCCA(latent_dimensions=2, c=[0.1, 0.3]), views, n_resamples=B_public)`` end to end, with the host's
-  ``rng.integers`` draws, ``np.bincount`` and the count uploads; ``B_public`` is ``B`` scaled down at the largest n (stated in
-  the output).  Beside it the host's draw + bincount alone, per resample.
+- ``draw``: ``ccz_draw_counts`` (csrc/draw.hip) alone, through the C ABI: ``B`` resamples as calls of ``CHUNK`` each into one
+  device buffer (the rows zeroed, then one integer atomic add per draw).  Beside it the traffic MODEL ``8 n`` bytes per
+  resample -- 4 n zeroed, 4 n added -- and the rate it gives.
+- ``public``: ``bootstrap(rCCA(latent_dimensions=2, c=[0.1, 0.3]), views, n_resamples=B_public)`` end to end, once with
+  ``draws="numpy"`` (the host's ``rng.integers`` draws, ``np.bincount`` and the count uploads) and once with
+  ``draws="device"``, in the same run; ``B_public`` is ``B`` scaled down at the largest n (stated in the output).  Beside it
+  the host's draw + bincount alone, per resample.
 - ``refit``: the loop a user writes without this function: ``rCCA.fit([X1[idx], X2[idx]])`` on float32 CUDA views, the
   resampled views made by torch indexing on the device (``torch.randint`` on the device); ``B'`` fits, stated.
 - ``numpy``: the restatement's refit (tests/boot_restatement.py: gather, means, covariances, Cholesky, LAPACK SVD) on the
@@ -38,7 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-NS = (16384, 1048576)
+NS = (16384, 131072, 1048576)
 WIDTHS = ((16, 16), (64, 64))
 C_RIDGE = [0.1, 0.3]
 K = 2
@@ -88,6 +92,35 @@ def probe_device(views, B):
             "shift_share_of_B_resamples": round(shift_ms / (shift_ms + ms), 4)}
 
 
+def probe_draw(views, B):
+    import ctypes as C
+
+    from cca_zoo_amd import _backend
+    from cca_zoo_amd.model_selection import _bootstrap as bs
+
+    n = views[0].shape[0]
+    h = _backend.default_handle()
+    CHUNK = bs.chunk_length(n)
+    out = h.alloc(CHUNK * n * 4)
+    calls = max(1, B // CHUNK)
+
+    def run(k):
+        for i in range(k):
+            h.check(h.lib.ccz_draw_counts(h.raw, n, CHUNK, 12345, i * CHUNK, C.c_void_p(out.ptr)))
+        h.sync()
+
+    run(1)
+    t0 = time.perf_counter()
+    run(calls)
+    ms = (time.perf_counter() - t0) * 1e3
+    assert int(h.to_host(out, (CHUNK, n), dtype=np.int32)[-1].sum()) == n
+    done = calls * CHUNK
+    model = done * n * 8
+    return {"n": n, "resamples": done, "resamples_per_call": CHUNK, "draw_ms": round(ms, 3),
+            "us_per_resample": round(ms * 1e3 / done, 3), "traffic_model_bytes": model,
+            "traffic_model_tb_per_s": round(model / ms / 1e9, 3)}
+
+
 def probe_public(views, B):
     from cca_zoo_amd.linear import rCCA
     from cca_zoo_amd.model_selection import bootstrap
@@ -98,6 +131,10 @@ def probe_public(views, B):
     t0 = time.perf_counter()
     res = bootstrap(rCCA(latent_dimensions=K, c=C_RIDGE), views, n_resamples=b, random_state=0)
     ms = (time.perf_counter() - t0) * 1e3
+    bootstrap(rCCA(latent_dimensions=K, c=C_RIDGE), views, n_resamples=2, random_state=0, draws="device")
+    t0 = time.perf_counter()
+    dev = bootstrap(rCCA(latent_dimensions=K, c=C_RIDGE), views, n_resamples=b, random_state=0, draws="device")
+    dev_ms = (time.perf_counter() - t0) * 1e3
     rng = np.random.default_rng(0)
     t0 = time.perf_counter()
     for _ in range(5):
@@ -105,7 +142,9 @@ def probe_public(views, B):
     draw_ms = (time.perf_counter() - t0) * 1e3 / 5
     return {"n": n, "p": [v.shape[1] for v in views], "B_public": b, "scaled_down_by": B // b, "total_ms": round(ms, 2),
             "ms_per_resample": round(ms / b, 4), "host_integers_plus_bincount_ms_each": round(draw_ms, 4),
-            "sigma_1": float(res.singular_values[0]), "sigma_1_se": float(res.singular_values_se[0])}
+            "sigma_1": float(res.singular_values[0]), "sigma_1_se": float(res.singular_values_se[0]),
+            "device_draws_total_ms": round(dev_ms, 2), "device_draws_ms_per_resample": round(dev_ms / b, 4),
+            "device_draws_sigma_1_se": float(dev.singular_values_se[0]), "numpy_over_device": round(ms / dev_ms, 2)}
 
 
 def probe_refit(views, B):
@@ -155,12 +194,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--B", type=int, default=1000)
-    ap.add_argument("--parts", default="device,public,refit,numpy")
+    ap.add_argument("--parts", default="device,draw,public,refit,numpy")
     ap.add_argument("--shapes", default="all", help="all, or n:p1:p2[,n:p1:p2...]")
     a = ap.parse_args(argv)
     parts = a.parts.split(",")
     shapes = [(n, p1, p2) for n in NS for p1, p2 in WIDTHS] if a.shapes == "all" else [tuple(int(x) for x in s.split(":")) for s in a.shapes.split(",")]
-    fns = {"device": probe_device, "public": probe_public, "refit": probe_refit, "numpy": probe_numpy}
+    fns = {"device": probe_device, "draw": probe_draw, "public": probe_public, "refit": probe_refit, "numpy": probe_numpy}
     res = {"B": a.B, **{k: [] for k in parts}}
     for n, p1, p2 in shapes:
         views = make_views(n, p1, p2)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measure ``permutation_test`` (csrc/perm.hip) on one GPU and print one JSON object (``--out`` also writes it).
 
-    python tools/perm_probe.py [--out profiles/perm_probe.json] [--B 1000] [--parts device,public,refit,numpy] [--shapes all]
+    python tools/perm_probe.py [--out profiles/perm_probe.json] [--B 1000] [--parts device,draw,public,refit,numpy] [--shapes all]
 
 Shapes: n = 16384 / 131072 / 1048576, (p1, p2) = (16, 16) and (64, 64), float32 host views (planted rank 2 plus noise).
 
@@ -14,8 +14,14 @@ Shapes: n = 16384 / 131072 / 1048576, (p1, p2) = (16, 16) and (64, 64), float32 
   The split between ``k_perm_cross`` and ``k_perm_fold_svd`` comes from a kernel trace of ``--parts device`` taken in a
   run of its own (``rocprofv3 --kernel-trace --stats``, summarised by tools/rocpd_stats.py into
   ``profiles/perm_kernel_stats.md``).  How much of ``Z_1`` is served from L2 is not measured here (it needs counters).
-- ``public``: ``permutation_test(rCCA(c=[0.1, 0.3]), views, n_permutations=B_public)`` end to end, with the host's
-  ``rng.permutation`` draws and the index uploads; ``B_public`` is ``B`` scaled down at the largest n (stated in the output).
+- ``draw``: ``ccz_draw_permutations`` (csrc/draw.hip) alone, through the C ABI: ``B`` permutations as calls of ``CHUNK`` each
+  into one device buffer.  Beside it the traffic MODEL ``12 n`` bytes per permutation -- the rows written in bucket order, read
+  back by the sort pass and written in their final order, 4 bytes each; nothing for the bucket cursors or the atomics -- and
+  the rate it gives.  The share of each pass comes from a kernel trace of ``--parts draw`` taken in a run of its own
+  (``profiles/draw_kernel_stats.md``).
+- ``public``: ``permutation_test(rCCA(c=[0.1, 0.3]), views, n_permutations=B_public)`` end to end, once with ``draws="numpy"``
+  (the host's ``rng.permutation`` draws and the index uploads) and once with ``draws="device"``, in the same run;
+  ``B_public`` is ``B`` scaled down at the largest n (stated in the output).
 - ``refit``: the loop a user writes today: ``rCCA.fit([X1, X2[pi]])`` on float32 CUDA views, the permuted view made by torch
   indexing on the device (``torch.randperm`` on the device); ``B'`` fits, stated.
 - ``numpy``: the restatement's permutation step (tests/perm_restatement.py: gather, product, LAPACK SVD) on the host's threads,
@@ -85,6 +91,34 @@ def probe_device(views, B):
             "whitening_share_of_B_permutations": round(whiten_ms / (whiten_ms + null_ms), 4)}
 
 
+def probe_draw(views, B):
+    import ctypes as C
+
+    from cca_zoo_amd import _backend
+    from cca_zoo_amd.model_selection import _permutation as pm
+
+    n = views[0].shape[0]
+    h = _backend.default_handle()
+    CHUNK = pm.chunk_length(n)
+    out = h.alloc(CHUNK * n * 4)
+    calls = max(1, B // CHUNK)
+
+    def run(k):
+        for i in range(k):
+            h.check(h.lib.ccz_draw_permutations(h.raw, n, CHUNK, 12345, i * CHUNK, 0, C.c_void_p(out.ptr)))
+        h.sync()
+
+    run(1)
+    t0 = time.perf_counter()
+    run(calls)
+    ms = (time.perf_counter() - t0) * 1e3
+    done = calls * CHUNK
+    model = done * n * 12
+    return {"n": n, "permutations": done, "permutations_per_call": CHUNK, "draw_ms": round(ms, 3),
+            "us_per_permutation": round(ms * 1e3 / done, 3), "traffic_model_bytes": model,
+            "traffic_model_tb_per_s": round(model / ms / 1e9, 3)}
+
+
 def probe_public(views, B):
     from cca_zoo_amd.linear import rCCA
     from cca_zoo_amd.model_selection import permutation_test
@@ -95,13 +129,19 @@ def probe_public(views, B):
     t0 = time.perf_counter()
     res = permutation_test(rCCA(c=C_RIDGE), views, n_permutations=b, random_state=0)
     ms = (time.perf_counter() - t0) * 1e3
+    permutation_test(rCCA(c=C_RIDGE), views, n_permutations=2, random_state=0, draws="device")
+    t0 = time.perf_counter()
+    dev = permutation_test(rCCA(c=C_RIDGE), views, n_permutations=b, random_state=0, draws="device")
+    dev_ms = (time.perf_counter() - t0) * 1e3
     rng = np.random.default_rng(0)
     t0 = time.perf_counter()
     for _ in range(5):
         rng.permutation(n)
     draw_ms = (time.perf_counter() - t0) * 1e3 / 5
     return {"n": n, "p": [v.shape[1] for v in views], "B_public": b, "scaled_down_by": B // b, "total_ms": round(ms, 2),
-            "ms_per_permutation": round(ms / b, 4), "host_rng_permutation_ms_each": round(draw_ms, 4), "pvalue_0": float(res.pvalues[0])}
+            "ms_per_permutation": round(ms / b, 4), "host_rng_permutation_ms_each": round(draw_ms, 4), "pvalue_0": float(res.pvalues[0]),
+            "device_draws_total_ms": round(dev_ms, 2), "device_draws_ms_per_permutation": round(dev_ms / b, 4),
+            "device_draws_pvalue_0": float(dev.pvalues[0]), "numpy_over_device": round(ms / dev_ms, 2)}
 
 
 def probe_refit(views, B):
@@ -151,12 +191,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--B", type=int, default=1000)
-    ap.add_argument("--parts", default="device,public,refit,numpy")
+    ap.add_argument("--parts", default="device,draw,public,refit,numpy")
     ap.add_argument("--shapes", default="all", help="all, or n:p1:p2[,n:p1:p2...]")
     a = ap.parse_args(argv)
     parts = a.parts.split(",")
     shapes = [(n, p1, p2) for n in NS for p1, p2 in WIDTHS] if a.shapes == "all" else [tuple(int(x) for x in s.split(":")) for s in a.shapes.split(",")]
-    fns = {"device": probe_device, "public": probe_public, "refit": probe_refit, "numpy": probe_numpy}
+    fns = {"device": probe_device, "draw": probe_draw, "public": probe_public, "refit": probe_refit, "numpy": probe_numpy}
     res = {"B": a.B, **{k: [] for k in parts}}
     for n, p1, p2 in shapes:
         views = make_views(n, p1, p2)
