@@ -80,8 +80,11 @@ __global__ void __launch_bounds__(256) k_perm_fold_svd(const double* __restrict_
   column_norms(A, RS_LDA, m, r, [&](int j, double s) { nrm[j] = (settled && s == s) ? sqrt(s) : rs_nan(); });
   __syncthreads();
   if (tid < r) {
-    const double v = nrm[tid];
-    sv[int64_t(blockIdx.x) * r + (v == v ? rank_desc(nrm, r, tid) : tid)] = v;   // NaN: every slot of the row is written once
+    // One NaN norm makes the whole row NaN, every slot written once.  (With p1 < p2 the columns are the ROWS of T, so a NaN in
+    // Z_1 reaches one column only: ranking the others beside it would write one slot twice and leave the last one untouched.)
+    bool fine = true;
+    for (int k = 0; k < r; ++k) fine = fine && nrm[k] == nrm[k];
+    sv[int64_t(blockIdx.x) * r + (fine ? rank_desc(nrm, r, tid) : tid)] = fine ? nrm[tid] : rs_nan();
   }
 }
 
