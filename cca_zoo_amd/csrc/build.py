@@ -23,7 +23,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libccz.so")
 ARCH = "gfx950"
-SOURCES = ["api.hip", "comm.hip", "ops_hip.hip", "gram.hip", "gram_split.hip", "half_io.hip", "gemm_split.hip", "project_split.hip", "project_bf16.hip", "gemm_big.hip", "gemm64_big.hip", "gemm64_skinny.hip", "cholinv.hip", "evd_block.hip", "loss.hip", "ssl_loss.hip", "rng.hip", "kernel_matrix.hip", "ey.hip", "als.hip", "gfa.hip", "svi.hip", "nuts.hip", "krmoment.hip", "cp_als.hip", "rrr.hip", "tree.hip", "perm.hip", "boot.hip", "draw.hip", "solve.cpp", "kcca.cpp"]
+SOURCES = ["api.hip", "comm.hip", "runtime.hip", "gemm64.hip", "dense_ops.hip", "potrf.hip", "syev_small.hip", "gram.hip", "gram_split.hip", "half_io.hip", "gemm_split.hip", "project_split.hip", "project_bf16.hip", "gemm_big.hip", "gemm64_big.hip", "gemm64_skinny.hip", "cholinv.hip", "evd_block.hip", "loss.hip", "ssl_loss.hip", "rng.hip", "kernel_matrix.hip", "ey.hip", "als.hip", "gfa.hip", "svi.hip", "nuts.hip", "krmoment.hip", "cp_als.hip", "rrr.hip", "tree.hip", "perm.hip", "boot.hip", "draw.hip", "solve.cpp", "kcca.cpp"]
 HEADERS = ["ops.h", "env.h", "hip_common.h", "abi_guard.h", "gram_map.h", "split_mma.h", "jacobi_dev.h", "resample_dev.h", "rng_hash.h", "half_cvt.h", "fit_driver.h", "row_load.h", "reduce.h", "svi_fused.h", os.path.join(ROOT, "include", "ccz.h")]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 HIPFLAGS = [f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fgpu-rdc" if False else "-fno-gpu-rdc"]

@@ -228,7 +228,7 @@ int ccz_moments_exchange(ccz_handle h, double* moments_dev, int64_t D, const int
     double nt = 0.0;
     d2h(h, &nt, packed + n_head - 1, 8);                    // waits for the head only; the tail is still in flight
     *n_total_out = int64_t(nt + 0.5);
-    if (n_tail > 0) im->deferred_event = xev[2];    // consumed by the next solve (ops_hip.hip: wait_deferred)
+    if (n_tail > 0) im->deferred_event = xev[2];    // consumed by the next solve (runtime.hip: wait_deferred)
   })
 }
 

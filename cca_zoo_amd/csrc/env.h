@@ -68,37 +68,37 @@ using STR = const char*;
   X(GEMM_BIG_MIN_K, I64, 64, ONCE, "smallest K of the big kernel -- gemm64_big.hip gemm_f64_big_eligible: A/B")                              \
   X(GEMM_HALF_TILE, I64, 1, ONCE, "0: no half-height tiles on grids smaller than the chip -- gemm64_big.hip gemm_f64_big: A/B")              \
   X(GEMM_SKINNY_OFF, STR, nullptr, ONCE, "text starting with 1: the skinny kernel is never eligible -- gemm64_skinny.hip gemm_f64_skinny_eligible: A/B") \
-  /* ---- Cholesky and triangular solves (cholinv.hip, ops_hip.hip) ---- */                                                                   \
+  /* ---- Cholesky and triangular solves (cholinv.hip, potrf.hip) ---- */                                                                     \
   X(CHOLINV_CHAIN, INT, 1, ONCE, "0: the launch-per-link form instead of the persistent chain kernel -- cholinv.hip chain_launch: A/B")      \
   X(CHAIN_WGS, INT, 128, ONCE, "workgroups of the chain launch (below 2: 2; Impl::chain_cap overrides it) -- cholinv.hip chain_launch: A/B")  \
-  X(CHAIN_WGS_LA, INT, 64, ONCE, "the same on the look-ahead stream, next to the update GEMMs -- ops_hip.hip potrf_lower_batched_sb: A/B")   \
+  X(CHAIN_WGS_LA, INT, 64, ONCE, "the same on the look-ahead stream, next to the update GEMMs -- potrf.hip potrf_lower_batched_sb: A/B")     \
   X(CHAIN_SLEEP, INT, 1, ONCE, "sleep of the chain kernel's polling loops (below 1: 1) -- cholinv.hip chain_launch: A/B")                    \
   X(CHAIN_DEBUG, INT, 0, ONCE, "non-zero: shader-clock stamps of matrix 0's chain workgroup per launch (synchronises) -- cholinv.hip chain_launch: trace") \
-  X(POTRF_SB, I64, 512, LOAD, "256 | 512 | 1024 (else: 512) columns per super-block; every user of the kept inverses sees one value -- ops_hip.hip SB: A/B") \
-  X(POTRF_LOOKAHEAD, INT, 1, ONCE, "0: the next super-block is factored on the handle's stream, not on a second one -- ops_hip.hip potrf_lookahead: A/B") \
-  X(POTRF_RIDER, INT, 1, ONCE, "0: the first whitening solve does not ride along the factorization -- ops_hip.hip potrf_lower_batched_aux_rider: A/B") \
-  X(BACKPROJ_SPLIT, INT, 4, ONCE, "split-K factor of the batched few-row solves -- ops_hip.hip trsm_right_lower_aux_multi: A/B")             \
-  /* ---- eigensolvers (solve.cpp, ops_hip.hip, evd_block.hip) ---- */                                                                        \
+  X(POTRF_SB, I64, 512, LOAD, "256 | 512 | 1024 (else: 512) columns per super-block; every user of the kept inverses sees one value -- potrf.hip SB: A/B")   \
+  X(POTRF_LOOKAHEAD, INT, 1, ONCE, "0: the next super-block is factored on the handle's stream, not on a second one -- potrf.hip potrf_lookahead: A/B")   \
+  X(POTRF_RIDER, INT, 1, ONCE, "0: the first whitening solve does not ride along the factorization -- potrf.hip potrf_lower_batched_aux_rider: A/B")   \
+  X(BACKPROJ_SPLIT, INT, 4, ONCE, "split-K factor of the batched few-row solves -- potrf.hip trsm_right_lower_aux_multi: A/B")               \
+  /* ---- eigensolvers (solve.cpp, syev_small.hip, evd_block.hip) ---- */                                                                     \
   X(EVD_REFRESH_MIN, INT, 1536, ONCE, "size from which the block Jacobi restarts from clean data near convergence -- evd_block.hip syev_block: knob") \
   X(BJ_GROUP_MIN_TILES, I64, 2048, ONCE, "row tiles from which a workgroup takes four 64-column chunks -- evd_block.hip bj_row_group: A/B")  \
   X(BJ_GRAM_SPLIT, INT, 0, ONCE, "column splits of the pair Gram products (below 1: 1); UNSET: sized to fill the chip -- evd_block.hip jacobi_rows_block: A/B") \
   X(BJ_DEBUG, FLAG, false, ONCE, "clock stamps of the pair kernel's three waves, printed in sweep 2 -- evd_block.hip syev_block: trace")     \
-  X(SYEV_TWOSIDED, INT, 2, ONCE, "small EVD: 2 packed H + replayed V' (d <= 160), 1 fused LDS kernel (d <= 96), else no one-workgroup kernel: every size takes the block Jacobi of evd_block.hip -- ops_hip.hip syev_mode: A/B") \
-  X(SYEV_CHASE, INT, 1, ONCE, "0: the replay of V' is a launch of its own, not a chaser next to the solve -- ops_hip.hip syev_small: A/B")   \
+  X(SYEV_TWOSIDED, INT, 2, ONCE, "small EVD: 2 packed H + replayed V' (d <= 160), 1 fused LDS kernel (d <= 96), else no one-workgroup kernel: every size takes the block Jacobi of evd_block.hip -- syev_small.hip syev_mode: A/B") \
+  X(SYEV_CHASE, INT, 1, ONCE, "0: the replay of V' is a launch of its own, not a chaser next to the solve -- syev_small.hip syev_small: A/B") \
   X(RR1_TOL, REAL, 1e-9, ONCE, "Jacobi threshold of the FIRST Rayleigh-Ritz (at or below 2.2e-16: full accuracy) -- solve.cpp topk_symmetric: A/B") \
   X(CHEB_MARGIN, REAL, 1e3, ONCE, "safety factor on the damping asked of the Chebyshev filter -- solve.cpp topk_symmetric: A/B")             \
   X(CHEB_MAXDEG, INT, 40, ONCE, "largest filter degree -- solve.cpp topk_symmetric: A/B")                                                    \
   X(CHEB_FIRSTCAP, INT, 28, ONCE, "largest degree of the first filter (below 2: 2) -- solve.cpp topk_symmetric: A/B")                        \
-  /* ---- handle, host waits, communication (api.hip, ops_hip.hip, comm.hip) ---- */                                                          \
+  /* ---- handle, host waits, communication (api.hip, runtime.hip, comm.hip) ---- */                                                          \
   X(GRAPHS, INT, 1, HANDLE, "0: launch chains are issued directly, never captured into hipGraphs -- api.hip ccz_create: A/B")               \
-  X(SPIN_WAIT_MS, REAL, 50.0, ONCE, "milliseconds a short host wait polls before it blocks (0: always block) -- ops_hip.hip spin_budget_ms: knob") \
-  X(D2H_MODE, INT, 0, LIVE, "small read-backs: 0 copy kernel with 8-byte lanes, 1 with 16-byte lanes, 2 hipMemcpyAsync + polled event, 3 + hipStreamSynchronize, 4 one blocking hipMemcpy -- ops_hip.hip d2h: A/B (tools/d2h_probe.py)") \
+  X(SPIN_WAIT_MS, REAL, 50.0, ONCE, "milliseconds a short host wait polls before it blocks (0: always block) -- runtime.hip spin_budget_ms: knob") \
+  X(D2H_MODE, INT, 0, LIVE, "small read-backs: 0 copy kernel with 8-byte lanes, 1 with 16-byte lanes, 2 hipMemcpyAsync + polled event, 3 + hipStreamSynchronize, 4 one blocking hipMemcpy -- runtime.hip d2h: A/B (tools/d2h_probe.py)") \
   X(RCCL_LIB, STR, nullptr, ONCE, "path of the one RCCL library to dlopen (read by the first communicator call) -- comm.hip rccl: knob; tests force the not-found path with it") \
   /* ---- traces ---- */                                                                                                                      \
   X(TRACE_PHASES, INT, 0, ONCE, "1 synchronise at phase boundaries and print wall times, 2 (rCCA solve only) events + shader clock without synchronising -- solve.cpp PhaseTimer (rcca, kcca, kgcca): trace") \
   X(TRACE_SOLVER, FLAG, false, ONCE, "Jacobi sweeps, cycles and filter degrees of the subspace iteration -- solve.cpp rayleigh_ritz, topk_symmetric: trace") \
-  X(TRACE_POOL, FLAG, false, ONCE, "every hipMalloc behind a pool miss and every graph capture -- ops_hip.hip dev_alloc, graph_run: trace")  \
-  X(TRACE_D2H, FLAG, false, LIVE, "device and host time of every small read-back -- ops_hip.hip d2h: trace")
+  X(TRACE_POOL, FLAG, false, ONCE, "every hipMalloc behind a pool miss and every graph capture -- runtime.hip dev_alloc, graph_run: trace")  \
+  X(TRACE_D2H, FLAG, false, LIVE, "device and host time of every small read-back -- runtime.hip d2h: trace")
 
 #define CCZ_ENV_ROW(id, kind, dflt_, when_, doc)        \
   struct id##_t {                                       \

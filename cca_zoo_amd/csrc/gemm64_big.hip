@@ -9,7 +9,7 @@
 //     owns one row, reads 64 contiguous bytes of it and scatters 8 ds_write_b64 (consecutive lanes ->
 //     consecutive addresses).
 // Rows / columns past M / N are clamped on load and masked on store; K must be a multiple of 16.
-// The super-blocked Cholesky / triangular solves in ops_hip.hip put ~all solver flops through this kernel
+// The super-blocked Cholesky / triangular solves in potrf.hip put ~all solver flops through this kernel
 // with K = 512 (the 64 x 64-tile generic kernel keeps the small and ragged products).
 #include <algorithm>
 #include <cstdlib>

@@ -121,14 +121,14 @@ struct Impl {
   PinMem<> small_pin[kSmallSlots];
   Event small_ev[kSmallSlots];
   int small_next = 0;
-  // second stream + events for the look-ahead of the super-blocked Cholesky (ops_hip.hip), created on first use
+  // second stream + events for the look-ahead of the super-blocked Cholesky (potrf.hip), created on first use
   std::optional<SideStream<2>> aux;
   // sticky failure record of the stream-native loss (loss.hip): pinned + mapped host words written by the device
   PinMem<int> loss_status;          // host view
   int* loss_status_dev = nullptr;   // device view of the same words (not owned)
   // hand-over events between a caller's stream and the handle's stream (ccz_stream_acquire / ccz_stream_release)
   Event xs_ev[2];
-  // polled waits (ops_hip.hip: wait_stream_short) and the pinned landing buffer of small device -> host copies
+  // polled waits (runtime.hip: wait_stream_short) and the pinned landing buffer of small device -> host copies
   Event wait_ev;
   PinMem<> d2h_pin;
   void* d2h_pin_dev = nullptr;      // device view of d2h_pin (host-mapped, not owned): written by a copy kernel
@@ -197,7 +197,7 @@ __device__ __forceinline__ void st_shared2(double* p, double a, double b) {
 }
 #endif
 
-// ops_hip.hip: capture-once / replay-later for launch-bound fixed sequences, keyed on shapes AND pointers
+// runtime.hip: capture-once / replay-later for launch-bound fixed sequences, keyed on shapes AND pointers
 uint64_t graph_key_mix(uint64_t h, uint64_t v);
 void graph_run_fn(ccz_ctx* c, uint64_t key, const std::function<void()>& fn);
 void sync_short(ccz_ctx* c);   // polled wait for the handle's stream (short waits)
@@ -205,8 +205,11 @@ void sync_short(ccz_ctx* c);   // polled wait for the handle's stream (short wai
 // evd_block.hip: one-sided block Jacobi on the rows of W (p a multiple of 64, even leading dimensions)
 int jacobi_rows_block(ccz_ctx* c, int64_t p, int64_t q, double* W, int64_t ldw, double* Q, int64_t qc, int64_t ldq, int max_sweeps);
 
-// ops_hip.hip: wait for the handle's stream, then give the pool's unused blocks back to the driver; returns the bytes released
+// runtime.hip: wait for the handle's stream, then give the pool's unused blocks back to the driver; returns the bytes released
 size_t pool_trim(ccz_ctx* c);
+
+// potrf.hip: the wave kernel uses 65 KiB of dynamic LDS: opt in once per device (activate; never inside a graph capture)
+void wave_kernels_init();
 
 // api.hip: blocks layout of the sharded exchange (ccz.h), pack or unpack, head / tail / both, optionally on a foreign stream
 void moments_blocks(ccz_ctx* c, bool pack, double* mom, int64_t D, const int64_t* dims, int m, double* packed, int which,

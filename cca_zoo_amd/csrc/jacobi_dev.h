@@ -1,4 +1,4 @@
-// Device-side helpers shared by the Jacobi kernels (ops_hip.hip: the one-workgroup eigen-solvers of the Rayleigh-Ritz
+// Device-side helpers shared by the Jacobi kernels (syev_small.hip: the one-workgroup eigen-solvers of the Rayleigh-Ritz
 // steps; evd_block.hip: the blocked two-sided / one-sided Jacobi for d > 160; resample_dev.h: the one-sided Jacobi SVD of
 // permutation_test and bootstrap).
 #pragma once
@@ -43,7 +43,7 @@ __device__ __forceinline__ jac_cs jac_rotation(double hpp, double hqq, double hp
 }
 
 
-// Workgroup barrier that orders LDS traffic only (see the note in ops_hip.hip above k_syev_packed).
+// Workgroup barrier that orders LDS traffic only (see the note in syev_small.hip above k_syev_packed).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ int tri_off(int i, int j) {

@@ -2,8 +2,9 @@
 //
 // The solver drivers (solve.cpp: Cholesky whitening, Chebyshev-filtered
 // subspace iteration, rCCA/MCCA/GCCA assembly) are plain C++ written against
-// this header only.  The product implementation is ops_hip.hip (HIP kernels on
-// gfx950).  tests/hostsim/ops_host.cpp implements the same interface with
+// this header only.  The product implementation is runtime.hip, gemm64.hip,
+// dense_ops.hip, potrf.hip and syev_small.hip (HIP kernels on gfx950), with the
+// files they dispatch to.  tests/hostsim/ops_host.cpp implements the same interface with
 // host loops so that the driver LOGIC can be unit-tested in a container
 // without a GPU; that library is test infrastructure and is never loaded by
 // the cca_zoo_amd package.

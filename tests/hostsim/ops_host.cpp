@@ -245,7 +245,7 @@ void trsm_right_lower_aux_multi(ccz_ctx* c, int count, bool trans, const int64_t
   for (int b = 0; b < count; ++b) trsm_right_lower(c, trans, r[b], d[b], L[b], ldl[b], X[b], ldx[b]);
 }
 
-// Two-sided Jacobi in the device kernel's own formulation (k_syev_small, ops_hip.hip): round-robin tournament,
+// Two-sided Jacobi in the device kernel's own formulation (k_syev_small, syev_small.hip): round-robin tournament,
 // all rotation parameters of a round from the current H, then every 2 x 2 block R_a' M R_b and the rows of V'.
 int syev_small_max(ccz_ctx*) { return 160; }
 int syev_small(ccz_ctx*, const double* A, int64_t d, int64_t lda, double* w, double* Vt, int64_t ldv, int max_sweeps, double tol) {

@@ -458,7 +458,7 @@ def cholinv_mixed():
 
 
 def rcca_from_moments():
-    """rCCA from float64 moments with BOTH views wider than 1024 columns: ops_hip.hip potrf_dispatch factors them on
+    """rCCA from float64 moments with BOTH views wider than 1024 columns: potrf.hip potrf_dispatch factors them on
     super-blocks with kept inverses, so the first whitening solve rides along the factorization of view 2's factor
     (potrf_lower_batched_aux_rider; solve.cpp: rider.matrix = 1) and the back-projection of the k directions is the batched
     few-row solve (trsm_right_lower_aux_multi: every d > 1024, 1 <= r <= 256).  At (600, 520) neither site is reached.
@@ -569,12 +569,12 @@ def svd_topk(p, q, k):
 
 
 def eigen_probes():
-    for d in (2, 3, 12, 65, 96, 97, 160, 161):       # ops_hip.hip syev_small_max: 160 (mode 2), 96 (mode 1), 0 (else): the
+    for d in (2, 3, 12, 65, 96, 97, 160, 161):       # syev_small.hip syev_small_max: 160 (mode 2), 96 (mode 1), 0 (else): the
         syevj(d)                                     # sizes either side of each; wider ones take evd_block.hip syev_block
     gevp_topk(60, 5)                                 # p <= 192: the direct route (one small / block EVD)
     for d in (200, 513):                             # evd_block.hip syev_block (two-sided), padded to 256 / 576
         syevj(d)
-    gesvj(200, 513)                                  # ops_hip.hip jacobi_rows: 200 x (513 + 200) doubles > 144 KiB -> jacobi_rows_block
+    gesvj(200, 513)                                  # syev_small.hip jacobi_rows: 200 x (513 + 200) doubles > 144 KiB -> jacobi_rows_block
     gevp_topk(300, 12)                               # solve.cpp topk_symmetric: p > 192, 3 k < p -> filter cycles + Rayleigh-Ritz
     svd_topk(250, 320, 10)
 

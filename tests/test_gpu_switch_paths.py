@@ -214,7 +214,7 @@ def test_projection_keeps_the_fp32_kernel_on_a_split_handle(H, monkeypatch):
 
 @pytest.mark.parametrize("trace", [False, True])
 def test_small_read_backs_are_the_same_bytes_in_every_mode(H, monkeypatch, capfd, trace):
-    """CCZ_D2H_MODE=1..4 (ops_hip.hip d2h: 16-byte lanes, hipMemcpyAsync + polled event, + hipStreamSynchronize, one blocking
+    """CCZ_D2H_MODE=1..4 (runtime.hip d2h: 16-byte lanes, hipMemcpyAsync + polled event, + hipStreamSynchronize, one blocking
     hipMemcpy) against mode 0, bit for bit; with CCZ_TRACE_D2H every read-back also reports to stderr.  1, 7, 513 and 4097
     doubles are odd byte counts for mode 1 (no multiple of 16: it falls back to 8-byte lanes), so 2 and 4098 doubles are read
     too, and 4098 once more from a source that is 8 but not 16 bytes aligned."""

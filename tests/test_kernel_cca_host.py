@@ -125,6 +125,18 @@ def test_new_entry_points_are_declared_and_bound():
     assert '"kernel_matrix.hip"' in src and '"kcca.cpp"' in src
 
 
+def test_build_lists_name_every_source_and_header():
+    """build() takes staleness and the link line from these two lists: a file missing from them is not built, or not watched."""
+    from cca_zoo_amd.csrc import build
+
+    csrc = os.path.join(ROOT, "cca_zoo_amd", "csrc")
+    names = [f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
+    assert len(build.SOURCES) == len(set(build.SOURCES)) and len(build.HEADERS) == len(set(build.HEADERS))
+    assert set(build.SOURCES) == {f for f in names if f.endswith((".hip", ".cpp"))}
+    headers = {os.path.join(csrc, f) for f in names if f.endswith(".h")} | {os.path.join(ROOT, "include", "ccz.h")}
+    assert {os.path.normpath(os.path.join(csrc, h)) for h in build.HEADERS} == headers
+
+
 def test_solve_cpp_does_not_call_the_kernel_ops():
     """The host test double compiles solve.cpp alone: the KCCA drivers must live elsewhere."""
     src = open(os.path.join(ROOT, "cca_zoo_amd", "csrc", "solve.cpp")).read()

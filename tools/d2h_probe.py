@@ -3,7 +3,7 @@
 
 The outliers of bench.py's extras sit in the back-projection phase of the rCCA solve at the metric shape (three read-backs of
 2 MB, 2 MB and 64 KB).  This script fits CCA on resident views n x (4096, 4096) a few times under each read-back mode of
-ops_hip.hip's d2h() (CCZ_D2H_MODE) with CCZ_TRACE_D2H=1, which prints, per read-back, the time between two events around the
+runtime.hip's d2h() (CCZ_D2H_MODE) with CCZ_TRACE_D2H=1, which prints, per read-back, the time between two events around the
 copy on the DEVICE time line and the host's wall time for the whole call.  Usage: python tools/d2h_probe.py [rows] [fits]"""
 import os
 import sys
