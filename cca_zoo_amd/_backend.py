@@ -228,6 +228,7 @@ SIGNATURES = {
     "ccz_tree_predict": (_int, [_vp, _int, C.POINTER(View), _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64]),
     "ccz_perm_singular_values": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _dbl, _vp]),
     "ccz_boot_rcca": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _dbl, _dbl, _int, _i64, _vp, _vp, _vp]),
+    "ccz_jack_rcca": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _dbl, _int, _i64, _vp, _vp, _vp]),
     "ccz_draw_permutations": (_int, [_vp, _i64, _i64, C.c_uint64, _i64, _i64, _vp]),
     "ccz_draw_counts": (_int, [_vp, _i64, _i64, C.c_uint64, _i64, _vp]),
 }

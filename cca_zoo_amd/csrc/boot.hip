@@ -25,6 +25,10 @@
 //                   substitution (roles swapped for p1 < p2); the pair (u_j, v_j) keeps its coupled sign.  info: see
 //                   include/ccz.h; non-zero -> NaN rows.
 // Nothing is dereferenced through a count, so a bad count cannot fault.
+//
+// The delete-group jackknife of the same fit (ccz_jack_rcca, cca_zoo_amd/model_selection/_jackknife.py; specification:
+// tests/jack_restatement.py) shares these kernels: k_jack_downdate, further down, turns the full-sample moments into one
+// partial per replicate, in k_boot_moments' layout, for k_boot_solve.
 #include "abi_guard.h"
 #include "resample_dev.h"
 
@@ -356,11 +360,142 @@ void boot_rcca_impl(ccz_ctx* c, int64_t n, int64_t p1, int64_t p2, const double*
   });
 }
 
+// ---- the jackknife: replicate g leaves out the rows s with s % J == g (J = ngroups), so its moments are the full-sample
+// moments minus those of the few rows left out -- one pass over the data for the whole jackknife, no count matrix:
+//   G_(g) = G - sum_{s in g} x_s x_s',   s_(g) = s - sum_{s in g} x_s,   N_(g) = n - |g|.
+//
+//   k_jack_downdate grid (replicate), 256 threads.  The stacked row x = [x1 (P1, zero padded) | x2 (P2)] has P = P1 + P2 <= 128
+//                   entries; the upper triangle of x x' in 4 x 4 tiles (T = P / 4 per side, T (T + 1) / 2 <= 528 tiles, row-major)
+//                   covers G11 on and above the diagonal, all of G12 and G22 on and above the diagonal (P1 is a multiple of 16:
+//                   no tile straddles two blocks).  A thread owns tiles tid, tid + 256, tid + 512 in registers, thread a < P
+//                   column sum a.  The group's rows g, g + J, g + 2 J, ... are staged through LDS in chunks of RS_S and
+//                   accumulated with fma in row order, then part[e] = total[e] - D[e] once; N = n - |g| is an integer.  The
+//                   partial has k_boot_moments' layout; entries below the diagonal of the 11 and 22 blocks are not written
+//                   (k_boot_solve does not read them).  Plain fp64 FMAs: with one row per replicate an MFMA tile would be
+//                   1 / 32 full, and the whole jackknife's downdate is n PER FMAs, no more than one moments pass.
+constexpr int JK_LW = 2 * RS_MAXP + 4;                   // LDS row stride of a staged stacked row (16-byte aligned rows)
+constexpr int JK_TILES = 3;                              // 4 x 4 tiles per thread: 3 * 256 >= 32 * 33 / 2
+
+__global__ void __launch_bounds__(256) k_jack_downdate(const double* __restrict__ X1, const double* __restrict__ X2, int64_t n, int p1, int p2,
+                                                       int64_t ngroups, int64_t g0, const double* __restrict__ total,
+                                                       double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) double xs[RS_S * JK_LW];
+  const int tid = threadIdx.x;
+  const int P1 = 16 * ((p1 + 15) >> 4), P2 = 16 * ((p2 + 15) >> 4), P = P1 + P2, T = P >> 2;
+  const int64_t g = g0 + blockIdx.x;
+  const int64_t m = (n - g + ngroups - 1) / ngroups;     // rows of this group: g + i * ngroups < n
+  int ti[JK_TILES], tj[JK_TILES];
+#pragma unroll
+  for (int t = 0; t < JK_TILES; ++t) {                   // tile tid + 256 t of the row-major upper triangle (ti = T: none)
+    int rest = tid + 256 * t, row = 0;
+    while (row < T && rest >= T - row) { rest -= T - row; ++row; }
+    ti[t] = row;
+    tj[t] = row + rest;
+  }
+  double acc[JK_TILES][16];
+#pragma unroll
+  for (int t = 0; t < JK_TILES; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.0;
+  double ssum = 0.0;
+  const int sr = tid >> 4, sc = tid & 15;
+  for (int64_t c0 = 0; c0 < m; c0 += RS_S) {
+    __syncthreads();                                     // the previous chunk's reads
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int sl = sr + 16 * j;
+      if (c0 + sl >= m) continue;                        // rows past the group's end are neither staged nor read
+      const int64_t s = g + (c0 + sl) * ngroups;         // < n
+      const double* a = X1 + s * p1;
+      const double* b = X2 + s * p2;
+      for (int cc = sc; cc < P1; cc += 16) xs[sl * JK_LW + cc] = cc < p1 ? a[cc] : 0.0;
+      for (int cc = sc; cc < P2; cc += 16) xs[sl * JK_LW + P1 + cc] = cc < p2 ? b[cc] : 0.0;
+    }
+    __syncthreads();
+    const int rows = m - c0 < RS_S ? int(m - c0) : RS_S;
+    for (int q = 0; q < rows; ++q) {
+      const double* x = xs + q * JK_LW;
+#pragma unroll
+      for (int t = 0; t < JK_TILES; ++t) {
+        if (ti[t] >= T) continue;
+        double xa[4], xb[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          xa[i] = x[4 * ti[t] + i];
+          xb[i] = x[4 * tj[t] + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[t][4 * i + j] = fma(xa[i], xb[j], acc[t][4 * i + j]);
+      }
+      if (tid < P) ssum += x[tid];
+    }
+  }
+  const int PER = boot_per(P1, P2);
+  double* out = part + int64_t(blockIdx.x) * PER;
+#pragma unroll
+  for (int t = 0; t < JK_TILES; ++t) {
+    if (ti[t] >= T) continue;
+    const int a0 = 4 * ti[t], b0 = 4 * tj[t];            // a0 <= b0; both on one side of P1, or a0 < P1 <= b0
+    const int off = b0 < P1 ? 0 : (a0 < P1 ? P1 * P1 : P1 * P1 + P1 * P2);
+    const int ld = b0 < P1 ? P1 : P2;
+    const int ra = a0 < P1 || b0 < P1 ? a0 : a0 - P1, cb = b0 < P1 ? b0 : b0 - P1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (ti[t] == tj[t] && i > j) continue;           // below the diagonal of the 11 or 22 block
+        const int e = off + (ra + i) * ld + cb + j;
+        out[e] = total[e] - acc[t][4 * i + j];
+      }
+  }
+  const int os = P1 * P1 + P1 * P2 + P2 * P2;            // s1 at os + [0, P1), s2 at os + P1 + [0, P2): os + stacked index
+  if (tid < P) out[os + tid] = total[os + tid] - ssum;
+  if (tid == 255) out[os + P] = double(n - m);
+}
+
+void jack_rcca_impl(ccz_ctx* c, int64_t n, int64_t p1, int64_t p2, const double* X1, const double* X2, int64_t ngroups, int64_t g0,
+                    int64_t ng, double c1, double c2, int center, int64_t k, double* sv, double* W, int32_t* info) {
+  check_two_views("jack_rcca", "n, p1, p2, ng and k", k >= 1, X1 && X2 && sv && W && info, "", "ng", true, ng, n, p1, p2);
+  if (ngroups < 2 || ngroups > n) fail(CCZ_EINVAL, "jack_rcca: ngroups must lie in [2, n], got %lld with n = %lld", (long long)ngroups, (long long)n);
+  if (g0 < 0 || g0 >= ngroups || ng > ngroups - g0)
+    fail(CCZ_EINVAL, "jack_rcca: replicates [g0, g0 + ng) must lie in [0, ngroups), got g0 = %lld, ng = %lld, ngroups = %lld", (long long)g0,
+         (long long)ng, (long long)ngroups);
+  const int r = int(std::min(p1, p2));
+  if (k > r) fail(CCZ_EINVAL, "jack_rcca: k = %lld exceeds min(p1, p2) = %d", (long long)k, r);
+  const int PER = boot_per(16 * (int(p1 + 15) / 16), 16 * (int(p2 + 15) / 16));
+  const int64_t nsplit = (n + RS_ROWS - 1) / RS_ROWS;
+  const int64_t nw = (p1 + p2) * k;
+  // the full-sample moments, once per call: the all-ones resample of boot_rcca_impl, folded in split order
+  DBuf splits(c, nsplit * PER), folded(c, nsplit > 1 ? PER : 0);
+  hipLaunchKernelGGL(k_boot_moments, dim3(unsigned(nsplit), 1, 3), dim3(256), 0, stream(c), X1, X2, (const int*)nullptr, n, int(p1), int(p2),
+                     splits.get());
+  CCZ_LAUNCH_CHECK();
+  if (nsplit > 1) {
+    hipLaunchKernelGGL(k_boot_fold, dim3(unsigned((PER + 255) / 256), 1), dim3(256), 0, stream(c), splits.get(), int(nsplit), PER, folded.get());
+    CCZ_LAUNCH_CHECK();
+  }
+  const double* total = nsplit > 1 ? folded.get() : splits.get();
+  for_batches(c, ng, PER, [&](double* part, int64_t b0, int64_t nb, int64_t) {
+    hipLaunchKernelGGL(k_jack_downdate, dim3(unsigned(nb)), dim3(256), 0, stream(c), X1, X2, n, int(p1), int(p2), ngroups, g0 + b0, total, part);
+    CCZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_boot_solve, dim3(unsigned(nb)), dim3(256), 0, stream(c), part, 1, int(p1), int(p2), c1, c2, center, int(k),
+                       sv + b0 * r, W + b0 * nw, info + b0);
+    CCZ_LAUNCH_CHECK();
+  });
+}
+
 }  // namespace
 
 }  // namespace ccz
 
 extern "C" {
+
+int ccz_jack_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* X1_dev, const double* X2_dev, int64_t ngroups,
+                  int64_t g0, int64_t ng, double c1, double c2, int center, int64_t k, double* sv_dev, double* W_dev, int32_t* info_dev) {
+  CCZ_GUARD(h, ccz::jack_rcca_impl(h, n, p1, p2, X1_dev, X2_dev, ngroups, g0, ng, c1, c2, center, k, sv_dev, W_dev, info_dev));
+}
 
 int ccz_boot_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* X1_dev, const double* X2_dev,
                   const int32_t* counts_dev, int64_t nboot, double c1, double c2, int center, int64_t k, double* sv_dev,

@@ -20,7 +20,8 @@ cancellation in ``G - s s' / n``), then ``ccz_boot_rcca`` (``csrc/boot.hip``): w
 workgroup that factors, solves and runs a one-sided Jacobi SVD with vectors.  The host draws the indices with NumPy and counts
 them (``np.bincount``), one chunk ahead of the device (``_resample.py``, shared with ``_permutation.py``); with
 ``draws="device"`` the multiplicities are drawn on the device instead (``ccz_draw_counts``, ``csrc/draw.hip``), straight into the
-slot the moments read.  Signs and summaries are the host's: a sign flip is exact.
+slot the moments read.  Signs and summaries are the host's: a sign flip is exact.  With ``method="BCa"`` the delete-group
+jackknife (``_jackknife.py``, ``ccz_jack_rcca``) runs on the same shifted views and the intervals are bias-corrected and accelerated.
 """
 
 from __future__ import annotations
@@ -66,6 +67,33 @@ class BootstrapResult:
     estimator: Any                      # the clone fitted on the full views by its ordinary fit
 
 
+@dataclass
+class BCaBootstrapResult(BootstrapResult):
+    """What :func:`bootstrap` returns with ``method="BCa"``: ``singular_values_ci`` and ``weights_ci`` hold the BCa intervals;
+    ``J = n_groups`` jackknife replicates (:func:`~cca_zoo_amd.model_selection.jackknife`)."""
+
+    singular_values_ci_percentile: np.ndarray = None    # (2, r)  what method="percentile" returns as singular_values_ci
+    weights_ci_percentile: list = None                  # two (2, p_i, k)
+    singular_values_jack: np.ndarray = None             # (J, r)  replicate g: the fit without the rows s % J == g
+    weights_jack: list = None                           # two (J, p_i, k), each column aligned in sign with the observed one
+    singular_values_z0: np.ndarray = None               # (r,)    bias correction
+    weights_z0: list = None                             # two (p_i, k)
+    singular_values_acceleration: np.ndarray = None     # (r,)
+    weights_acceleration: list = None                   # two (p_i, k)
+    n_groups: int = None                                # J
+
+
+#: how the intervals are formed: the percentile interval, or the bias-corrected and accelerated one (needs a jackknife)
+METHODS = ("percentile", "BCa")
+
+
+def _jackknife():
+    """The jackknife's module, imported when first needed (it imports this one)."""
+    from cca_zoo_amd.model_selection import _jackknife as jk
+
+    return jk
+
+
 def draw_counts(rng, n, count):
     """``count`` x ``n`` multiplicities (int32): row ``b`` counts the ``b``-th ``rng.integers(0, n, size=n)``."""
     out = np.empty((count, n), dtype=np.int32)
@@ -106,6 +134,14 @@ def summaries(boot, confidence_level):
     boot = np.asarray(boot, dtype=np.float64)
     q = [(1.0 - confidence_level) / 2.0, (1.0 + confidence_level) / 2.0]
     return np.std(boot, axis=0, ddof=1), np.quantile(boot, q, axis=0)
+
+
+def check_method(method, jackknife_groups):
+    """``ValueError`` for an unknown ``method``, or ``jackknife_groups`` without the jackknife."""
+    if not (isinstance(method, str) and method in METHODS):
+        raise ValueError(f"bootstrap: method must be one of {list(METHODS)}, got {method!r}")
+    if method == "percentile" and jackknife_groups is not None:
+        raise ValueError("bootstrap: jackknife_groups needs method='BCa'; the percentile interval runs no jackknife")
 
 
 def check_limits(n, p, n_resamples, confidence_level):
@@ -153,7 +189,8 @@ def raise_for_info(info):
         raise np.linalg.LinAlgError(f"bootstrap: {which}: {INFO_CAUSES.get(code, f'info = {code}')}")
 
 
-def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_state=None, *, draws="numpy"):
+def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_state=None, *, draws="numpy", method="percentile",
+              jackknife_groups=None):
     r"""Non-parametric bootstrap of the weights and singular values of a two-view CCA, rCCA or PLS.
 
     The rows are drawn with replacement ``n_resamples`` times (n out of n); every resample is refitted on the device from
@@ -176,12 +213,22 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
             ``seed = np.random.default_rng(random_state).integers(0, 2**64, dtype=np.uint64)``.  The two settings give
             different, equally valid random resamples: the observed values are the same bits, standard errors and intervals
             differ by Monte Carlo error only.  Either setting is reproducible from ``random_state``.
+        method: ``"percentile"`` (default): the percentile interval; no jackknife runs.  ``"BCa"``: the bias-corrected and
+            accelerated interval (Efron 1987, the default of ``scipy.stats.bootstrap``; the rule is that of
+            :func:`~cca_zoo_amd.model_selection.bca_intervals`), which corrects the percentile interval's known first-order
+            bias -- sample canonical correlations are biased upward, weights near a sign flip are skewed.  It runs the
+            delete-group jackknife of :func:`~cca_zoo_amd.model_selection.jackknife` on the same device views.
+        jackknife_groups: the jackknife's ``n_groups`` (``None``: ``min(n, 4096)``); only with ``method="BCa"``.
 
     Returns:
         :class:`BootstrapResult`.  ``se = std(axis=0, ddof=1)``, ``ci = quantile(boot, [(1 - cl) / 2, (1 + cl) / 2], axis=0)``,
         ``bootstrap_ratio = weights / weights_se``.  Each observed weight column is signed so that the entry of largest
         magnitude of the stacked column ``[w1; w2]`` is positive; each resampled column so that its stacked dot product with
-        the observed column is >= 0 (the two views of a column always flip together).
+        the observed column is >= 0 (the two views of a column always flip together).  With ``method="BCa"``:
+        :class:`BCaBootstrapResult`, a subclass whose ``singular_values_ci`` and ``weights_ci`` are the BCa intervals; it keeps
+        the percentile intervals (``*_ci_percentile``) and adds the jackknife values (``*_jack``), the bias corrections
+        (``*_z0``), the accelerations (``*_acceleration``) and ``n_groups``.  An entry whose observed value lies outside its
+        bootstrap values, or whose jackknife values are all equal, has a NaN interval (one ``RuntimeWarning``).
 
     Limits of this first cut (``ValueError`` before the device is touched): ``max(p1, p2) <= 64`` -- wider views are reduced
     first (e.g. to their leading principal components); ``n < 2^31``; ``n >= 2``; ``draws`` is one of the two names.  Sparse views and half-precision views raise
@@ -189,9 +236,15 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
     covariance cannot be factored (with ``c = 0``: fewer distinct rows than columns) raises ``np.linalg.LinAlgError`` that
     names the resample and the remedy ``c > 0``.
     """
-    est, views_, n, p, c_, center, on_device = _resample.prepare(
-        "bootstrap", "refits on all rows of one device", estimator, views,
-        lambda n, p: check_limits(n, p, n_resamples, confidence_level), draws)
+    def check(n, p):
+        check_method(method, jackknife_groups)
+        if method == "BCa":
+            _jackknife().check_groups_type("jackknife_groups", jackknife_groups)
+        check_limits(n, p, n_resamples, confidence_level)
+        if method == "BCa":
+            _jackknife().resolve_groups("jackknife_groups", n, jackknife_groups)
+
+    est, views_, n, p, c_, center, on_device = _resample.prepare("bootstrap", "refits on all rows of one device", estimator, views, check, draws)
     B, r = int(n_resamples), min(p)
     k, pt = min(int(est.latent_dimensions), r), p[0] + p[1]
 
@@ -214,6 +267,9 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
                                                W.ptr + (1 + done) * pt * k * 8, info.ptr + (1 + done) * 4))
         sv_h, W_h = h.to_host(sv, (B + 1, r)), h.to_host(W, (B + 1, pt, k))
         info_h = h.to_host(info, (B + 1,), dtype=np.int32)
+        if method == "BCa":                                # on the same shifted views, before they are released
+            J = _jackknife().resolve_groups("jackknife_groups", n, jackknife_groups)
+            sv_j, W_j, info_j = _jackknife().run_replicates(h, n, p, zptr, c_, center, k, J)
     finally:
         release(h, sp)
     del x64, Z, slots
@@ -227,9 +283,23 @@ def bootstrap(estimator, views, n_resamples=1000, confidence_level=0.95, random_
     cut = [slice(0, p[0]), slice(p[0], pt)]
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = W_obs / w_se
+    fields = dict(singular_values=sv_h[0].copy(), singular_values_boot=sv_h[1:].copy(), singular_values_se=sv_se,
+                  singular_values_ci=sv_ci, weights=[W_obs[s].copy() for s in cut],
+                  weights_boot=[np.ascontiguousarray(W_boot[:, s]) for s in cut], weights_se=[w_se[s].copy() for s in cut],
+                  weights_ci=[np.ascontiguousarray(w_ci[:, s]) for s in cut], bootstrap_ratio=[ratio[s].copy() for s in cut])
+    if method == "percentile":
+        est.fit(list(views))
+        return BootstrapResult(**fields, estimator=est)
+    _jackknife().raise_for_info(info_j, "bootstrap: jackknife")
+    if not np.all(np.isfinite(sv_j)) or not np.all(np.isfinite(W_j)):
+        raise np.linalg.LinAlgError("bootstrap: the jackknife replicates' solutions are not finite")
+    W_jack = orient_to(W_j, W_obs)
+    sv_bca, sv_z0, sv_a = _jackknife().bca_intervals(fields["singular_values"], fields["singular_values_boot"], sv_j, confidence_level)
+    w_bca, w_z0, w_a = _jackknife().bca_intervals(W_obs, W_boot, W_jack, confidence_level)
+    fields.update(singular_values_ci=sv_bca, weights_ci=[np.ascontiguousarray(w_bca[:, s]) for s in cut])
     est.fit(list(views))
-    return BootstrapResult(singular_values=sv_h[0].copy(), singular_values_boot=sv_h[1:].copy(), singular_values_se=sv_se,
-                           singular_values_ci=sv_ci, weights=[W_obs[s].copy() for s in cut],
-                           weights_boot=[np.ascontiguousarray(W_boot[:, s]) for s in cut], weights_se=[w_se[s].copy() for s in cut],
-                           weights_ci=[np.ascontiguousarray(w_ci[:, s]) for s in cut], bootstrap_ratio=[ratio[s].copy() for s in cut],
-                           estimator=est)
+    return BCaBootstrapResult(**fields, estimator=est, singular_values_ci_percentile=sv_ci,
+                              weights_ci_percentile=[np.ascontiguousarray(w_ci[:, s]) for s in cut], singular_values_jack=sv_j,
+                              weights_jack=[np.ascontiguousarray(W_jack[:, s]) for s in cut], singular_values_z0=sv_z0,
+                              weights_z0=[w_z0[s].copy() for s in cut], singular_values_acceleration=sv_a,
+                              weights_acceleration=[w_a[s].copy() for s in cut], n_groups=J)

@@ -1134,7 +1134,24 @@ CCZ_API int ccz_boot_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const
                           const int32_t* counts_dev, int64_t nboot, double c1, double c2, int center, int64_t k, double* sv_dev,
                           double* W_dev, int32_t* info_dev);
 
-/* ---- the draws of the two routines above, made on the device (csrc/draw.hip) ---
+/* ---- delete-group jackknife of the same fit (csrc/boot.hip) ----------------
+ * Replicate g in [g0, g0 + ng) is the fit above on all rows EXCEPT those with s % ngroups == g (ngroups == n: leave-one-out).
+ * The groups are interleaved, so rows sorted by class do not put a whole stratum into one group; group sizes differ by at
+ * most 1.  In exact arithmetic replicate g equals ccz_boot_rcca with the 0/1 counts m[s] = (s % ngroups != g); here its moments
+ * are the full-sample moments (one pass per call, the all-ones resample of ccz_boot_rcca) minus those of the rows left out,
+ *   G_(g) = G - sum_{s in g} x_s x_s',   s_(g) = s - sum_{s in g} x_s,   N_(g) = n - |g|,
+ * one workgroup per replicate (plain fp64 FMAs in row order, subtracted once), then the solve of ccz_boot_rcca unchanged: no
+ * count matrix, and the whole jackknife reads the data twice.  sv_dev (ng x r), W_dev (ng x (p1 + p2) x k), info_dev (ng): row i
+ * is replicate g0 + i; layouts, the coupled sign, CCZ_BOOT_INFO_* and NaN rows as above.  No floating-point atomics and every
+ * sum in a fixed order: the bits of replicate g depend on (X, ngroups, g, c, center, k) only -- not on g0 or ng.  With center
+ * set, pass views whose column means are near zero, as above.  Enqueue-only on the handle's stream.
+ * CCZ_EUNSUP: p_i > 64 or n >= 2^31;  CCZ_EINVAL: n, p_i, ng, k < 1, k > r, a null pointer, ngroups < 2, ngroups > n, g0 < 0 or
+ * g0 + ng > ngroups. */
+CCZ_API int ccz_jack_rcca(ccz_handle h, int64_t n, int64_t p1, int64_t p2, const double* X1_dev, const double* X2_dev,
+                          int64_t ngroups, int64_t g0, int64_t ng, double c1, double c2, int center, int64_t k, double* sv_dev,
+                          double* W_dev, int32_t* info_dev);
+
+/* ---- the draws of ccz_perm_singular_values and ccz_boot_rcca, made on the device (csrc/draw.hip) ---
  * Pure functions of (seed, b, n), b = the resample's index in the whole call (row i of a call is resample first + i), on
  * the stream convention of the ccz_svi_* and ccz_nuts_* sections (all arithmetic uint64, wrapping):
  *   stream(seed, b, site) = splitmix64(splitmix64(splitmix64(seed) + b) + site)
